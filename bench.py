@@ -254,7 +254,26 @@ def attach_profile(out, name, alg_bytes, loaded, profiles_dir=None):
                                            % (out["roofline"]["traffic_lower_bound"] / alg_bytes, out["roofline"]["traffic"] / alg_bytes, 100 * d.get("L2_hit_rate", 0), busy))
 
 
-def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps, warmup, with_cpu, dump_film=None):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rgb, alpha):
+    """--dump-outputs: the resolved film of the last timed step, what a caller of the timed path receives, as float32 .npy files.  A film
+    above DUMP_LIMIT_BYTES is written as a fixed sample of pixels (seed 0, same sample for the same film size) with their flat indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = np.ascontiguousarray(rgb, np.float32); alpha = np.ascontiguousarray(alpha, np.float32)
+    H, W = alpha.shape
+    arrays = {"rgb": rgb, "alpha": alpha}
+    if rgb.nbytes + alpha.nbytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (4 * 3 + 4 + 8)                      # rgb + alpha (float32) + the pixel index (float64) per sampled pixel
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        arrays = {"rgb": rgb.reshape(-1, 3)[idx], "alpha": alpha.reshape(-1)[idx], "pixel_index": idx.astype(np.float64)}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps, warmup, with_cpu, dump_film=None, dump_dir=None):
     """Render `steps` timed frames of one workload on this rank's shard; rank 0 returns the record (others None)."""
     import numpy as np
     text, label, crop = workload(name)
@@ -396,6 +415,13 @@ def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps,
         stats.append(ds.last_stats())       # HIP events around the kernels on their stream
     fence()
     elapsed = time.perf_counter() - t0
+    last_out = None
+    if dump_dir and rank == 0:                                   # the last timed step's resolved film, off the device before the hand-over loop renders again
+        if merge == "reduce_scatter":
+            rgba = rgba_all[:H].cpu().numpy()
+            last_out = (rgba[..., :3], rgba[..., 3])
+        else:
+            last_out = (rgb_dev.cpu().numpy(), alpha_dev.cpu().numpy())
     # the same frames with the hand-over to host memory at the end of each (PCIe): reported beside the device-resident figure, never as `value`
     t1 = time.perf_counter()
     for _ in range(steps):
@@ -422,6 +448,8 @@ def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps,
     if rank == 0:
         if dump_film:
             np.savez(dump_film, rgb=host_rgb, alpha=host_alpha)
+        if last_out is not None:
+            dump_outputs(dump_dir, *last_out)
         ms_per_step = elapsed / steps * 1e3
         # the dominant kernel: rt::render_kernel (megakernel) or the rt::pipe_trace_kernel launches of the queue pipeline
         k_ms = k_ms_local
@@ -524,6 +552,9 @@ def main():
     # (10 M triangles, 2048 x 2048 @ 256 spp, "tiles over 8 x MI355X") at 8 ranks, C5 ("4 MI355X") at 4 and 8 ranks
     ap.add_argument("--multi-workloads", default="auto")
     ap.add_argument("--dump-film", default=None, help="rank 0 writes the last resolved film of the headline workload here (.npz)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the resolved film of the headline workload's last timed step as DIR/rgb.npy and DIR/alpha.npy (float32; "
+                         "a film over 64 MB as a fixed seeded pixel sample plus DIR/pixel_index.npy)")
     # 48: with the 1028-pixel sample rows of the default frame, 64-pixel tiles give 16.06 tiles per row, so one rank owns the
     # same columns for ~16 consecutive rows and whole 16x16 film-gather blocks fall to a single rank (measured at 8 ranks:
     # rank share 10.06 ms with 64, 9.61 ms with 48)
@@ -535,6 +566,8 @@ def main():
     ap.add_argument("--merge", choices=["allreduce", "reduce_scatter"], default="reduce_scatter")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even for one rank: exercises the N > 1 code path on a single GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")             # dmabuf IPC only on these hosts: without it RCCL's buffer exchange fails with hipIpcGetMemHandle errors
     import torch
@@ -577,7 +610,7 @@ def main():
                 backend, rank, world, os.environ.get("MASTER_ADDR"), os.environ.get("MASTER_PORT"), type(e).__name__, e))
 
     out = run_workload(args.workload, args, pkg, torch, dist, world, rank, device_index, args.steps, args.warmup,
-                       with_cpu=not args.no_cpu_baseline, dump_film=args.dump_film)
+                       with_cpu=not args.no_cpu_baseline, dump_film=args.dump_film, dump_dir=args.dump_outputs)
     if world > 1:
         multi = ({8: "c4full,c5", 4: "c5"}.get(world, "") if args.workload == HEADLINE else "") if args.multi_workloads == "auto" else args.multi_workloads
         extras = [] if args.no_extra else [w for w in multi.split(",") if w]

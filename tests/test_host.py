@@ -348,6 +348,28 @@ def test_bench_scene_texts_for_the_tuned_tree_and_the_parity_leg(pkg):
     assert bench.workload("tsmall_tuned")[0] == tuned
 
 
+def test_bench_dump_outputs_whole_film_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a film within the limit is written whole as float32 rgb.npy / alpha.npy; a larger one as the same seeded pixel sample
+    every time, with the flat pixel indices (float64, exact) beside it, the whole dump within the limit."""
+    import bench
+    rng = np.random.default_rng(5)
+    rgb = rng.random((30, 40, 3), dtype=np.float32); alpha = rng.random((30, 40), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), rgb, alpha)
+    r, a = np.load(tmp_path / "whole" / "rgb.npy"), np.load(tmp_path / "whole" / "alpha.npy")
+    assert r.dtype == a.dtype == np.float32 and np.array_equal(r, rgb) and np.array_equal(a, alpha)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["alpha.npy", "rgb.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4800)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), rgb, alpha)
+    files = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in ("rgb", "alpha", "pixel_index")}
+    assert sum(v.nbytes for v in files.values()) <= 4800 and files["pixel_index"].dtype == np.float64
+    idx = files["pixel_index"].astype(np.int64)
+    assert len(idx) == 200 and len(np.unique(idx)) == len(idx) and idx.max() < 30 * 40
+    assert np.array_equal(files["rgb"], rgb.reshape(-1, 3)[idx]) and np.array_equal(files["alpha"], alpha.reshape(-1)[idx])
+    for k, v in files.items():
+        assert np.array_equal(v, np.load(tmp_path / "s2" / (k + ".npy"))), k
+
+
 def _walk_leaf(tn_x, tn_y, entries, stride, runs):
     """A leaf's record slots in test order, decoded exactly as the kernels do (rt_traverse.h leaf_cursor_enter / leaf_test_flat)."""
     MORE, LIST, POS, NONE = 0x80000000, 0x40000000, 0x3fffffff, 0xffffffff
