@@ -12,6 +12,10 @@ Scene::IntersectP call (camera, bounce, MIS closest-hit and shadow rays), the me
 Scene data is resident in HBM before the timed region; the frame is fixed, so N > 1 is strong scaling
 (image tiles dealt round-robin to ranks).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: scene set-up, one counted frame (the ray count
+`value` is priced on), W warm-up and K timed steps, --dump-outputs, and the line with `roofline` and `per_rank`.  Everything else runs only
+with `--full`: the `host_handover` loop, `cpu_baseline` (null in a plain run), `parity` and the `workloads` sub-records.
+
 Prints ONE JSON line on rank 0 (see the contract in the task description) including
   roofline     : algorithmic bytes (8 B/node visit + 4 B/leaf ref + 48 B/triangle test + 48 B/ray,
                  SURVEY.md section 8d) of one frame / the HIP-event duration of the dominant kernel
@@ -273,8 +277,9 @@ def dump_outputs(out_dir, rgb, alpha):
         np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
-def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps, warmup, with_cpu, dump_film=None, dump_dir=None):
-    """Render `steps` timed frames of one workload on this rank's shard; rank 0 returns the record (others None)."""
+def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps, warmup, with_cpu, dump_film=None, dump_dir=None, handover_loop=True):
+    """Render `steps` timed frames of one workload on this rank's shard; rank 0 returns the record (others None).  `handover_loop`: time the
+    same steps again with the hand-over to host memory (`host_handover`)."""
     import numpy as np
     text, label, crop = workload(name)
     ps = pkg.ParsedScene(text=text)
@@ -423,11 +428,15 @@ def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps,
         else:
             last_out = (rgb_dev.cpu().numpy(), alpha_dev.cpu().numpy())
     # the same frames with the hand-over to host memory at the end of each (PCIe): reported beside the device-resident figure, never as `value`
-    t1 = time.perf_counter()
-    for _ in range(steps):
-        step(); handover()
-    fence()
-    elapsed_host = time.perf_counter() - t1
+    elapsed_host = 0.0
+    if handover_loop:
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            step(); handover()
+        fence()
+        elapsed_host = time.perf_counter() - t1
+    elif dump_film:
+        handover()                                              # --dump-film without the loop: the last timed step's resolved film
     rays_local = cnt["closest_rays"] + cnt["any_rays"]
     if os.environ.get("PBRT_BENCH_COUNTERS"):
         print("COUNTERS " + json.dumps({k: int(v) for k, v in cnt.items()}), file=sys.stderr, flush=True)
@@ -467,9 +476,9 @@ def run_workload(name, args, pkg, torch, dist, world, rank, device_index, steps,
             "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": round(ms_per_step, 3),
             "s_per_frame": round(ms_per_step / 1e3, 5),
-            "host_handover": {"ms_per_step": round(elapsed_host / steps * 1e3, 3), "value": round(rays_total * steps / elapsed_host / 1e6, 3),
-                              "note": "the same steps with the resolved film copied to page-locked host memory at the end of each (rank 0, %d x %d x 4 floats over PCIe); "
-                                      "`value` and `ms_per_step` end with the resolved film in device memory" % (W, H)},
+            **({"host_handover": {"ms_per_step": round(elapsed_host / steps * 1e3, 3), "value": round(rays_total * steps / elapsed_host / 1e6, 3),
+                                  "note": "the same steps with the resolved film copied to page-locked host memory at the end of each (rank 0, %d x %d x 4 floats over PCIe); "
+                                          "`value` and `ms_per_step` end with the resolved film in device memory" % (W, H)}} if handover_loop else {}),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -544,11 +553,14 @@ def main():
     # the headline is the LARGEST stated single-GPU configuration of BASELINE.json: configs[2] (C3: 1 M-triangle soup, DirectLighting,
     # 1920x1080 @ 16 spp).  configs[1] (C2, Cornell) is cache-resident and VALU-bound; it is reported as a sub-record.
     ap.add_argument("--workload", default=HEADLINE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    # the other BASELINE.json configs at the size one GPU holds, reported as full sub-records in "workloads" (N = 1 only)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the host hand-over loop, the reference-CPU and parity legs, and the sub-records of the other "
+                         "configurations (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the reference-CPU and parity legs")
+    # --full: the other BASELINE.json configs at the size one GPU holds, reported as full sub-records in "workloads" (N = 1 only)
     ap.add_argument("--extra-workloads", default="c2,p1000000,c4,c5,c3_tuned,p1000000_tuned,c4full")
-    ap.add_argument("--no-extra", action="store_true")
-    # N > 1: the configurations BASELINE.json states for several GPUs, as sub-records with `per_rank` next to the headline: "auto" = C4 as stated
+    ap.add_argument("--no-extra", action="store_true", help="--full without the sub-records")
+    # --full, N > 1: the configurations BASELINE.json states for several GPUs, as sub-records with `per_rank` next to the headline: "auto" = C4 as stated
     # (10 M triangles, 2048 x 2048 @ 256 spp, "tiles over 8 x MI355X") at 8 ranks, C5 ("4 MI355X") at 4 and 8 ranks
     ap.add_argument("--multi-workloads", default="auto")
     ap.add_argument("--dump-film", default=None, help="rank 0 writes the last resolved film of the headline workload here (.npz)")
@@ -610,12 +622,14 @@ def main():
                 backend, rank, world, os.environ.get("MASTER_ADDR"), os.environ.get("MASTER_PORT"), type(e).__name__, e))
 
     out = run_workload(args.workload, args, pkg, torch, dist, world, rank, device_index, args.steps, args.warmup,
-                       with_cpu=not args.no_cpu_baseline, dump_film=args.dump_film, dump_dir=args.dump_outputs)
-    if world > 1:
-        multi = ({8: "c4full,c5", 4: "c5"}.get(world, "") if args.workload == HEADLINE else "") if args.multi_workloads == "auto" else args.multi_workloads
-        extras = [] if args.no_extra else [w for w in multi.split(",") if w]
-    else:
-        extras = [] if (args.no_extra or args.workload != HEADLINE) else [w for w in args.extra_workloads.split(",") if w]
+                       with_cpu=args.full and not args.no_cpu_baseline, dump_film=args.dump_film, dump_dir=args.dump_outputs, handover_loop=args.full)
+    extras = []
+    if args.full and not args.no_extra:
+        if world > 1:
+            multi = ({8: "c4full,c5", 4: "c5"}.get(world, "") if args.workload == HEADLINE else "") if args.multi_workloads == "auto" else args.multi_workloads
+            extras = [w for w in multi.split(",") if w]
+        elif args.workload == HEADLINE:
+            extras = [w for w in args.extra_workloads.split(",") if w]
     records = []
     for w in extras:
         # a sub-record must never cost the headline: whatever goes wrong in an extra workload (memory, a collective timing out) is recorded in its place

@@ -58,7 +58,7 @@ def test_a_failing_sub_workload_does_not_cost_the_headline(pkg):
     if pkg.device_count() < 1:
         pytest.fail("no HIP device visible")
     env = dict(os.environ, PBRT_BENCH_BACKEND="gloo", PBRT_BENCH_SAME_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    j = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "tsmall", "--multi-workloads", "t5,nosuchworkload,t8", "--no-cpu-baseline", "--tile-2d", "16"], env, nproc=2)
+    j = _bench(["--gpus", "2", "--full", "--steps", "1", "--warmup", "0", "--workload", "tsmall", "--multi-workloads", "t5,nosuchworkload,t8", "--no-cpu-baseline", "--tile-2d", "16"], env, nproc=2)
     assert j["n_gpus"] == 2 and j["value"] > 0
     w = j["workloads"]
     assert [x["workload"] for x in w] == ["t5", "nosuchworkload"] and w[0]["value"] > 0 and len(w[0]["per_rank"]) == 2 and "unknown workload" in w[1]["error"]
@@ -79,6 +79,24 @@ def test_single_rank_rccl_process_group(pkg, tmp_path):
         assert j2["config"]["rays_per_frame"] == j1["config"]["rays_per_frame"]
         a, b = np.load(one), np.load(two)
         assert np.array_equal(a["rgb"], b["rgb"]) and np.array_equal(a["alpha"], b["alpha"]), merge
+
+
+def test_plain_run_times_the_headline_only(pkg, tmp_path):
+    """A plain bench.py run prints the headline without the host hand-over loop, the reference-CPU leg or sub-records; --full adds them.  Both
+    time the same frame: same rays, and --dump-film writes the same film (plain: the last timed step's, --full: the last hand-over frame's)."""
+    if pkg.device_count() < 1:
+        pytest.fail("no HIP device visible")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    plain, full = str(tmp_path / "plain.npz"), str(tmp_path / "full.npz")
+    base = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tsmall"]
+    jp = _bench(base + ["--dump-film", plain], env)
+    jf = _bench(base + ["--dump-film", full, "--full", "--no-cpu-baseline"], env)
+    assert "host_handover" not in jp and "workloads" not in jp and "parity" not in jp and jp["cpu_baseline"] is None
+    assert jp["value"] > 0 and jp["ms_per_step"] > 0 and jp["roofline"]["kernel_ms"] > 0
+    assert jf["host_handover"]["value"] > 0
+    assert jp["config"]["rays_per_frame"] == jf["config"]["rays_per_frame"]
+    a, b = np.load(plain), np.load(full)
+    assert a["rgb"].max() > 0 and np.array_equal(a["rgb"], b["rgb"]) and np.array_equal(a["alpha"], b["alpha"])
 
 
 def test_prebuilt_accelerator_gives_the_same_scene(pkg, scenes, tmp_path):
@@ -136,7 +154,7 @@ def test_four_ranks_on_one_gpu_rehearsal(pkg, tmp_path):
         pytest.fail("no HIP device visible")
     env = dict(os.environ, PBRT_BENCH_BACKEND="gloo", PBRT_BENCH_SAME_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     one, four = str(tmp_path / "one.npz"), str(tmp_path / "four.npz")
-    base = ["--steps", "1", "--warmup", "0", "--workload", "tsmall", "--multi-workloads", "t8,t5", "--no-cpu-baseline", "--tile-2d", "16", "--merge", "reduce_scatter"]
+    base = ["--full", "--steps", "1", "--warmup", "0", "--workload", "tsmall", "--multi-workloads", "t8,t5", "--no-cpu-baseline", "--tile-2d", "16", "--merge", "reduce_scatter"]
     j4 = _bench(["--gpus", "4", "--dump-film", four] + base, env, nproc=4, timeout=2400)
     assert j4["n_gpus"] == 4 and len(j4["per_rank"]) == 4
     assert [w["workload"] for w in j4["workloads"]] == ["t8", "t5"]

@@ -14,10 +14,10 @@ rnd, tag = sys.argv[1], sys.argv[2]
 publish = "--publish" in sys.argv[3:]
 src = os.path.join(ROOT, "gpurun_out", "prof_%s_%s" % (rnd, tag))
 wl = tag.split("_pipe")[0]
-FRAMES = 8          # bench.py --steps 3 --warmup 1: 1 counted (counting twin) + 1 warm-up + 3 timed + 3 host-hand-over frames
+FRAMES = 8          # bench.py --full --steps 3 --warmup 1: 1 counted (counting twin) + 1 warm-up + 3 timed + 3 host-hand-over frames
 code_id = entry.load_package().code_id()
 out = {"workload": wl, "round": rnd, "code_id": code_id,
-       "command": "rocprofv3 --kernel-trace --stats | --pmc <group> (one group per run) -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra --workload " + wl,
+       "command": "rocprofv3 --kernel-trace --stats | --pmc <group> (one group per run) -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra --workload " + wl,
        "frames_per_run": FRAMES, "kernels": {}, "pmc_per_frame": {}}
 KERNELS = ("render_kernel", "pipe_trace", "pipe_shade", "pipe_vertex", "pipe_march", "film_slot", "film_march", "film_gather", "derive_")
 for f in glob.glob(os.path.join(src, "trace", "**", "*kernel_stats.csv"), recursive=True):
