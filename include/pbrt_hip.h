@@ -86,6 +86,20 @@ typedef struct RtVolume {
     float g;
 } RtVolume;
 
+/* ---- density media: DensityRegion (core/volume.h:62-90, core/volume.cpp:137-153) with ExponentialDensity
+ * (volumes/exponential.cpp:27-69) or VolumeGrid (volumes/volumegrid.cpp:27-110).  Kept out of RtVolume and
+ * RtSceneDesc so that their byte images stay those of every scene without one: RtVolume still carries
+ * world_to_volume, the extent p0 / p1, sigma_a, sigma_s, Le and g, and this record names how the density
+ * Density(WorldToVolume(p)) scales them.  Handed over with rt_scene_set_density. ---- */
+enum { RT_DENSITY_NONE = 0, RT_DENSITY_EXPONENTIAL = 1, RT_DENSITY_GRID = 2 };
+typedef struct RtDensityRegion {
+    int32_t kind;          /* RT_DENSITY_*                                                                     */
+    float a, b;            /* exponential: a * expf(-b * Dot(Pobj - pMin, updir)) inside the extent             */
+    float updir[3];        /* exponential: Normalize(updir), as the constructor stores it                       */
+    int32_t nx, ny, nz;    /* grid: voxel counts, nx*ny*nz > 0 and below 2^31                                  */
+    const float *density;  /* grid: [nz][ny][nx] (density[z*nx*ny + y*nx + x]); caller-owned, copied by the call */
+} RtDensityRegion;
+
 /* ---- accelerator parameters: accelerators/kdtree.cpp:489-498, grid.cpp:431-434 ---- */
 enum { RT_ACCEL_KDTREE = 0, RT_ACCEL_GRID = 1 };
 typedef struct RtAccelParams {
@@ -242,6 +256,18 @@ typedef struct RtPrebuiltAccel {
     int32_t grid_nvoxels[3]; float grid_width[3], grid_inv_width[3];   /* grid only (RtAccelInfo) */
 } RtPrebuiltAccel;
 int rt_scene_create_prebuilt(const RtSceneDesc *desc, int device, const RtPrebuiltAccel *accel, RtScene **out);
+/* Make the scene's medium a DensityRegion: what pbrtVolume (core/api.cpp:403-409) keeps when MakeVolumeRegion
+ * (core/dynload.cpp:365-375) returns an ExponentialDensity or a VolumeGrid.  Call once, after rt_scene_create or
+ * rt_scene_create_prebuilt and before the first rt_render; the scene's RtVolume (desc->volume) must be present and
+ * supplies the transform, the extent and the constants.  A grid is copied to device memory (the library owns it;
+ * `region->density` may be freed on return).  Frames of such a scene run the EXT kernels, whose optical depth is
+ * DensityRegion::Tau's ray march (volume.cpp:137-153) at the reference's three call sites: .5f * stepSize per march step
+ * (emission.cpp:82-83, single.cpp:83-84), 4.f * stepSize for Scene::Transmittance (scene.cpp:127-129) and stepSize
+ * with the sampler's tau value for Scene::Li's T (scene.cpp:120-126).
+ * Returns RT_EINVAL (null argument, unknown kind, no medium in the scene, grid counts not positive or
+ * nx*ny*nz >= 2^31, null grid), RT_ESTATE (called twice, or after rt_render), RT_EDEVICE (upload failed);
+ * rt_last_error() says which. */
+int rt_scene_set_density(RtScene *s, const RtDensityRegion *region);
 int rt_scene_destroy(RtScene *s);
 int rt_scene_set_stream(RtScene *s, void *hip_stream);
 int rt_scene_accel_info(const RtScene *s, RtAccelInfo *info);
@@ -293,7 +319,11 @@ int rt_film_read(RtScene *s, float *host_accum);          /* 5*W*H floats, synch
 int rt_film_resolve(RtScene *s, int premultiply_alpha, float *rgb_out, float *alpha_out);
 
 /* Scene::Render's sample loop (scene.cpp:42-84) for this shard, asynchronous on the
- * handle's stream.  rt_sync waits.  Counters accumulate until rt_counters_reset. */
+ * handle's stream.  rt_sync waits.  Counters accumulate until rt_counters_reset.
+ * With a medium the frame is refused (RT_EINVAL, before any launch) when a march needs more than 65536 steps; with a
+ * density region also when an optical-depth march could take more than 2^20 samples of .5f * stepSize across the
+ * volume's world bound, or when a ray parameter t within the union of the scene bound, the camera position and that
+ * world bound is so large that t + .5f * stepSize == t (DensityRegion::Tau's loop would not advance). */
 int rt_render(RtScene *s, const RtRenderDesc *rd);
 int rt_sync(RtScene *s);
 /* per-camera-sample results of the last rt_render, before filtering: out[count][8] = L.rgb, alpha, imageX, imageY, 0, 0 in the

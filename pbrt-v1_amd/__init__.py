@@ -141,6 +141,18 @@ class RtRenderStats(C.Structure):
         return {n: (list(getattr(self, n)) if n == "weighted_ms" else getattr(self, n)) for n, _ in self._fields_}
 
 
+class RtVolume(C.Structure):
+    _fields_ = [("present", C.c_int32), ("world_to_volume", C.c_float * 16), ("p0", C.c_float * 3), ("p1", C.c_float * 3),
+                ("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3), ("le", C.c_float * 3), ("g", C.c_float)]
+
+
+class RtDensityRegion(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("updir", C.c_float * 3),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("density", C.POINTER(C.c_float))]
+
+
+RT_DENSITY_NAMES = {1: "exponential", 2: "volumegrid"}
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -187,9 +199,10 @@ def hip_lib():
                      "rt_counters_reset", "rt_last_render_ms", "rt_last_render_stats", "rt_samples_read", "rt_device_count", "rt_set_counting",
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
-                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout"):
+                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_scene_create_prebuilt.argtypes = [C.c_void_p, C.c_int, C.POINTER(RtPrebuiltAccel), C.POINTER(C.c_void_p)]
         L.rt_scene_destroy.argtypes = [C.c_void_p]
         L.rt_scene_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -264,6 +277,10 @@ def host_lib():
         L.pbrt_host_format_iota.argtypes = [C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong]
         L.pbrt_host_accel_params.restype = C.c_void_p
         L.pbrt_host_accel_params.argtypes = [C.c_void_p]
+        L.pbrt_host_volume.restype = C.POINTER(RtVolume)
+        L.pbrt_host_volume.argtypes = [C.c_void_p]
+        L.pbrt_host_density_desc.restype = C.POINTER(RtDensityRegion)
+        L.pbrt_host_density_desc.argtypes = [C.c_void_p, C.c_int]
         _host = L
     return _host
 
@@ -507,6 +524,31 @@ class ParsedScene:
                 "step_size": float(a[4:5].view(np.float32)[0]), "sampler": int(a[5]), "x_samples": int(a[6]), "y_samples": int(a[7]),
                 "jitter": int(a[8]), "pixel_samples": int(a[9]), "seed": int(a[10:11].view(np.uint32)[0])}
 
+    def volume(self) -> dict | None:
+        """The frame's medium as RtVolume carries it (include/pbrt_hip.h), or None without one: world_to_volume (4x4, row-major), the
+        extent p0 / p1, sigma_a, sigma_s, Le, g, and `density`: the DensityRegion handed to rt_scene_set_density (kind "exponential" with
+        a, b and the normalised updir, or "volumegrid" with nx, ny, nz and the values [nz][ny][nx]), None for a homogeneous medium."""
+        v = host_lib().pbrt_host_volume(self.scene_desc).contents
+        if not v.present:
+            return None
+        out = {"world_to_volume": np.array(v.world_to_volume, np.float32).reshape(4, 4), "p0": list(v.p0), "p1": list(v.p1),
+               "sigma_a": list(v.sigma_a), "sigma_s": list(v.sigma_s), "le": list(v.le), "g": float(v.g), "density": None}
+        dp = self.density_desc()
+        if dp:
+            d = dp.contents
+            dens = {"kind": RT_DENSITY_NAMES[d.kind]}
+            if d.kind == 1:
+                dens.update(a=float(d.a), b=float(d.b), updir=[float(x) for x in d.updir])
+            else:
+                dens.update(nx=int(d.nx), ny=int(d.ny), nz=int(d.nz),
+                            values=np.ctypeslib.as_array(d.density, shape=(d.nz, d.ny, d.nx)).copy())
+            out["density"] = dens
+        return out
+
+    def density_desc(self):
+        """Pointer to the frame's RtDensityRegion (pbrt_host_density_desc), or a null pointer when the medium is homogeneous or absent."""
+        return host_lib().pbrt_host_density_desc(self._h, self.frame)
+
     def kdtree(self):
         """The kd-tree rt_scene_create would build for this scene, built on the host only."""
         return build_kdtree(self.tri_verts(), self.accel_params_ptr())
@@ -558,6 +600,13 @@ class DeviceScene:
             for i in range(3):
                 pa.grid_nvoxels[i] = info.grid_nvoxels[i]; pa.grid_width[i] = info.grid_width[i]; pa.grid_inv_width[i] = info.grid_inv_width[i]
             _chk(hip_lib().rt_scene_create_prebuilt(parsed.scene_desc, device, C.byref(pa), C.byref(self._s)))
+        dens = parsed.density_desc()
+        if dens:                                  # an exponential / volumegrid medium: DensityRegion on top of the scene's RtVolume
+            rc = hip_lib().rt_scene_set_density(self._s, dens)
+            if rc != 0:
+                err = hip_lib().rt_last_error().decode(errors="replace")
+                hip_lib().rt_scene_destroy(self._s); self._s = C.c_void_p()
+                raise RtError("rt_scene_set_density failed (%d): %s" % (rc, err))
         self._film_bound = False
 
     def accel_info(self) -> RtAccelInfo:

@@ -95,6 +95,11 @@ struct DevScene {
     float gwidth[3], ginv_width[3];
     RtCamera cam;
     RtVolume vol;
+    // the medium as a DensityRegion (rt_scene_set_density; read only by the EXT kernels): RT_DENSITY_NONE = homogeneous
+    int dens_kind;
+    float dens_a, dens_b, dens_up[3];      // ExponentialDensity (exponential.cpp:27-52)
+    int dens_n[3];                         // VolumeGrid (volumegrid.cpp:27-84): nx, ny, nz and density[z*nx*ny + y*nx + x]
+    const float *dens_grid;
 };
 
 #define RT_INTEG_DIRECT_WEIGHTED 3    // device-side template value only: DirectLighting with strategy "weighted" (render_kernel family g_render_kernels_weighted)
@@ -152,6 +157,7 @@ struct DevFrame {
     int wt_mixed;
     unsigned wt_nd;                 // number of drawing lights
     const unsigned *wt_recbase;     // [total_work + 1], float offsets into wt_rec
+    int dens_cap;                   // density region: no DensityRegion::Tau march takes more samples (rt_render bounds it by the volume's world diagonal)
 #ifdef RT_TAIL_PROBE
     unsigned long long *probe;      // -DRT_TAIL_PROBE builds (tools/build_variant.py): per megakernel wave {start, work list found empty, end} in 10 ns ticks + samples taken
 #endif

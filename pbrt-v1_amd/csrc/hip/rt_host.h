@@ -88,6 +88,9 @@ struct RtScene {
     float *resolve_buf = nullptr; size_t resolve_cap = 0;
     float *vol_buf = nullptr; size_t vol_cap = 0;          // volume scratch: rays | state | samp
     RtVolume volume{};
+    int density_kind = RT_DENSITY_NONE;                    // rt_scene_set_density
+    double vol_world[6] = {0, 0, 0, 0, 0, 0};             // density region: the volume's world bound (WorldToVolume^-1 of its extent)
+    bool rendered = false;                                 // an rt_render has been accepted
     int spill_depth = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_timing = false;

@@ -405,11 +405,69 @@ RT_DEV V3 vol_transmittance(const RtVolume &v, V3 o, V3 d, float mint, float max
     const V3 tau = (mat_color(v.sigma_a) + mat_color(v.sigma_s)) * dist;
     return mk3(expf(-tau.x), expf(-tau.y), expf(-tau.z));
 }
-// Scene::Transmittance(ray) (scene.cpp:127-129): sample == NULL => one RandomFloat() for the (unused) offset
-template <bool VOL>
-RT_DEV V3 scene_transmittance(const DevScene &sc, Lane &ln, V3 o, V3 d, float mint, float maxt) {
+// ---- density media: DensityRegion (core/volume.h:62-90) with ExponentialDensity or VolumeGrid (DevScene::dens_kind, set by rt_scene_set_density).
+// Only the EXT kernels carry this code; the medium's kind is uniform over the frame, so every branch on it is wave-uniform.
+RT_DEV float lerp_ref(float t, float v1, float v2) { return (1.f - t) * v1 + t * v2; }          // Lerp, pbrt.h:549-551
+RT_DEV int clamp_ref(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }          // Clamp(int), pbrt.h:557-561
+// Density(Pobj), Pobj in volume space: exponential.cpp:44-48, volumegrid.cpp:56-85, float32 in the reference's order of operations.  A grid
+// lookup is eight 4-byte gathers, all issued before the first one is used (the lerps wait on them together, not one HBM round trip each).
+RT_DEV float density_at(const DevScene &sc, V3 q) {
+    const RtVolume &v = sc.vol;
+    if (!(q.x >= v.p0[0] && q.x <= v.p1[0] && q.y >= v.p0[1] && q.y <= v.p1[1] && q.z >= v.p0[2] && q.z <= v.p1[2])) return 0.f;   // extent.Inside
+    if (sc.dens_kind == RT_DENSITY_EXPONENTIAL) {
+        const float height = (q.x - v.p0[0]) * sc.dens_up[0] + (q.y - v.p0[1]) * sc.dens_up[1] + (q.z - v.p0[2]) * sc.dens_up[2];
+        return sc.dens_a * expf(-sc.dens_b * height);
+    }
+    const int nx = sc.dens_n[0], ny = sc.dens_n[1], nz = sc.dens_n[2];
+    const float voxx = (q.x - v.p0[0]) / (v.p1[0] - v.p0[0]) * float(nx) - .5f;
+    const float voxy = (q.y - v.p0[1]) / (v.p1[1] - v.p0[1]) * float(ny) - .5f;
+    const float voxz = (q.z - v.p0[2]) / (v.p1[2] - v.p0[2]) * float(nz) - .5f;
+    const int vx = int(floorf(voxx)), vy = int(floorf(voxy)), vz = int(floorf(voxz));            // Floor2Int without FAST_INT: (int)floor
+    const float dx = voxx - float(vx), dy = voxy - float(vy), dz = voxz - float(vz);
+    const int x0 = clamp_ref(vx, 0, nx - 1), x1 = clamp_ref(vx + 1, 0, nx - 1);                  // D(): indices clamped to the grid (:40-45)
+    const int y0 = clamp_ref(vy, 0, ny - 1), y1 = clamp_ref(vy + 1, 0, ny - 1);
+    const int z0 = clamp_ref(vz, 0, nz - 1), z1 = clamp_ref(vz + 1, 0, nz - 1);
+    const float RT_G *g = RT_GPTR(const float, sc.dens_grid);
+    const int r00 = z0 * nx * ny + y0 * nx, r10 = z0 * nx * ny + y1 * nx, r01 = z1 * nx * ny + y0 * nx, r11 = z1 * nx * ny + y1 * nx;
+    const float c000 = g[r00 + x0], c100 = g[r00 + x1], c010 = g[r10 + x0], c110 = g[r10 + x1];
+    const float c001 = g[r01 + x0], c101 = g[r01 + x1], c011 = g[r11 + x0], c111 = g[r11 + x1];
+    const float d00 = lerp_ref(dx, c000, c100), d10 = lerp_ref(dx, c010, c110);
+    const float d01 = lerp_ref(dx, c001, c101), d11 = lerp_ref(dx, c011, c111);
+    const float d0 = lerp_ref(dy, d00, d10), d1 = lerp_ref(dy, d01, d11);
+    return lerp_ref(dz, d0, d1);
+}
+// DensityRegion::Tau(r, step, u) (volume.cpp:137-153): the ray normalised (Vector::operator/ multiplies by 1.f / length) with mint / maxt scaled,
+// clipped against the extent in volume space, then tau += sigma_t(rn(t0)) every `step` from t0 + u * step while t0 < t1; returns tau * step.
+// sigma_t(p) = Density(WorldToVolume(p)) * (sig_a + sig_s).  The loop is also capped at DevFrame::dens_cap samples (rt_render bounds the march by
+// the volume's world diagonal and refuses frames where t + step would not advance): a value that slips through ends the loop instead of spinning.
+RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float mint, float maxt, float step, float u) {
+    const float length = len3(d);
+    if (length == 0.f) return mk3(0.f);
+    const float inv = 1.f / length;
+    const V3 dn = mk3(d.x * inv, d.y * inv, d.z * inv);
+    float t0, t1;
+    if (!vol_intersect(sc.vol, o, dn, mint * length, maxt * length, t0, t1)) return mk3(0.f);
+    const V3 sig_t = mat_color(sc.vol.sigma_a) + mat_color(sc.vol.sigma_s);
+    V3 tau = mk3(0.f);
+    t0 += u * step;
+    const int cap = fr.dens_cap;
+#pragma unroll 1
+    for (int k = 0; t0 < t1 && k < cap; ++k) {
+        const float D = density_at(sc, xform_point(sc.vol.world_to_volume, o + dn * t0));
+        tau = tau + sig_t * D;
+        t0 += step;
+    }
+    return tau * step;
+}
+RT_DEV V3 exp_neg(V3 tau) { return mk3(expf(-tau.x), expf(-tau.y), expf(-tau.z)); }       // Exp(-tau)
+
+// Scene::Transmittance(ray) (scene.cpp:127-129): sample == NULL => one RandomFloat() for the offset, which a homogeneous medium ignores
+// and a density region marches with at 4.f * stepSize (emission.cpp:47-59, single.cpp:48-56)
+template <bool VOL, bool EXT>
+RT_DEV V3 scene_transmittance(const DevScene &sc, const DevFrame &fr, Lane &ln, V3 o, V3 d, float mint, float maxt) {
     if (!VOL) return mk3(1.f);
-    (void)ln.rng.next_float();
+    const float u = ln.rng.next_float();
+    if (EXT && sc.dens_kind != RT_DENSITY_NONE) return exp_neg(density_tau(sc, fr, o, d, mint, maxt, 4.f * fr.step_size, u));
     return vol_transmittance(sc.vol, o, d, mint, maxt);
 }
 
@@ -491,6 +549,7 @@ struct March { int i, N; float t0, step; V3 Tr, p, Lv; float s0, s1, s2; };     
 // The head of the march: clip against the medium, step count and size, the scatter offset, the LatinHypercube table (3 N draws, then 3 N
 // dependent swaps through memory: run where thousands of marches start side by side -- the shade pass of the queue pipeline, or the megakernel's
 // lanes -- never inside the persistent march kernel, where one lane's table would stall its wave for ~6 N memory round trips).  N = 0: nothing to march.
+template <bool EXT>
 RT_DEV void march_begin(const DevScene &sc, const DevFrame &fr, Lane &ln, const Ray &ray, March &m, float RT_G *samp, size_t st) {
     const RtVolume &vol = sc.vol;
     const bool single = fr.volume_integrator == RT_VOLUME_SINGLE;
@@ -512,6 +571,13 @@ RT_DEV void march_begin(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
         }
     }
     m.i = 0; m.N = N; m.t0 = t0; m.step = step; m.Tr = mk3(1.f); m.p = p; m.Lv = mk3(0.f);
+    if (EXT && sc.dens_kind != RT_DENSITY_NONE) {
+        // Scene::Li's T (scene.cpp:120-126) with sample != NULL: Tau(ray, stepSize, the tau sample, sampler dimension tauSampleOffset) and no draw.
+        // Taken here, where the sampler's values are at hand (the march kernel of the queue pipeline has none), and applied at once: the reference's
+        // T * Lo + Lv becomes (T * Lo) + Lv when the march ends -- the same two operations.
+        const V3 T = exp_neg(density_tau(sc, fr, ray.o, ray.d, ray.mint, ray.maxt, fr.step_size, dim_value(fr, ln, fr.one_d[fr.n1d - 2], 0, 0)));
+        ln.L = T * ln.L;
+    }
 }
 // The steps.  `resume`: ln.tv holds the result of the shadow ray of step m.i.  Returns true with the next step's shadow ray set up (ln.has_ray,
 // ln.pend, ln.stage = ST_VOL_STEP), false when the level is complete (ln.L = T * L + Lv, ln.stage = ST_POP).
@@ -527,23 +593,27 @@ RT_DEV bool march_steps(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
     if (resume) {
         if (COUNT) ++*c_any;
         if (ln.tv.hit_prim < 0)                                                // vis.Unoccluded: Ld = L * vis.Transmittance(scene)
-            Lv = Lv + ln.pend * scene_transmittance<true>(sc, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
+            Lv = Lv + ln.pend * scene_transmittance<true, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
         ++i; t0 += step;
         have_row = PREFETCH;
     }
     while (i < N) {
         const V3 pPrev = p; p = ray.o + ray.d * t0;
-        (void)ln.rng.next_float();                                             // Tau's offset argument
-        const V3 stepT = vol_transmittance(vol, pPrev, p - pPrev, 0.f, 1.f);
+        const float u = ln.rng.next_float();                                   // Tau's offset argument
+        const bool dens = EXT && sc.dens_kind != RT_DENSITY_NONE;
+        const V3 stepT = dens ? exp_neg(density_tau(sc, fr, pPrev, p - pPrev, 0.f, 1.f, .5f * fr.step_size, u))
+                              : vol_transmittance(vol, pPrev, p - pPrev, 0.f, 1.f);
         Tr = Tr * stepT;
         if (lum_y(Tr) < 1e-3) {
             if (ln.rng.next_float() > .5f) break;
             Tr = div_s(Tr, .5f);
         }
-        const bool in = vol_inside(vol, p);
-        Lv = Lv + Tr * (in ? mat_color(vol.le) : mk3(0.f));
+        // Lve / sigma_s: homogeneous.cpp's inside test, or Density(WorldToVolume(p)) times the constant (volume.h:72-80; PhaseHG without a test)
+        const float D = dens ? density_at(sc, xform_point(vol.world_to_volume, p)) : 0.f;
+        const bool in = dens || vol_inside(vol, p);
+        Lv = Lv + Tr * (dens ? D * mat_color(vol.le) : (in ? mat_color(vol.le) : mk3(0.f)));
         if (single) {
-            const V3 ss = in ? mat_color(vol.sigma_s) : mk3(0.f);
+            const V3 ss = dens ? D * mat_color(vol.sigma_s) : (in ? mat_color(vol.sigma_s) : mk3(0.f));
             const int nLights = int(sc.n_lights);
             if (!is_black(ss) && nLights > 0) {
                 const float r0 = have_row ? m.s0 : samp[size_t(3 * i) * st], u1 = have_row ? m.s1 : samp[size_t(3 * i + 1) * st], u2 = have_row ? m.s2 : samp[size_t(3 * i + 2) * st];
@@ -573,8 +643,11 @@ RT_DEV bool march_steps(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
         ++i; t0 += step; have_row = false;
     }
     Lv = Lv * step;
-    const V3 T = vol_transmittance(vol, ray.o, ray.d, ray.mint, ray.maxt);      // sample != NULL: no draw
-    ln.L = T * ln.L + Lv;
+    if (EXT && sc.dens_kind != RT_DENSITY_NONE) ln.L = ln.L + Lv;               // T * Lo was applied by march_begin
+    else {
+        const V3 T = vol_transmittance(vol, ray.o, ray.d, ray.mint, ray.maxt);  // sample != NULL: no draw
+        ln.L = T * ln.L + Lv;
+    }
     ln.stage = ST_POP;
     return false;
 }
@@ -601,7 +674,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                        ln.tv.o.x, ln.tv.o.y, ln.tv.o.z, ln.tv.d.x, ln.tv.d.y, ln.tv.d.z, ln.v.p.x, ln.v.p.y, ln.v.p.z, ln.v.nn.x, ln.v.nn.y, ln.v.nn.z, ln.v.sn.x, ln.v.sn.y, ln.v.sn.z);
 #endif
             if (ln.depth == 0) { ln.alpha = 1.f; if (VOL) vol_ray_ptr(fr, 0, gtid)[7 * size_t(fr.n_threads)] = ln.tv.maxt; }   // r.maxt = ray.maxt
-            else if (VOL) ln.thr = ln.thr * scene_transmittance<VOL>(sc, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);           // path.cpp:89
+            else if (VOL) ln.thr = ln.thr * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);           // path.cpp:89
             if ((ln.depth == 0 || ln.specular) && ln.v.light >= 0)              // path.cpp:91-92
                 ln.L = ln.L + ln.thr * area_L(RT_LIGHT(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);   // isect.Le: dg.nn, the geometric normal
         } else {
@@ -715,11 +788,11 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         if (COUNT) ++*c_any;
         const bool occluded = ln.tv.hit_prim >= 0;
         if (INTEG == RT_INTEGRATOR_WHITTED) {
-            if (!occluded) ln.L = ln.L + ln.pend * scene_transmittance<VOL>(sc, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);   // whitted.cpp:80
+            if (!occluded) ln.L = ln.L + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);   // whitted.cpp:80
             ln.stage = ST_DIRECT_NEXT;
             return;
         }
-        if (!occluded) ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL>(sc, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);       // transport.cpp:155
+        if (!occluded) ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);       // transport.cpp:155
         ln.stage = ST_ED_BSDF;
         return;
     }
@@ -734,7 +807,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             prim_normal_light<EXT>(sc, ln.tv, nh, light);
             if (light == ln.cur_light) {
                 if (dot3(nh, -ln.tv.d) > 0)                                    // isect.Le(-wi) non-black; transport.cpp:188-190
-                    ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL>(sc, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
+                    ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
             }
         }
         ln.stage = ST_ED_DONE;
@@ -850,7 +923,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         March m;
         bool park;
         if (STAGE == ST_VOL_BEGIN) {
-            march_begin(sc, fr, ln, ray, m, samp, st);
+            march_begin<EXT>(sc, fr, ln, ray, m, samp, st);
             if (PARK) { ln.stage = ST_VOL_STEP; park = true; }
             else park = march_steps<COUNT, EXT, DEFER>(sc, fr, ln, ray, m, samp, st, false, c_any);
         } else {                                                                   // resume after the step's shadow ray

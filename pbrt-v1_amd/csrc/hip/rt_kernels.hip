@@ -442,6 +442,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     const bool skip_film = knob("PBRT_HIP_DEBUG_NOFILM") != nullptr;   // perf experiments only
     FilmGather fg; rc = film_gather_plan(s, fr, fg); if (rc) return rc;
     int vol_levels = 0, vol_nmax = 0; size_t vol_samp_words = 0;
+    fr.dens_cap = 0;
     if (s->volume.present) {
         if (!(rd->step_size > 0.f)) return fail(RT_EINVAL, "rt_render: volume integrator stepsize must be positive");
         if (rd->volume_integrator != RT_VOLUME_EMISSION && rd->volume_integrator != RT_VOLUME_SINGLE) return fail(RT_EINVAL, "rt_render: unknown volume integrator");
@@ -450,6 +451,33 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
         const double nsteps = std::ceil(diag / rd->step_size) + 2;
         if (nsteps > 65536) return fail(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
         vol_nmax = int(nsteps);
+        if (s->density_kind != RT_DENSITY_NONE) {
+            // DensityRegion::Tau (volume.cpp:137-153) marches `while (t0 < t1) t0 += step` along the normalised world-space ray: its samples are bounded by
+            // the volume's world diagonal over the smallest step (.5f * stepsize), and the loop only ends if t + .5f * stepsize > t for every t a ray can
+            // reach -- bounded by the union of the scene bound, the camera position and the volume's world bound (ray parameters start at mint >= 0)
+            const double *wb = s->vol_world;
+            const double wx = wb[3] - wb[0], wy = wb[4] - wb[1], wz = wb[5] - wb[2];
+            const double wdiag = std::sqrt(wx * wx + wy * wy + wz * wz);
+            const float half = .5f * rd->step_size;
+            const double taus = std::ceil(wdiag / double(half)) + 2;
+            if (taus > double(1 << 20)) return fail(RT_EINVAL, "rt_render: stepsize too small for the density region (an optical-depth march would take more than 2^20 samples)");
+            double u[6] = {wb[0], wb[1], wb[2], wb[3], wb[4], wb[5]};
+            const float *c2w = s->dev.cam.camera_to_world;                          // the camera position, CameraToWorld(0,0,0)
+            const double cam[3] = {c2w[3], c2w[7], c2w[11]};
+            for (int i = 0; i < 3; ++i) { u[i] = std::min(u[i], cam[i]); u[3 + i] = std::max(u[3 + i], cam[i]); }
+            const float *sb = s->dev.bounds;
+            if (sb[0] <= sb[3] && sb[1] <= sb[4] && sb[2] <= sb[5])
+                for (int i = 0; i < 3; ++i) { u[i] = std::min(u[i], double(sb[i])); u[3 + i] = std::max(u[3 + i], double(sb[3 + i])); }
+            const double ux = u[3] - u[0], uy = u[4] - u[1], uz = u[5] - u[2];
+            const float tmax = std::nextafter(float(std::sqrt(ux * ux + uy * uy + uz * uz)), INFINITY);
+            volatile float tv = tmax;                                               // the device's float addition, not a wider one
+            const float adv = tv + half;
+            if (!std::isfinite(tmax) || !(adv > tmax))
+                return fail(RT_EINVAL, "rt_render: stepsize too small for the density region: at the scene's ray parameters t + .5 * stepsize == t, the optical-depth march would not advance");
+            fr.dens_cap = int(taus);
+            vol_nmax = std::max(vol_nmax, int(std::ceil(wdiag / rd->step_size)) + 2);     // march steps along a world-space ray (a scaled volume)
+            if (vol_nmax > 65536) return fail(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
+        }
         vol_levels = (rd->integrator == RT_INTEGRATOR_PATH) ? 1 : rd->max_depth + 2;
         vol_samp_words = rd->volume_integrator == RT_VOLUME_SINGLE ? size_t(3) * vol_nmax : 0;
     }
@@ -468,6 +496,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     fr.samples = s->samples; s->samples_last = fr.total_work; s->samples_spp = fr.spp;
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
+    s->rendered = true;
     if (fr.pipeline) {
         rc = render_pipeline(s, rd, fr, vol_levels, vol_nmax, vol_samp_words); if (rc) return rc;
         s->last_weighted = false;

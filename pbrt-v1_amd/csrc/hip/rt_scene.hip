@@ -624,6 +624,53 @@ int rt_scene_set_stream(RtScene *s, void *hip_stream) {
     return RT_OK;
 }
 
+// DensityRegion (volume.h:62-90) for the scene's medium: the region's parameters go into DevScene (read by the EXT kernels only), a grid into HBM.
+int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
+    if (!s || !r) return fail(RT_EINVAL, "rt_scene_set_density: null argument");
+    if (s->rendered) return fail(RT_ESTATE, "rt_scene_set_density: the scene has rendered a frame already");
+    if (s->density_kind != RT_DENSITY_NONE) return fail(RT_ESTATE, "rt_scene_set_density: the scene has a density region already");
+    if (!s->volume.present) return fail(RT_EINVAL, "rt_scene_set_density: the scene has no medium (RtSceneDesc.volume.present == 0)");
+    if (r->kind != RT_DENSITY_EXPONENTIAL && r->kind != RT_DENSITY_GRID) return fail(RT_EINVAL, "rt_scene_set_density: unknown density kind");
+    // the volume's world bound, WorldToVolume.GetInverse()(extent) (exponential.cpp:38, volumegrid.cpp:36): its corners through the inverse, in double
+    double a[4][8];
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { a[i][j] = s->volume.world_to_volume[4 * i + j]; a[i][4 + j] = i == j ? 1.0 : 0.0; }
+    for (int c = 0; c < 4; ++c) {                                               // Gauss-Jordan with partial pivoting
+        int piv = c;
+        for (int i = c + 1; i < 4; ++i) if (std::fabs(a[i][c]) > std::fabs(a[piv][c])) piv = i;
+        if (!(std::fabs(a[piv][c]) > 0.0)) return fail(RT_EINVAL, "rt_scene_set_density: singular world_to_volume");
+        for (int j = 0; j < 8; ++j) std::swap(a[c][j], a[piv][j]);
+        const double inv = 1.0 / a[c][c];
+        for (int j = 0; j < 8; ++j) a[c][j] *= inv;
+        for (int i = 0; i < 4; ++i) if (i != c) { const double f = a[i][c]; for (int j = 0; j < 8; ++j) a[i][j] -= f * a[c][j]; }
+    }
+    double wb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int k = 0; k < 8; ++k) {
+        const double q[3] = {(k & 1) ? s->volume.p1[0] : s->volume.p0[0], (k & 2) ? s->volume.p1[1] : s->volume.p0[1], (k & 4) ? s->volume.p1[2] : s->volume.p0[2]};
+        double w[4];
+        for (int i = 0; i < 4; ++i) w[i] = a[i][4] * q[0] + a[i][5] * q[1] + a[i][6] * q[2] + a[i][7];
+        for (int i = 0; i < 3; ++i) { const double v = w[3] != 1.0 ? w[i] / w[3] : w[i]; wb[i] = std::min(wb[i], v); wb[3 + i] = std::max(wb[3 + i], v); }
+    }
+    for (double v : wb) if (!std::isfinite(v)) return fail(RT_EINVAL, "rt_scene_set_density: the volume's world bound is not finite");
+    HIPCHK(hipSetDevice(s->device));
+    const float *grid = nullptr;
+    if (r->kind == RT_DENSITY_GRID) {
+        const long long total = (long long)r->nx * r->ny * r->nz;
+        if (r->nx <= 0 || r->ny <= 0 || r->nz <= 0 || total > 0x7fffffffLL) return fail(RT_EINVAL, "rt_scene_set_density: grid counts must be positive with nx*ny*nz < 2^31");
+        if (!r->density) return fail(RT_EINVAL, "rt_scene_set_density: null density grid");
+        int rc = upload(s, r->density, size_t(total), &grid); if (rc) return rc;
+    }
+    DevScene &d = s->dev;
+    d.dens_kind = r->kind; d.dens_a = r->a; d.dens_b = r->b;
+    for (int i = 0; i < 3; ++i) d.dens_up[i] = r->updir[i];
+    d.dens_n[0] = r->nx; d.dens_n[1] = r->ny; d.dens_n[2] = r->nz; d.dens_grid = grid;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
+    std::memcpy(s->vol_world, wb, sizeof wb);
+    s->density_kind = r->kind;
+    s->has_ext = true;                                                          // the density code exists only in the EXT kernels
+    return RT_OK;
+}
+
 int rt_scene_accel_info(const RtScene *s, RtAccelInfo *info) {
     if (!s || !info) return fail(RT_EINVAL, "null argument");
     fill_info(s->tree, s->gridacc, s->accel_kind, s->n_tris, info);

@@ -344,6 +344,7 @@ void SceneDescription::finalize_pointers() {
     scene.tri_shading = tri_shading.empty() ? nullptr : tri_shading.data();
     scene.n_shading = uint32_t(shading.size()); scene.shading = shading.empty() ? nullptr : shading.data();
     scene.n_xforms = uint32_t(xforms.size() / 32); scene.xforms = xforms.empty() ? nullptr : xforms.data();
+    density.density = density.kind == RT_DENSITY_GRID ? density_values.data() : nullptr;
 }
 
 PbrtApi::PbrtApi() : state(STATE_OPTIONS), nVolumes(0), inObject(false) {
@@ -352,7 +353,7 @@ PbrtApi::PbrtApi() : state(STATE_OPTIONS), nVolumes(0), inObject(false) {
     // one of the supported samplers fails loudly in MakeSampler ("Unable to load plugin") and its frame is invalid.
     filterOpt.name = "mitchell"; filmOpt.name = "image"; samplerOpt.name = "bestcandidate"; accelOpt.name = "kdtree";
     surfOpt.name = "directlighting"; volOpt.name = "emission"; cameraOpt.name = "perspective";
-    std::memset(&volume, 0, sizeof volume);
+    std::memset(&volume, 0, sizeof volume); std::memset(&density, 0, sizeof density);
 }
 PbrtApi::~PbrtApi() { for (SceneDescription *f : frames) delete f; }
 void PbrtApi::Diagnostic(int severity, const std::string &msg) { if (severity) Error("%s", msg.c_str()); else Warning("%s", msg.c_str()); }
@@ -717,16 +718,49 @@ void PbrtApi::quadricShape(const std::string &name, const ParamSet &ps) {
     meshes.push_back(std::move(mesh));
 }
 
-void PbrtApi::Volume(const std::string &n, const ParamList &p) {                    // api.cpp:403-409, homogeneous.cpp:76-88
+// pbrtVolume (api.cpp:403-409): MakeVolumeRegion (dynload.cpp:365-375) runs the factory, then ReportUnused, and a region the factory
+// rejects (NULL) is not kept.  Factories: homogeneous.cpp:76-88, exponential.cpp:54-69, volumegrid.cpp:85-110 (DensityRegion, volume.h:62-90).
+void PbrtApi::Volume(const std::string &n, const ParamList &p) {
     if (!verifyWorld("Volume")) return;
     ParamSet ps(p);
-    if (n != "homogeneous") { Error("Unable to load plugin \"%s\" (volume region): only \"homogeneous\" is on the accelerated path", n.c_str()); return; }
-    if (nVolumes++ > 0) { Error("Only one volume region is supported on the accelerated path (AggregateVolume is out of scope)"); return; }
+    const bool exponential = n == "exponential", grid = n == "volumegrid";
+    if (n != "homogeneous" && !exponential && !grid) { Error("Unable to load plugin \"%s\" (volume region): only \"homogeneous\", \"exponential\" and \"volumegrid\" are on the accelerated path", n.c_str()); return; }
+    if (!exponential && !grid) {
+        if (nVolumes++ > 0) { Error("Only one volume region is supported on the accelerated path (AggregateVolume is out of scope)"); return; }
+    }
     Float3 sa = ps.FindOneSpectrum("sigma_a", Float3{0, 0, 0}), ss = ps.FindOneSpectrum("sigma_s", Float3{0, 0, 0});
     float g = ps.FindOneFloat("g", 0.);
     Float3 Le = ps.FindOneSpectrum("Le", Float3{0, 0, 0});
     Float3 p0 = ps.FindOnePoint("p0", Float3{0, 0, 0}), p1 = ps.FindOnePoint("p1", Float3{1, 1, 1});
+    RtDensityRegion dr; std::memset(&dr, 0, sizeof dr);
+    std::vector<float> values;
+    if (exponential) {                                                              // exponential.cpp:63-66, the constructor's Normalize(up) :33
+        dr.kind = RT_DENSITY_EXPONENTIAL;
+        dr.a = ps.FindOneFloat("a", 1.); dr.b = ps.FindOneFloat("b", 1.);
+        Float3 up = ps.FindOneVector("updir", Float3{0, 1, 0});
+        const float inv = 1.f / std::sqrt(up.x * up.x + up.y * up.y + up.z * up.z);   // Vector::operator/ (geometry.h:65-69) of Normalize
+        dr.updir[0] = up.x * inv; dr.updir[1] = up.y * inv; dr.updir[2] = up.z * inv;
+    } else if (grid) {                                                              // volumegrid.cpp:93-108
+        dr.kind = RT_DENSITY_GRID;
+        int nitems = 0;
+        const float *data = ps.FindFloat("density", &nitems);
+        if (!data) { Error("No \"density\" values provided for volume grid?"); ps.ReportUnused(); return; }
+        const int nx = ps.FindOneInt("nx", 1), ny = ps.FindOneInt("ny", 1), nz = ps.FindOneInt("nz", 1);
+        const long long total = (long long)nx * ny * nz;
+        if (nx <= 0 || ny <= 0 || nz <= 0 || total > 0x7fffffffLL) {
+            Error("VolumeGrid: nx*ny*nz = %d*%d*%d is not a positive count below 2^31", nx, ny, nz); ps.ReportUnused(); return;
+        }
+        if ((long long)nitems != total) {
+            Error("VolumeGrid has %d density values but nx*ny*nz = %d", nitems, int(total)); ps.ReportUnused(); return;
+        }
+        dr.nx = nx; dr.ny = ny; dr.nz = nz;
+        values.assign(data, data + nitems);
+    }
     ps.ReportUnused();
+    if (exponential || grid) {
+        if (nVolumes++ > 0) { Error("Only one volume region is supported on the accelerated path (AggregateVolume is out of scope)"); return; }
+    }
+    density = dr; densityValues.swap(values);
     volume.present = 1;
     Xform w2v = ctm.inverse();
     std::memcpy(volume.world_to_volume, w2v.m.m, 16 * sizeof(float));
@@ -744,6 +778,7 @@ void PbrtApi::ObjectInstance(const std::string &n) { if (verifyWorld("ObjectInst
 void PbrtApi::resetWorld() {
     meshes.clear(); materials.clear(); lights.clear(); light_tris.clear(); quadrics.clear();
     std::memset(&volume, 0, sizeof volume); nVolumes = 0;
+    std::memset(&density, 0, sizeof density); densityValues.clear();
 }
 
 void PbrtApi::WorldEnd() {                                                          // api.cpp:458-529
@@ -782,6 +817,7 @@ void PbrtApi::WorldEnd() {                                                      
     if (materials.size() > 65535) { Error("more than 65535 material instances"); all = false; }
     sd->materials = materials; sd->lights = lights; sd->light_tris = light_tris; sd->quadrics = quadrics;
     sd->scene.volume = volume; sd->scene.accel = acc.params;
+    sd->density = density; sd->density_values.swap(densityValues);
     RtRenderDesc &r = sd->render;
     r.integrator = si.kind; r.max_depth = si.maxDepth; r.strategy = si.strategy;
     r.volume_integrator = vi.kind; r.step_size = vi.stepSize;
@@ -847,6 +883,12 @@ void pbrt_host_scene_counts(const RtSceneDesc *s, unsigned *out4) { out4[0] = s-
 const float *pbrt_host_camera(const RtSceneDesc *s) { return s->camera.raster_to_camera; }
 const float *pbrt_host_tri_verts(const RtSceneDesc *s) { return s->tri_verts; }
 const RtAccelParams *pbrt_host_accel_params(const RtSceneDesc *s) { return &s->accel; }
+const RtVolume *pbrt_host_volume(const RtSceneDesc *s) { return &s->volume; }
+// the frame's DensityRegion for rt_scene_set_density, or NULL when its medium (if any) is homogeneous
+const RtDensityRegion *pbrt_host_density_desc(PbrtHostScene *h, int i) {
+    const SceneDescription *sd = h->api.frames[i];
+    return sd->density.kind != RT_DENSITY_NONE && sd->scene.volume.present ? &sd->density : nullptr;
+}
 // canonical byte image of a frame's descriptors (include/pbrt_hip_desc.h); returns the size, writes when the buffer is large enough
 long long pbrt_host_serialize(PbrtHostScene *h, int i, unsigned char *out, long long cap) {
     const size_t n = rt_desc_serialize(&h->api.frames[i]->scene, &h->api.frames[i]->render, nullptr);

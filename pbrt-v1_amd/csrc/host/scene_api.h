@@ -8,7 +8,7 @@
 //     (SURVEY.md section 8a): filters box/gaussian/mitchell/sinc/triangle, film "image", camera
 //     "perspective", samplers stratified/lowdiscrepancy/random, surface integrators
 //     whitted/directlighting/path, volume integrators emission/single, accelerators kdtree/grid, shape
-//     "trianglemesh", materials matte/glass/mirror, lights point + area, volume "homogeneous";
+//     "trianglemesh", materials matte/glass/mirror, lights point + area, volumes "homogeneous", "exponential", "volumegrid";
 //     each takes the same parameters with the same defaults as the reference factory it replaces.
 //   * RenderOptions::MakeScene (core/api.cpp:484-529): instead of building C++ objects it flattens.
 // Plugins the reference has but this path does not accelerate produce the reference's own
@@ -47,6 +47,7 @@ struct SceneDescription {
     std::vector<RtMaterial> materials; std::vector<RtLight> lights; std::vector<float> light_tris; std::vector<RtQuadric> quadrics;
     std::vector<int32_t> tri_shading; std::vector<RtTriShading> shading; std::vector<float> xforms;   // per-vertex uv / N / S (trianglemesh)
     RtSceneDesc scene; RtRenderDesc render;
+    RtDensityRegion density; std::vector<float> density_values;   // the medium's DensityRegion (kind RT_DENSITY_NONE: none), rt_scene_set_density
     Film film;
     bool valid = false;
     void finalize_pointers();
@@ -127,6 +128,7 @@ class PbrtApi : public DirectiveSink {
     std::vector<Mesh> meshes;
     std::vector<RtMaterial> materials; std::vector<RtLight> lights; std::vector<float> light_tris;
     RtVolume volume; int nVolumes;
+    RtDensityRegion density; std::vector<float> densityValues;
     bool inObject;
     bool verifyOptions(const char *fn); bool verifyWorld(const char *fn);
     int makeMaterial(const ParamSet &shapeParams);
