@@ -35,7 +35,8 @@ extern "C" {
 typedef struct RtScene RtScene; /* opaque */
 
 /* ---- materials: materials/matte.cpp:46-64, glass.cpp:46-63, mirror.cpp:42-55, plastic.cpp:47-69, uber.cpp:52-89 ---- */
-enum { RT_MAT_MATTE = 0, RT_MAT_MIRROR = 1, RT_MAT_GLASS = 2, RT_MAT_PLASTIC = 3, RT_MAT_UBER = 4 };
+/*      shinymetal.cpp:43-73, translucent.cpp:45-94 (both need the EXT kernels, as plastic and uber do)                       */
+enum { RT_MAT_MATTE = 0, RT_MAT_MIRROR = 1, RT_MAT_GLASS = 2, RT_MAT_PLASTIC = 3, RT_MAT_UBER = 4, RT_MAT_SHINYMETAL = 5, RT_MAT_TRANSLUCENT = 6 };
 typedef struct RtMaterial {
     int32_t type;
     float kd[3];   /* matte/plastic Kd  | mirror/glass Kr  (already .Clamp()'ed >= 0) */
@@ -46,6 +47,13 @@ typedef struct RtMaterial {
     float roughness; /* plastic / uber "roughness"                                */
     float kr[3];   /* uber: op*Kr (SpecularReflection, FresnelDielectric(1.5, 1)).  For uber kd = op*Kd, ks = op*Ks,
                     * kt = 1 - op (SpecularTransmission(1 - op, 1, 1), present iff op != 1), ior = 1; lobe order T, D, G, R */
+    /* shinymetal (types 5, 6 reuse the fields above; the layout of types 0-4 is unchanged): ks = Ks, kr = Kr (.Clamp()'ed), roughness.
+     *   Lobes {Microfacet(1, FresnelConductor(FresnelApproxEta(Ks), 0), Blinn(1/roughness)), SpecularReflection(1,
+     *   FresnelConductor(FresnelApproxEta(Kr), 0))}, both always present (shinymetal.cpp:52-61, reflection.cpp:40-56, :74-76).
+     * translucent: kd = Kd, ks = Ks, kr = "reflect", kt = "transmit" (.Clamp()'ed), roughness.  Lobes, each present iff its colour
+     *   is not black: Lambertian(reflect*Kd), BRDFToBTDF(Lambertian(transmit*Kd)), Microfacet(reflect*Ks, FresnelDielectric(1.5, 1),
+     *   Blinn(1/roughness)), BRDFToBTDF(Microfacet(transmit*Ks, ...)) (translucent.cpp:53-80, reflection.cpp:63-73, :231-234).
+     * include/pbrt_hip_material.h derives the etas, the products and the lobe flags exactly as rt_scene_create does. */
 } RtMaterial;
 
 /* ---- lights: lights/point.cpp:49-69, lights/area.cpp:28-105, lights/spot.cpp:54-79, lights/distant.cpp:51-62 ---- */

@@ -50,7 +50,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | No
     headers = [d for d in hip_dep if d.endswith((".h", ".inc"))]
     host_src = [os.path.join(CSRC, "host", "scene_api.cpp")]
     host_dep = [os.path.join(CSRC, "host", f) for f in os.listdir(os.path.join(CSRC, "host"))] + \
-               [os.path.join(_HERE, "..", "include", f) for f in ("pbrt_hip.h", "pbrt_hip_desc.h", "pbrt_hip_plugin.h")]
+               [os.path.join(_HERE, "..", "include", f) for f in ("pbrt_hip.h", "pbrt_hip_desc.h", "pbrt_hip_plugin.h", "pbrt_hip_material.h")]
 
     def stale(out, deps):
         return force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
@@ -149,6 +149,19 @@ class RtVolume(C.Structure):
 class RtDensityRegion(C.Structure):
     _fields_ = [("kind", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("updir", C.c_float * 3),
                 ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("density", C.POINTER(C.c_float))]
+
+
+RT_MATERIAL_NAMES = ("matte", "mirror", "glass", "plastic", "uber", "shinymetal", "translucent")
+
+
+class RtMaterial(C.Structure):                     # include/pbrt_hip.h (64 bytes)
+    _fields_ = [("type", C.c_int32), ("kd", C.c_float * 3), ("kt", C.c_float * 3), ("sigma", C.c_float), ("ior", C.c_float),
+                ("ks", C.c_float * 3), ("roughness", C.c_float), ("kr", C.c_float * 3)]
+
+
+class RtMaterialLobes(C.Structure):                # include/pbrt_hip_material.h
+    _fields_ = [(n, C.c_float * 3) for n in ("eta_ks", "eta_kr", "r_kd", "t_kd", "r_ks", "t_ks")] + \
+               [(n, C.c_int32) for n in ("has_dr", "has_dt", "has_gr", "has_gt")]
 
 
 RT_DENSITY_NAMES = {1: "exponential", 2: "volumegrid"}
@@ -281,6 +294,9 @@ def host_lib():
         L.pbrt_host_volume.argtypes = [C.c_void_p]
         L.pbrt_host_density_desc.restype = C.POINTER(RtDensityRegion)
         L.pbrt_host_density_desc.argtypes = [C.c_void_p, C.c_int]
+        L.pbrt_host_materials.restype = C.POINTER(RtMaterial)
+        L.pbrt_host_materials.argtypes = [C.c_void_p]
+        L.pbrt_host_material_lobes.argtypes = [C.POINTER(RtMaterial), C.POINTER(RtMaterialLobes)]
         _host = L
     return _host
 
@@ -543,6 +559,44 @@ class ParsedScene:
                 dens.update(nx=int(d.nx), ny=int(d.ny), nz=int(d.nz),
                             values=np.ctypeslib.as_array(d.density, shape=(d.nz, d.ny, d.nx)).copy())
             out["density"] = dens
+        return out
+
+    def materials(self) -> list:
+        """The parsed material table (RtMaterial, include/pbrt_hip.h) as dictionaries: `type` (the material's name) and its parameters as
+        float32 arrays / floats under the reference's parameter names, after .Clamp() and with textures and shape parameters resolved.
+        shinymetal and translucent also carry what rt_scene_create derives from them (include/pbrt_hip_material.h): `eta_Ks`, `eta_Kr`
+        (FresnelApproxEta), or the products `reflect*Kd`, `transmit*Kd`, `reflect*Ks`, `transmit*Ks` and `lobes`, the lobes present in the
+        order the BSDF holds them."""
+        H = host_lib()
+        tab = H.pbrt_host_materials(self.scene_desc)
+        f3 = lambda a: np.array(list(a), np.float32)
+        out = []
+        for i in range(self.n_materials):
+            m = tab[i]
+            name = RT_MATERIAL_NAMES[m.type]
+            d = {"type": name}
+            if name == "matte":
+                d.update(Kd=f3(m.kd), sigma=float(m.sigma))
+            elif name == "mirror":
+                d.update(Kr=f3(m.kd))
+            elif name == "glass":
+                d.update(Kr=f3(m.kd), Kt=f3(m.kt), index=float(m.ior))
+            elif name == "plastic":
+                d.update(Kd=f3(m.kd), Ks=f3(m.ks), roughness=float(m.roughness))
+            elif name == "uber":          # the colours as the descriptor holds them: opacity already multiplied in (include/pbrt_hip.h)
+                d.update({"opacity*Kd": f3(m.kd), "opacity*Ks": f3(m.ks), "opacity*Kr": f3(m.kr), "1-opacity": f3(m.kt), "roughness": float(m.roughness)})
+            else:
+                lb = RtMaterialLobes()
+                H.pbrt_host_material_lobes(C.byref(m), C.byref(lb))
+                if name == "shinymetal":
+                    d.update(Ks=f3(m.ks), Kr=f3(m.kr), roughness=float(m.roughness), eta_Ks=f3(lb.eta_ks), eta_Kr=f3(lb.eta_kr),
+                             lobes=["glossy_reflection", "specular_reflection"])
+                else:
+                    d.update({"Kd": f3(m.kd), "Ks": f3(m.ks), "reflect": f3(m.kr), "transmit": f3(m.kt), "roughness": float(m.roughness),
+                              "reflect*Kd": f3(lb.r_kd), "transmit*Kd": f3(lb.t_kd), "reflect*Ks": f3(lb.r_ks), "transmit*Ks": f3(lb.t_ks)})
+                    d["lobes"] = [n for n, on in (("diffuse_reflection", lb.has_dr), ("diffuse_transmission", lb.has_dt),
+                                                  ("glossy_reflection", lb.has_gr), ("glossy_transmission", lb.has_gt)) if on]
+            out.append(d)
         return out
 
     def density_desc(self):

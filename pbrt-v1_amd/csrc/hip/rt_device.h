@@ -39,6 +39,9 @@ struct DevMaterial {
     float exponent;    // plastic / uber: Blinn exponent = 1/roughness, capped at 1000 (reflection.h:313)
     float kr[3];       // uber: SpecularReflection reflectance (Fresnel 1.5 / 1)
     int has_g, has_kr; // uber: glossy / specular-reflection lobes present (non-black, uber.cpp:71-86)
+    // shinymetal (shinymetal.cpp:52-61): ks = FresnelApproxEta(Ks), kr = FresnelApproxEta(Kr) (the two FresnelConductor etas, k = 0), exponent
+    // translucent (translucent.cpp:53-80): r = reflect*Kd, t = transmit*Kd, ks = reflect*Ks, kr = transmit*Ks, exponent; the lobes
+    //   present are has_r (diffuse R), has_t (diffuse T), has_g (glossy R), has_kr (glossy T).  Same 84 bytes: no read got wider.
 };
 
 struct DevLight {

@@ -27,8 +27,10 @@ enum { PV_S = 4u, PV_M = 8u, PV_B = 16u, PV_ED = 32u, PV_ENDED = 64u, PV_SPECULA
 // ray kinds of a slot: queue entry = slot | kind << 30; ray_d / hit planes are indexed by kind
 enum { PV_RAY_S = 0, PV_RAY_M = 1, PV_RAY_B = 2 };
 
+// the timed EXT kernel is held to 3 waves per SIMD (168 VGPRs): with the shinymetal / translucent lobes it allocates 171 on its own, 166 without
+// scratch when asked; a minimum of 1 is what a kernel without the second argument gets
 template <bool COUNT, bool EXT>
-__global__ __launch_bounds__(RT_BLOCK) void pipe_vertex_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
+__global__ __launch_bounds__(RT_BLOCK, (EXT && !COUNT) ? 3 : 1) void pipe_vertex_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
                                                                 const PipePool *__restrict__ plp, PipeLaunch pk) {
     constexpr int INTEG = RT_INTEGRATOR_PATH;
     const DevScene &sc = *scp;

@@ -2,6 +2,7 @@
 // uploaded -- primitive records and leaf entries, sibling-pair blocks, shading constants, lights -- plus the launch geometry of the persistent kernels;
 // rt_scene_destroy, and the accelerator-only entry points (rt_accel_* / rt_kdtree_*) of the C ABI.
 #include "rt_host.h"
+#include "../../../include/pbrt_hip_material.h"
 
 // tri_frame() of rt_shade.h on the host: same operations in the same order (trianglemesh.cpp:248-274, shape.cpp:43-50,
 // reflection.cpp:475-476)
@@ -463,7 +464,17 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         for (int c = 0; c < 3; ++c) o.kr[c] = m.kr[c];
         o.has_g = (m.ks[0] != 0.f || m.ks[1] != 0.f || m.ks[2] != 0.f); o.has_kr = (m.kr[0] != 0.f || m.kr[1] != 0.f || m.kr[2] != 0.f);
         if (m.type == RT_MAT_PLASTIC || m.type == RT_MAT_UBER) { s->has_ext = true; float e = 1.f / m.roughness; if (e > 1000.f || std::isnan(e)) e = 1000.f; o.exponent = e; }
-        if (m.type < RT_MAT_MATTE || m.type > RT_MAT_UBER) return fail(RT_EINVAL, "rt_scene_create: unknown material type");
+        if (m.type == RT_MAT_SHINYMETAL || m.type == RT_MAT_TRANSLUCENT) {         // DevMaterial's fields per type: rt_device.h
+            RtMaterialLobes lb; rt_material_lobes(&m, &lb);
+            const bool shiny = m.type == RT_MAT_SHINYMETAL;
+            for (int c = 0; c < 3; ++c) {
+                o.r[c] = lb.r_kd[c]; o.t[c] = lb.t_kd[c];
+                o.ks[c] = shiny ? lb.eta_ks[c] : lb.r_ks[c]; o.kr[c] = shiny ? lb.eta_kr[c] : lb.t_ks[c];
+            }
+            o.has_r = lb.has_dr; o.has_t = lb.has_dt; o.has_g = lb.has_gr; o.has_kr = lb.has_gt;
+            s->has_ext = true; float e = 1.f / m.roughness; if (e > 1000.f || std::isnan(e)) e = 1000.f; o.exponent = e;
+        }
+        if (m.type < RT_MAT_MATTE || m.type > RT_MAT_TRANSLUCENT) return fail(RT_EINVAL, "rt_scene_create: unknown material type");
         if (m.type == RT_MAT_MATTE && m.sigma != 0.f) {
             float sigma = (3.14159265358979323846f / 180.f) * m.sigma;
             float sigma2 = sigma * sigma;

@@ -1,5 +1,5 @@
 // rt_shade.h -- device-side surface interaction: differential geometry of a triangle hit,
-// the BSDF set the three materials can produce, and the two light types.
+// the BSDF set the materials can produce, and the light types.
 // Each function names the reference code whose arithmetic (and association order) it follows.
 #pragma once
 #include "rt_traverse.h"
@@ -253,19 +253,40 @@ RT_DEV void concentric_disk(float u1, float u2, float &dx, float &dy) {
 // Microfacet::f reflection.cpp:163-175 with Blinn::D (reflection.h:315-320), Microfacet::G (:293-301) and
 // FresnelDielectric(1.5, 1) (plastic.cpp:59-60)
 RT_DEV float min_std(float a, float b) { return (b < a) ? b : a; }            // std::min
-RT_DEV V3 microfacet_f(MatRef m, V3 wo, V3 wi) {
+// COND: the Fresnel term is FresnelConductor(eta, 0) per channel (shinymetal.cpp:57, :59) instead of the scalar dielectric one
+// FrCond reflection.cpp:40-51 with k = 0 (eta*eta + k*k == eta*eta exactly) + FresnelConductor::Evaluate :74-76 (the caller passes fabsf(cosi))
+RT_DEV V3 fr_cond(float cosi, V3 eta) {
+    const V3 tmp_f = eta * eta;
+    const V3 tmp = (tmp_f * cosi) * cosi;
+    const V3 tec = (2.f * eta) * cosi;
+    const V3 Rparl2 = div_c((tmp - tec) + mk3(1.f), (tmp + tec) + mk3(1.f));
+    const V3 Rperp2 = div_c((tmp_f - tec) + mk3(cosi * cosi), (tmp_f + tec) + mk3(cosi * cosi));
+    return div_s(Rparl2 + Rperp2, 2.f);
+}
+template <bool COND>
+RT_DEV V3 microfacet_lobe(V3 R, V3 eta, float exponent, V3 wo, V3 wi) {
     const float cosThetaO = fabsf(wo.z), cosThetaI = fabsf(wi.z);
     if (cosThetaI == 0.f || cosThetaO == 0.f) return mk3(0.f);
     V3 wh = wi + wo;
     if (wh.x == 0.f && wh.y == 0.f && wh.z == 0.f) return mk3(0.f);
     wh = normalize3(wh);
     const float cosThetaH = dot3(wi, wh);
-    const float F = fresnel_dielectric(cosThetaH, 1.5f, 1.f);
-    const float D = (m.exponent + 2) * RT_INV_TWOPI * powf(fabsf(wh.z), m.exponent);
+    const V3 F = COND ? fr_cond(fabsf(cosThetaH), eta) : mk3(fresnel_dielectric(cosThetaH, 1.5f, 1.f));
+    const float D = (exponent + 2) * RT_INV_TWOPI * powf(fabsf(wh.z), exponent);
     const float NdotWh = fabsf(wh.z), NdotWo = fabsf(wo.z), NdotWi = fabsf(wi.z), WOdotWh = absdot3(wo, wh);
     const float G = min_std(1.f, min_std((2.f * NdotWh * NdotWo / WOdotWh), (2.f * NdotWh * NdotWi / WOdotWh)));
-    return div_s(((mat_color(m.ks) * D) * G) * mk3(F), 4.f * cosThetaI * cosThetaO);
+    return div_s(((R * D) * G) * F, 4.f * cosThetaI * cosThetaO);
 }
+// the glossy reflection lobe: plastic / uber / translucent Microfacet(ks, dielectric); shinymetal Microfacet(1, conductor(eta = m.ks))
+RT_DEV V3 microfacet_f(MatRef m, V3 wo, V3 wi) {
+    if (m.type == RT_MAT_SHINYMETAL) return microfacet_lobe<true>(mk3(1.f), mat_color(m.ks), m.exponent, wo, wi);
+    return microfacet_lobe<false>(mat_color(m.ks), mk3(0.f), m.exponent, wo, wi);
+}
+// BRDFToBTDF (reflection.h:140-175): f(wo, otherHemisphere(wi)) flips z only (reflection.cpp:63-66), Pdf(wo, -wi) negates the whole
+// vector (:231-234).  Translucent's two transmission lobes: Lambertian(m.t), whose f ignores its arguments, and Microfacet(m.kr, dielectric).
+RT_DEV V3 other_hemisphere(V3 w) { return mk3(w.x, w.y, -w.z); }
+RT_DEV V3 diffuse_t_f(MatRef m) { return mat_color(m.t) * RT_INV_PI; }
+RT_DEV V3 microfacet_t_f(MatRef m, V3 wo, V3 wi) { return microfacet_lobe<false>(mat_color(m.kr), mk3(0.f), m.exponent, wo, other_hemisphere(wi)); }
 // Blinn::Pdf reflection.cpp:263-272
 RT_DEV float blinn_pdf(float exponent, V3 wo, V3 wi) {
     const V3 H = normalize3(wo + wi);
@@ -277,12 +298,17 @@ RT_DEV float blinn_pdf(float exponent, V3 wo, V3 wi) {
 // BxDF::Pdf of the two non-specular lobes: reflection.cpp:227-230 (cosine) and Microfacet::Pdf :241-245
 RT_DEV float diffuse_pdf(V3 wo, V3 wi) { return (wo.z * wi.z > 0.f) ? fabsf(wi.z) * RT_INV_PI : 0.f; }
 RT_DEV float glossy_pdf(MatRef m, V3 wo, V3 wi) { return (wo.z * wi.z > 0.f) ? blinn_pdf(m.exponent, wo, wi) : 0.f; }
+RT_DEV float diffuse_t_pdf(V3 wo, V3 wi) { return diffuse_pdf(wo, -wi); }                      // BRDFToBTDF::Pdf reflection.cpp:231-234
+RT_DEV float glossy_t_pdf(MatRef m, V3 wo, V3 wi) { return glossy_pdf(m, wo, -wi); }
 
 // lobes in the order the material adds them: matte {diffuse}; plastic {diffuse, glossy} (plastic.cpp:66-67);
 // mirror {specular R}; glass {specular R, specular T} (glass.cpp:56-61, only the non-black ones)
 // non-specular lobes of a material: matte {D}; plastic {D, G}; uber {D if op*Kd != 0, G if op*Ks != 0} (uber.cpp:67-79)
-template <bool EXT> RT_DEV bool mat_has_diffuse(MatRef m) { return m.type == RT_MAT_MATTE || (EXT && (m.type == RT_MAT_PLASTIC || (m.type == RT_MAT_UBER && m.has_r))); }
-template <bool EXT> RT_DEV bool mat_has_glossy(MatRef m) { return EXT && (m.type == RT_MAT_PLASTIC || (m.type == RT_MAT_UBER && m.has_g)); }
+// shinymetal {G, specular R} (shinymetal.cpp:60-61); translucent {D, D transmitted, G, G transmitted}, each if non-black (translucent.cpp:59-78)
+template <bool EXT> RT_DEV bool mat_has_diffuse(MatRef m) { return m.type == RT_MAT_MATTE || (EXT && (m.type == RT_MAT_PLASTIC || ((m.type == RT_MAT_UBER || m.type == RT_MAT_TRANSLUCENT) && m.has_r))); }
+template <bool EXT> RT_DEV bool mat_has_glossy(MatRef m) { return EXT && (m.type == RT_MAT_PLASTIC || m.type == RT_MAT_SHINYMETAL || ((m.type == RT_MAT_UBER || m.type == RT_MAT_TRANSLUCENT) && m.has_g)); }
+template <bool EXT> RT_DEV bool mat_has_diffuse_t(MatRef m) { return EXT && m.type == RT_MAT_TRANSLUCENT && m.has_t; }
+template <bool EXT> RT_DEV bool mat_has_glossy_t(MatRef m) { return EXT && m.type == RT_MAT_TRANSLUCENT && m.has_kr; }
 RT_DEV bool flags_match(int type, int flags) { return (type & flags) == type; }
 
 template <bool EXT>
@@ -293,6 +319,14 @@ RT_DEV int bsdf_num_components(MatRef m, int flags) {
         if (m.has_r && flags_match(BX_REFLECTION | BX_DIFFUSE, flags)) ++n;
         if (m.has_g && flags_match(BX_REFLECTION | BX_GLOSSY, flags)) ++n;
         if (m.has_kr && flags_match(BX_REFLECTION | BX_SPECULAR, flags)) ++n;
+        return n;
+    }
+    if (EXT && m.type == RT_MAT_SHINYMETAL) return int(flags_match(BX_REFLECTION | BX_GLOSSY, flags)) + int(flags_match(BX_REFLECTION | BX_SPECULAR, flags));
+    if (EXT && m.type == RT_MAT_TRANSLUCENT) {
+        if (m.has_r && flags_match(BX_REFLECTION | BX_DIFFUSE, flags)) ++n;
+        if (m.has_t && flags_match(BX_TRANSMISSION | BX_DIFFUSE, flags)) ++n;
+        if (m.has_g && flags_match(BX_REFLECTION | BX_GLOSSY, flags)) ++n;
+        if (m.has_kr && flags_match(BX_TRANSMISSION | BX_GLOSSY, flags)) ++n;
         return n;
     }
     if (m.type == RT_MAT_MATTE || (EXT && m.type == RT_MAT_PLASTIC)) {
@@ -306,22 +340,26 @@ RT_DEV int bsdf_num_components(MatRef m, int flags) {
 }
 template <bool EXT> RT_DEV int bsdf_total_components(MatRef m) { return bsdf_num_components<EXT>(m, BX_ALL); }
 
-// sum of f over the non-specular reflection lobes matching `flags`, in lobe order (BSDF::f's loop, reflection.cpp:489-492)
+// sum of f over the non-specular lobes matching `flags`, in lobe order (BSDF::f's loop, reflection.cpp:489-492)
 template <bool EXT>
 RT_DEV V3 bsdf_f_lobes(MatRef m, V3 wo, V3 wi, int flags) {
     V3 f = mk3(0.f);
     if (mat_has_diffuse<EXT>(m) && flags_match(BX_REFLECTION | BX_DIFFUSE, flags)) f = f + diffuse_f(m, wo, wi);
+    if (mat_has_diffuse_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_DIFFUSE, flags)) f = f + diffuse_t_f(m);
     if (mat_has_glossy<EXT>(m) && flags_match(BX_REFLECTION | BX_GLOSSY, flags)) f = f + microfacet_f(m, wo, wi);
+    if (mat_has_glossy_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_GLOSSY, flags)) f = f + microfacet_t_f(m, wo, wi);
     return f;
 }
+template <bool EXT> RT_DEV bool mat_has_btdf(MatRef m) { return mat_has_diffuse_t<EXT>(m) || mat_has_glossy_t<EXT>(m); }
 
 // BSDF::f reflection.cpp:480-494 (flags = BSDF_ALL): only the non-specular lobes have a non-zero f
 template <bool EXT>
 RT_DEV V3 bsdf_f(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
-    if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m)) return mk3(0.f);
+    if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m) && !mat_has_btdf<EXT>(m)) return mk3(0.f);
     V3 wi = to_local(v, wiW), wo = to_local(v, woW);
     if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) return bsdf_f_lobes<EXT>(m, wo, wi, BX_ALL & ~BX_TRANSMISSION);   // BRDFs only
-    return mk3(0.f);                                                                                         // BTDFs only: none
+    if (mat_has_btdf<EXT>(m)) return bsdf_f_lobes<EXT>(m, wo, wi, BX_ALL & ~BX_REFLECTION);                  // BTDFs only: translucent has them
+    return mk3(0.f);
 }
 
 // BSDF::Pdf reflection.cpp:458-470 (flags = BSDF_ALL)
@@ -329,11 +367,13 @@ template <bool EXT>
 RT_DEV float bsdf_pdf(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
     int nc = bsdf_total_components<EXT>(m);
     if (nc == 0) return 0.f;
-    if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m)) return 0.f / float(nc);
+    if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m) && !mat_has_btdf<EXT>(m)) return 0.f / float(nc);
     V3 wo = to_local(v, woW), wi = to_local(v, wiW);
     float pdf = 0.f;
     if (mat_has_diffuse<EXT>(m)) pdf += diffuse_pdf(wo, wi);
+    if (mat_has_diffuse_t<EXT>(m)) pdf += diffuse_t_pdf(wo, wi);
     if (mat_has_glossy<EXT>(m)) pdf += glossy_pdf(m, wo, wi);
+    if (mat_has_glossy_t<EXT>(m)) pdf += glossy_t_pdf(m, wo, wi);
     return pdf / nc;
 }
 
@@ -349,9 +389,22 @@ RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, fl
     V3 wi, f;
     const bool diffuse_has = mat_has_diffuse<EXT>(m) && flags_match(BX_REFLECTION | BX_DIFFUSE, flags);
     const bool glossy_has = mat_has_glossy<EXT>(m) && flags_match(BX_REFLECTION | BX_GLOSSY, flags);
-    // which lobe `which` designates: matte / plastic {D, G}; uber {T, D, G, R}; mirror / glass {R, T}
-    int pick = 0;                                                   // 1 = diffuse, 2 = glossy, 3 = specular R, 4 = specular T
-    if (EXT && m.type == RT_MAT_UBER) {
+    const bool diffuse_t_has = mat_has_diffuse_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_DIFFUSE, flags);     // constant false without EXT, as glossy_has
+    const bool glossy_t_has = mat_has_glossy_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_GLOSSY, flags);
+    const bool shiny = EXT && m.type == RT_MAT_SHINYMETAL;
+    // which lobe `which` designates: matte / plastic {D, G}; uber {T, D, G, R}; mirror / glass {R, T}; shinymetal {G, R}; translucent {D, DT, G, GT}
+    int pick = 0;                                                   // 1 = diffuse, 2 = glossy, 3 = specular R, 4 = specular T, 5 = diffuse T, 6 = glossy T
+    if (shiny) {
+        int idx = which;
+        if (glossy_has && idx-- == 0) pick = 2;
+        else if (flags_match(BX_REFLECTION | BX_SPECULAR, flags)) pick = 3;
+    } else if (EXT && m.type == RT_MAT_TRANSLUCENT) {
+        int idx = which;
+        if (diffuse_has && idx-- == 0) pick = 1;
+        else if (diffuse_t_has && idx-- == 0) pick = 5;
+        else if (glossy_has && idx-- == 0) pick = 2;
+        else if (glossy_t_has) pick = 6;
+    } else if (EXT && m.type == RT_MAT_UBER) {
         int idx = which;
         const bool mT = m.has_t && flags_match(BX_TRANSMISSION | BX_SPECULAR, flags), mR = m.has_kr && flags_match(BX_REFLECTION | BX_SPECULAR, flags);
         if (mT && idx-- == 0) pick = 4;
@@ -359,16 +412,22 @@ RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, fl
         else if (glossy_has && idx-- == 0) pick = 2;
         else if (mR) pick = 3;
     } else if (diffuse_has || glossy_has) pick = (!glossy_has || (diffuse_has && which == 0)) ? 1 : 2;   // glossy_has is constant false without EXT
-    if (pick == 1 || pick == 2) {
-        if (pick == 1) {
+    if (pick == 1 || pick == 2 || (EXT && (pick == 5 || pick == 6))) {
+        const bool through = EXT && (pick == 5 || pick == 6);           // BRDFToBTDF::Sample_f reflection.cpp:67-73: the wrapped lobe's sample and pdf, wi.z flipped
+        if (pick == 1 || (EXT && pick == 5)) {
             // BxDF::Sample_f reflection.cpp:219-226 with CosineSampleHemisphere mc.h:38-44
             float dx, dy; concentric_disk(u1, u2, dx, dy);
             wi = mk3(dx, dy, sqrtf(fmaxf(0.f, 1.f - dx * dx - dy * dy)));
             if (wo.z < 0.f) wi.z *= -1.f;
             pdf = diffuse_pdf(wo, wi);
             if (pdf == 0.f) return mk3(0.f);
-            sampled = BX_REFLECTION | BX_DIFFUSE;
-            if (glossy_has) pdf += glossy_pdf(m, wo, wi);                        // the other matching non-specular lobe, :436-443
+            sampled = through ? (BX_TRANSMISSION | BX_DIFFUSE) : (BX_REFLECTION | BX_DIFFUSE);
+            if (through) wi = other_hemisphere(wi);
+            // the other matching non-specular lobes in lobe order, :436-443
+            if (through && diffuse_has) pdf += diffuse_pdf(wo, wi);
+            if (!through && diffuse_t_has) pdf += diffuse_t_pdf(wo, wi);
+            if (glossy_has) pdf += glossy_pdf(m, wo, wi);
+            if (glossy_t_has) pdf += glossy_t_pdf(m, wo, wi);
         } else {
             // Microfacet::Sample_f reflection.cpp:235-240 with Blinn::Sample_f :246-262
             const float costheta = powf(u1, 1.f / (m.exponent + 1));
@@ -380,25 +439,31 @@ RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, fl
             pdf = ((m.exponent + 1.f) * powf(costheta, m.exponent)) / (2.f * RT_PI * 4.f * dot3(wo, H));
             if (dot3(wo, H) <= 0.f) pdf = 0.f;
             if (pdf == 0.f) return mk3(0.f);
-            sampled = BX_REFLECTION | BX_GLOSSY;
+            sampled = through ? (BX_TRANSMISSION | BX_GLOSSY) : (BX_REFLECTION | BX_GLOSSY);
+            if (through) wi = other_hemisphere(wi);
             if (diffuse_has) pdf += diffuse_pdf(wo, wi);
+            if (diffuse_t_has) pdf += diffuse_t_pdf(wo, wi);
+            if (through && glossy_has) pdf += glossy_pdf(m, wo, wi);
+            if (!through && glossy_t_has) pdf += glossy_t_pdf(m, wo, wi);
         }
         wiW = to_world(v, wi);
         if (matching > 1) pdf /= matching;
         f = mk3(0.f);
         if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) f = bsdf_f_lobes<EXT>(m, wo, wi, flags & ~BX_TRANSMISSION);
+        else if (mat_has_btdf<EXT>(m)) f = bsdf_f_lobes<EXT>(m, wo, wi, flags & ~BX_REFLECTION);
         return f;
     }
     // specular lobes, in the order the material added them (glass.cpp:56-61, mirror.cpp:51-53)
     bool reflect_has = m.has_r && ((BX_REFLECTION | BX_SPECULAR) & flags) == (BX_REFLECTION | BX_SPECULAR);
-    bool pick_reflect = (EXT && m.type == RT_MAT_UBER) ? pick == 3 : (reflect_has && which == 0);
+    bool pick_reflect = ((EXT && m.type == RT_MAT_UBER) || shiny) ? pick == 3 : (reflect_has && which == 0);
     if (pick_reflect) {
         // SpecularReflection::Sample_f reflection.cpp:96-103
         wi = mk3(-wo.x, -wo.y, wo.z);
         pdf = 1.f;
         const bool uber = EXT && m.type == RT_MAT_UBER;
         float F = (m.type == RT_MAT_GLASS) ? fresnel_dielectric(wo.z, 1.f, m.ior) : (uber ? fresnel_dielectric(wo.z, 1.5f, 1.f) : 1.f);
-        f = div_s(mk3(F) * (uber ? mat_color(m.kr) : mat_color(m.r)), fabsf(wi.z));
+        if (shiny) f = div_s(fr_cond(fabsf(wo.z), mat_color(m.kr)) * mk3(1.f), fabsf(wi.z));     // SpecularReflection(1, FresnelConductor(eta = m.kr, 0)) shinymetal.cpp:58, :61
+        else f = div_s(mk3(F) * (uber ? mat_color(m.kr) : mat_color(m.r)), fabsf(wi.z));
         sampled = BX_REFLECTION | BX_SPECULAR;
     } else {
         // SpecularTransmission::Sample_f reflection.cpp:104-127

@@ -1,6 +1,7 @@
 // scene_api.cpp -- see scene_api.h.  Citations are to the reference tree (/root/reference).
 #include "scene_api.h"
 #include "../../../include/pbrt_hip_desc.h"
+#include "../../../include/pbrt_hip_material.h"
 #include "exr_io.h"
 #include "../../../include/pbrt_hip_plugin.h"
 #include <dlfcn.h>
@@ -488,7 +489,7 @@ int PbrtApi::makeMaterial(const ParamSet &shapeParams) {
     auto clamp0 = [](Float3 c) { Float3 r = {c.x < 0.f ? 0.f : c.x, c.y < 0.f ? 0.f : c.y, c.z < 0.f ? 0.f : c.z}; return r; };
     RtMaterial m; std::memset(&m, 0, sizeof m);
     std::string name = gs.material;
-    if (name != "matte" && name != "mirror" && name != "glass" && name != "plastic" && name != "uber") {
+    if (name != "matte" && name != "mirror" && name != "glass" && name != "plastic" && name != "uber" && name != "shinymetal" && name != "translucent") {
         Error("Unable to load plugin \"%s\" (material); using \"matte\" (api.cpp:376-379)", name.c_str());
         name = "matte";
     }
@@ -515,6 +516,21 @@ int PbrtApi::makeMaterial(const ParamSet &shapeParams) {
         m.ks[0] = op.x * ks.x; m.ks[1] = op.y * ks.y; m.ks[2] = op.z * ks.z;
         m.kr[0] = op.x * kr.x; m.kr[1] = op.y * kr.y; m.kr[2] = op.z * kr.z;
         m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
+    } else if (name == "shinymetal") {                                              // shinymetal.cpp:43-73; the etas: include/pbrt_hip_material.h
+        Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{1.f, 1.f, 1.f}));
+        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
+        m.type = RT_MAT_SHINYMETAL; m.ior = 1.f;
+        m.ks[0] = ks.x; m.ks[1] = ks.y; m.ks[2] = ks.z; m.kr[0] = kr.x; m.kr[1] = kr.y; m.kr[2] = kr.z;
+        m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
+    } else if (name == "translucent") {                                             // translucent.cpp:45-94; kr = reflect, kt = transmit
+        Float3 kd = clamp0(spectrumParam(shapeParams, mp, "Kd", Float3{1.f, 1.f, 1.f}));
+        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
+        Float3 rf = clamp0(spectrumParam(shapeParams, mp, "reflect", Float3{.5f, .5f, .5f}));
+        Float3 tr = clamp0(spectrumParam(shapeParams, mp, "transmit", Float3{.5f, .5f, .5f}));
+        m.type = RT_MAT_TRANSLUCENT; m.ior = 1.f;
+        m.kd[0] = kd.x; m.kd[1] = kd.y; m.kd[2] = kd.z; m.ks[0] = ks.x; m.ks[1] = ks.y; m.ks[2] = ks.z;
+        m.kr[0] = rf.x; m.kr[1] = rf.y; m.kr[2] = rf.z; m.kt[0] = tr.x; m.kt[1] = tr.y; m.kt[2] = tr.z;
+        m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
     } else if (name == "mirror") {                                                  // mirror.cpp:42-61
         Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{1.f, 1.f, 1.f}));
         m.type = RT_MAT_MIRROR; m.kd[0] = kr.x; m.kd[1] = kr.y; m.kd[2] = kr.z; m.ior = 1.f;
@@ -524,6 +540,7 @@ int PbrtApi::makeMaterial(const ParamSet &shapeParams) {
         m.type = RT_MAT_GLASS; m.kd[0] = kr.x; m.kd[1] = kr.y; m.kd[2] = kr.z; m.kt[0] = kt.x; m.kt[1] = kt.y; m.kt[2] = kt.z;
         m.ior = floatParam(shapeParams, mp, "index", 1.5f);
     }
+    if (m.type == RT_MAT_SHINYMETAL || m.type == RT_MAT_TRANSLUCENT) mp.ReportUnused();     // MakeMaterial dynload.cpp:314 (the shape's own parameters were reported by the shape)
     materials.push_back(m);
     return int(materials.size()) - 1;
 }
@@ -884,6 +901,9 @@ const float *pbrt_host_camera(const RtSceneDesc *s) { return s->camera.raster_to
 const float *pbrt_host_tri_verts(const RtSceneDesc *s) { return s->tri_verts; }
 const RtAccelParams *pbrt_host_accel_params(const RtSceneDesc *s) { return &s->accel; }
 const RtVolume *pbrt_host_volume(const RtSceneDesc *s) { return &s->volume; }
+// the parsed material table and what rt_scene_create derives from one entry (include/pbrt_hip_material.h)
+const RtMaterial *pbrt_host_materials(const RtSceneDesc *s) { return s->materials; }
+void pbrt_host_material_lobes(const RtMaterial *m, RtMaterialLobes *out) { rt_material_lobes(m, out); }
 // the frame's DensityRegion for rt_scene_set_density, or NULL when its medium (if any) is homogeneous
 const RtDensityRegion *pbrt_host_density_desc(PbrtHostScene *h, int i) {
     const SceneDescription *sd = h->api.frames[i];
