@@ -57,10 +57,14 @@ typedef struct RtMaterial {
 } RtMaterial;
 
 /* ---- lights: lights/point.cpp:49-69, lights/area.cpp:28-105, lights/spot.cpp:54-79, lights/distant.cpp:51-62 ---- */
-enum { RT_LIGHT_POINT = 0, RT_LIGHT_AREA = 1, RT_LIGHT_SPOT = 2, RT_LIGHT_DISTANT = 3 };
+/*      RT_LIGHT_INFINITE: InfiniteAreaLight with a constant radiance (lights/infinite.cpp:66-131, :155-169; no radiance map).  It needs the EXT
+ *      kernels.  It uses `color` (= L, Le of every ray that leaves the scene: whitted.cpp:52-58, directlighting.cpp:186-191, path.cpp:68-82,
+ *      transport.cpp:184-185) and `n_samples`; every other field is ignored, the record keeps its size and offsets.  One estimate of it draws one
+ *      RandomFloat() (infinite.cpp:104), so rt_render refuses it together with RT_STRATEGY_WEIGHTED.                      */
+enum { RT_LIGHT_POINT = 0, RT_LIGHT_AREA = 1, RT_LIGHT_SPOT = 2, RT_LIGHT_DISTANT = 3, RT_LIGHT_INFINITE = 4 };
 typedef struct RtLight {
     int32_t type;
-    float color[3];      /* point/spot: I   area: Lemit   distant: L                 */
+    float color[3];      /* point/spot: I   area: Lemit   distant / infinite: L      */
     float pos[3];        /* point/spot light position (world, LightToWorld(0,0,0))  */
     int32_t n_samples;   /* Light::nSamples (light.h:39)                            */
     uint32_t first_tri;  /* area: range in light_tris (ShapeSet order, shape.h:112) */

@@ -166,6 +166,14 @@ class RtMaterialLobes(C.Structure):                # include/pbrt_hip_material.h
 
 RT_DENSITY_NAMES = {1: "exponential", 2: "volumegrid"}
 
+RT_LIGHT_NAMES = ("point", "area", "spot", "distant", "infinite")
+
+
+class RtLight(C.Structure):                        # include/pbrt_hip.h (108 bytes)
+    _fields_ = [("type", C.c_int32), ("color", C.c_float * 3), ("pos", C.c_float * 3), ("n_samples", C.c_int32), ("first_tri", C.c_uint32),
+                ("n_tris", C.c_uint32), ("reverse_orientation", C.c_int32), ("flip_normal", C.c_int32), ("dir", C.c_float * 3),
+                ("world_to_light", C.c_float * 9), ("cos_total_width", C.c_float), ("cos_falloff_start", C.c_float), ("quadric_plus1", C.c_int32)]
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -297,6 +305,8 @@ def host_lib():
         L.pbrt_host_materials.restype = C.POINTER(RtMaterial)
         L.pbrt_host_materials.argtypes = [C.c_void_p]
         L.pbrt_host_material_lobes.argtypes = [C.POINTER(RtMaterial), C.POINTER(RtMaterialLobes)]
+        L.pbrt_host_lights.restype = C.POINTER(RtLight)
+        L.pbrt_host_lights.argtypes = [C.c_void_p]
         _host = L
     return _host
 
@@ -596,6 +606,26 @@ class ParsedScene:
                               "reflect*Kd": f3(lb.r_kd), "transmit*Kd": f3(lb.t_kd), "reflect*Ks": f3(lb.r_ks), "transmit*Ks": f3(lb.t_ks)})
                     d["lobes"] = [n for n, on in (("diffuse_reflection", lb.has_dr), ("diffuse_transmission", lb.has_dt),
                                                   ("glossy_reflection", lb.has_gr), ("glossy_transmission", lb.has_gt)) if on]
+            out.append(d)
+        return out
+
+    def lights(self) -> list:
+        """The parsed light table (RtLight, include/pbrt_hip.h) in scene order as dictionaries: `type` (the light's name), `nsamples` and its
+        colour as a float32 array under the reference's parameter name (`I` point / spot, `L` area / distant / infinite); point and spot
+        lights also carry `from` (world space), distant lights `dir`, area lights `n_tris`."""
+        tab = host_lib().pbrt_host_lights(self.scene_desc)
+        f3 = lambda a: np.array(list(a), np.float32)
+        out = []
+        for i in range(self.n_lights):
+            l = tab[i]
+            name = RT_LIGHT_NAMES[l.type]
+            d = {"type": name, "nsamples": int(l.n_samples), ("I" if name in ("point", "spot") else "L"): f3(l.color)}
+            if name in ("point", "spot"):
+                d["from"] = f3(l.pos)
+            elif name == "distant":
+                d["dir"] = f3(l.dir)
+            elif name == "area":
+                d["n_tris"] = int(l.n_tris)
             out.append(d)
         return out
 

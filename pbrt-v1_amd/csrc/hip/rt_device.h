@@ -56,6 +56,7 @@ struct DevLight {
     int quadric;       // area light on a quadric: index into DevScene::quadrics, else -1 (read by the EXT kernels)
     float w2l[9];      // spot: WorldToLight 3x3
     float cos_total, cos_falloff;
+    // RT_LIGHT_INFINITE (infinite.cpp, constant radiance): color = L, n_samples; nothing else is read
 };
 
 #define RT_MAX_DIM_REQ 12         // requests the frame descriptor itself carries (PathIntegrator: 11 one-dimensional, 9 two-dimensional); DirectLighting "all"
@@ -103,6 +104,7 @@ struct DevScene {
     float dens_a, dens_b, dens_up[3];      // ExponentialDensity (exponential.cpp:27-52)
     int dens_n[3];                         // VolumeGrid (volumegrid.cpp:27-84): nx, ny, nz and density[z*nx*ny + y*nx + x]
     const float *dens_grid;
+    int n_infinite;                        // RT_LIGHT_INFINITE lights in `lights` (read only by the EXT kernels; last, so that no other field moved)
 };
 
 #define RT_INTEG_DIRECT_WEIGHTED 3    // device-side template value only: DirectLighting with strategy "weighted" (render_kernel family g_render_kernels_weighted)

@@ -74,6 +74,7 @@ struct RtScene {
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
     unsigned *wt_recbase = nullptr; size_t wt_recbase_cap = 0;
+    unsigned n_infinite = 0;           // RT_LIGHT_INFINITE lights (each estimate draws one RandomFloat(), infinite.cpp:104: refused with strategy "weighted")
     int light_draws = 0;               // RandomFloat()s one EstimateDirect draws: the same for every light (0 / 1), or -1 when the lights differ
     unsigned *wt_base = nullptr; size_t wt_base_cap = 0; float *wt_rec = nullptr; size_t wt_rec_cap = 0; float2 *wt_pick = nullptr; size_t wt_pick_cap = 0;
     unsigned long long *wt_sums = nullptr;                     // per-block sums of the point-count scan

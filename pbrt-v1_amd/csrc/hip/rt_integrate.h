@@ -477,16 +477,19 @@ template <bool EXT, bool DEFER = false>
 RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
     LightRef Lt = RT_LIGHT(sc, ln.cur_light);
     ln.stage = ST_ED_DONE;
-    if (light_is_delta(Lt)) return;                                             // IsDeltaLight()
+    if (light_is_delta<EXT>(Lt)) return;                                        // IsDeltaLight()
     MatRef m = RT_MAT(sc, ln.v.mat);
     V3 wi; float bsdfPdf; int sampled;
     V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, ln.bs1, ln.bs2, ln.bcs, bsdfPdf, BX_ALL & ~BX_SPECULAR, sampled);
     if (!is_black(f) && bsdfPdf > 0.f) {
-        float lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+        float lightPdf;
+        if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(ln.v.nn, wi) : area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+        else lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);            // (the other kernels' statement, as it was)
         if (lightPdf > 0.f) {
             float fw = 1 * bsdfPdf, gw = 1 * lightPdf;                            // PowerHeuristic mc.h:55-59
             float weight = (fw * fw) / (fw * fw + gw * gw);
-            // Li is Lemit iff the closest hit is this emitter seen from its front side; decided after the trace
+            // Li is Lemit iff the closest hit is this emitter seen from its front side -- the infinite light's L iff the ray hits nothing
+            // (light->Le(ray), transport.cpp:184-185); decided after the trace
             ln.pend = div_s(((f * mat_color(Lt.color)) * absdot3(wi, ln.v.nn)) * weight, bsdfPdf);
             launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_MIS_DONE);
         }
@@ -494,7 +497,8 @@ RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
 }
 
 // DirectLighting "weighted" (rt_weighted.h): does one EstimateDirect of this light draw a random number (ShapeSet::Sample's triangle pick, shape.h:115-121)?
-RT_DEV bool light_draws_rng(LightRef L) { return !light_is_delta(L) && L.quadric < 0 && L.n_tris > 1u; }
+// (an infinite light draws too, infinite.cpp:104: rt_render refuses it with this strategy, so only emitters are asked here)
+RT_DEV bool light_draws_rng(LightRef L) { return L.type == RT_LIGHT_AREA && L.quadric < 0 && L.n_tris > 1u; }
 // ... and where the survey's record of the lane's current shading point starts in DevFrame::wt_rec (floats)
 RT_DEV size_t weighted_record(const DevFrame &fr, const Lane &ln, int nLights) {
     if (!fr.wt_mixed) return size_t(ln.ord) * size_t(1 + 2 * nLights);
@@ -510,9 +514,22 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
     LightRef Lt = RT_LIGHT(sc, light);
     MatRef m = RT_MAT(sc, ln.v.mat);
     V3 wi, Li, sd; float lightPdf, smax;
-    if (light_is_delta(Lt)) {                                                   // point.cpp:61-66, spot.cpp:80-84, distant.cpp:63-67
+    if (light_is_delta<EXT>(Lt)) {                                              // point.cpp:61-66, spot.cpp:80-84, distant.cpp:63-67
         Li = delta_light_sample(Lt, ln.v.p, wi, sd, smax);
         lightPdf = 1.f;
+    } else if constexpr (EXT) {                                                 // (discarded in the other kernels: their code is what it was)
+        if (light_is_infinite<EXT>(Lt)) {                                       // infinite.cpp:96-116, n = bsdf->dgShading.nn; SetRay(p, wi)
+            wi = infinite_sample_cosine(ln.v.nn, ls1, ls2, ln.rng, lightPdf);
+            Li = mat_color(Lt.color);
+            sd = wi; smax = RT_INF;
+        } else {                                                                // area.cpp:58-68
+            V3 ns;
+            V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
+            wi = normalize3(ps - ln.v.p);
+            lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+            Li = area_L(Lt, ns, -wi);
+            sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
+        }
     } else {                                                                    // area.cpp:58-68
         V3 ns;
         V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
@@ -524,7 +541,7 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
     if (lightPdf > 0.f && !is_black(Li)) {
         V3 f = bsdf_f<EXT>(m, ln.v, ln.v.wo, wi);
         if (!is_black(f)) {
-            if (light_is_delta(Lt)) ln.pend = div_s((f * Li) * absdot3(wi, ln.v.nn), lightPdf);
+            if (light_is_delta<EXT>(Lt)) ln.pend = div_s((f * Li) * absdot3(wi, ln.v.nn), lightPdf);
             else {
                 float bsdfPdf = bsdf_pdf<EXT>(m, ln.v, ln.v.wo, wi);
                 float fw = 1 * lightPdf, gw = 1 * bsdfPdf;
@@ -620,8 +637,15 @@ RT_DEV bool march_steps(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
                 const int lightNum = min(int(floorf(r0 * nLights)), nLights - 1);
                 LightRef Lt = RT_LIGHT(sc, lightNum);
                 V3 wo, L, sd; float pdf, smax;
-                if (light_is_delta(Lt)) { L = delta_light_sample(Lt, p, wo, sd, smax); pdf = 1.f; }
-                else {
+                if (light_is_delta<EXT>(Lt)) { L = delta_light_sample(Lt, p, wo, sd, smax); pdf = 1.f; }
+                else if constexpr (EXT) {                                       // (a discarded statement in the other kernels: their code is what it was)
+                    if (light_is_infinite<EXT>(Lt)) { wo = infinite_sample_sphere(u1, u2, pdf); L = mat_color(Lt.color); sd = wo; smax = RT_INF; }   // infinite.cpp:121-128
+                    else {
+                        V3 ns; V3 ps = area_sample_point<EXT>(sc, Lt, p, u1, u2, ln.rng, ns);
+                        wo = normalize3(ps - p); pdf = area_light_pdf<EXT>(sc, Lt, p, wo); L = area_L(Lt, ns, -wo);
+                        sd = ps - p; smax = 1.f - RT_RAY_EPSILON;
+                    }
+                } else {
                     V3 ns; V3 ps = area_sample_point<EXT>(sc, Lt, p, u1, u2, ln.rng, ns);
                     wo = normalize3(ps - p); pdf = area_light_pdf<EXT>(sc, Lt, p, wo); L = area_L(Lt, ns, -wo);
                     sd = ps - p; smax = 1.f - RT_RAY_EPSILON;
@@ -664,7 +688,11 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         const bool hit = ln.tv.hit_prim >= 0;
         if (INTEG == RT_INTEGRATOR_PATH) {
             if (!hit) {                                                         // path.cpp:68-83: point/area lights have Le(ray)=0
+                // ... and an infinite light's is its L: added at pathLength == 0, and after a specular bounce scaled by the throughput (:78-81;
+                // Scene::Render always passes an alpha, which that branch asks for and leaves alone)
+                if (EXT && ln.depth == 0) ln.L = infinite_le_sum(sc, ln.L, mk3(1.f), false);
                 if (ln.depth == 0) ln.alpha = (ln.L.x != 0.f || ln.L.y != 0.f || ln.L.z != 0.f) ? 1.f : 0.f;
+                else if (EXT && ln.specular) ln.L = infinite_le_sum(sc, ln.L, ln.thr, true);
                 ln.stage = ST_RETURN; return;
             }
             make_vertex<EXT>(sc, ln.tv, ln.v);
@@ -678,9 +706,13 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             if ((ln.depth == 0 || ln.specular) && ln.v.light >= 0)              // path.cpp:91-92
                 ln.L = ln.L + ln.thr * area_L(RT_LIGHT(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);   // isect.Le: dg.nn, the geometric normal
         } else {
-            if (!hit) {                                                         // whitted.cpp:52-59
+            if (!hit) {                                                         // whitted.cpp:52-59, directlighting.cpp:186-191
                 ln.L = mk3(0.f);
                 if (ln.depth == 0) ln.alpha = 0.f;
+                if (EXT) {                                                      // L += lights[i]->Le(ray); alpha = 1 unless the sum is black
+                    ln.L = infinite_le_sum(sc, ln.L, mk3(1.f), false);
+                    if (ln.depth == 0 && !is_black(ln.L)) ln.alpha = 1.f;
+                }
                 ln.stage = ST_RETURN; return;
             }
             make_vertex<EXT>(sc, ln.tv, ln.v);
@@ -765,8 +797,24 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             MatRef m = RT_MAT(sc, ln.v.mat);
             const int cur = ln.li++;
             V3 wi, Li, sd; float smax;
-            if (light_is_delta(Lt)) Li = delta_light_sample(Lt, ln.v.p, wi, sd, smax);   // point.cpp:55-60, spot.cpp:61-67, distant.cpp:57-62
-            else {                                                              // area.cpp:96-105
+            if (light_is_delta<EXT>(Lt)) Li = delta_light_sample(Lt, ln.v.p, wi, sd, smax);   // point.cpp:55-60, spot.cpp:61-67, distant.cpp:57-62
+            else if constexpr (EXT) {                                           // (discarded in the other kernels: their code is what it was)
+                if (light_is_infinite<EXT>(Lt)) {                               // infinite.cpp:155-162: the form without a normal, L / pdf
+                    float u2 = ln.rng.next_float();     // the two RandomFloat() arguments, right to left
+                    float u1 = ln.rng.next_float();
+                    float pdf; wi = infinite_sample_sphere(u1, u2, pdf);
+                    Li = (pdf == 0.f) ? mk3(0.f) : div_s(mat_color(Lt.color), pdf);
+                    sd = wi; smax = RT_INF;
+                } else {                                                          // area.cpp:96-105
+                    float u2 = ln.rng.next_float();     // g++ evaluates the two RandomFloat() arguments right to left
+                    float u1 = ln.rng.next_float();
+                    V3 ns; V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, u1, u2, ln.rng, ns);
+                    wi = normalize3(ps - ln.v.p);
+                    float pdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+                    Li = (pdf == 0.f) ? mk3(0.f) : div_s(area_L(Lt, ns, -wi), pdf);
+                    sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
+                }
+            } else {                                                              // area.cpp:96-105
                 float u2 = ln.rng.next_float();     // g++ evaluates the two RandomFloat() arguments right to left
                 float u1 = ln.rng.next_float();
                 V3 ns; V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, u1, u2, ln.rng, ns);
@@ -809,6 +857,10 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 if (dot3(nh, -ln.tv.d) > 0)                                    // isect.Le(-wi) non-black; transport.cpp:188-190
                     ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
             }
+        } else if (EXT) {                                                       // Li = light->Le(ray), :184-185: an infinite light's L, unless black (:186)
+            LightRef Lt = RT_LIGHT(sc, ln.cur_light);
+            if (Lt.type == RT_LIGHT_INFINITE && !is_black(mat_color(Lt.color)))
+                ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
         }
         ln.stage = ST_ED_DONE;
         return;

@@ -436,6 +436,10 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
         if (s->volume.present && s->light_draws != 0) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" in a participating medium needs lights whose estimates draw no random numbers "
                                                                             "(point / spot / distant / single-triangle / quadric lights): an emitter of several triangles draws its triangle, and the medium makes "
                                                                             "the draw's position in the stream depend on occlusion");
+        // An infinite light draws one RandomFloat() per estimate (infinite.cpp:104), whatever the light sample: the survey would have to keep one estimate of it
+        // per position of that draw, as it does for emitters of several triangles (DevFrame::wt_mixed); that is not built.
+        if (s->n_infinite != 0) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" with an infinite light is not supported (the light draws a random number per estimate); "
+                                                       "use strategy \"one\" or \"all\"");
         if (s->dev.n_lights > 2048u) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" holds the per-light tables of its recurrence in LDS: at most 2048 lights");
         if (fr.total_work >= 0xffffffffull) return fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 camera samples in the frame");
     }

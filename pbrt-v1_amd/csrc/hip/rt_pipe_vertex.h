@@ -88,6 +88,9 @@ __global__ __launch_bounds__(RT_BLOCK, (EXT && !COUNT) ? 3 : 1) void pipe_vertex
                     V3 nh; int light;
                     prim_normal_light<EXT>(sc, ln.tv, nh, light);
                     if (light == ln.cur_light && dot3(nh, -ln.tv.d) > 0) Ld = Ld + mk3(a6.x, a6.y, a6.z) * mk3(1.f);
+                } else if (EXT) {                                        // the ray left the scene: light->Le(ray), an infinite light's L (transport.cpp:184-186)
+                    LightRef Lt = RT_LIGHT(sc, ln.cur_light);
+                    if (Lt.type == RT_LIGHT_INFINITE && !is_black(mat_color(Lt.color))) Ld = Ld + mk3(a6.x, a6.y, a6.z) * mk3(1.f);
                 }
             }
             ln.L = ln.L + thr_old * (Ld * float(nLights));

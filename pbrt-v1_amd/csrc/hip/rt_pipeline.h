@@ -148,8 +148,10 @@ RT_DEV void pipe_store(const PipePool &pl, unsigned slot, const Lane &ln) {
 }
 
 // ---- shade: everything between two rays of a path, for every slot ---------------------------------------------------
+// (the counting EXT kernel of DirectLighting with a medium allocates 170 VGPRs on its own since the infinite light, 2 above the 3-wave step of gfx950: held to
+// 3 waves, without scratch -- DESIGN.md 4.9; a minimum of 1 is what every other instantiation had and keeps)
 template <bool COUNT, int INTEG, bool VOL, bool EXT>
-__global__ __launch_bounds__(RT_BLOCK, 1) void pipe_shade_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
+__global__ __launch_bounds__(RT_BLOCK, (EXT && COUNT && VOL && INTEG == RT_INTEGRATOR_DIRECT) ? 3 : 1) void pipe_shade_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
                                                                const PipePool *__restrict__ plp, PipeLaunch pk) {
     const DevScene &sc = *scp;
     const DevFrame &fr = *frp;

@@ -498,7 +498,8 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         o.cos_total = L.cos_total_width; o.cos_falloff = L.cos_falloff_start;
         o.quadric = L.quadric_plus1 - 1;
         if (L.quadric_plus1 < 0 || uint32_t(L.quadric_plus1) > d->n_quadrics) return fail(RT_EINVAL, "rt_scene_create: light refers to a quadric out of range");
-        if (L.type < RT_LIGHT_POINT || L.type > RT_LIGHT_DISTANT) return fail(RT_EINVAL, "rt_scene_create: unknown light type");
+        if (L.type < RT_LIGHT_POINT || L.type > RT_LIGHT_INFINITE) return fail(RT_EINVAL, "rt_scene_create: unknown light type");
+        if (L.type == RT_LIGHT_INFINITE) { s->has_ext = true; ++s->n_infinite; }      // the light's code exists only in the EXT kernels
         if (L.type != RT_LIGHT_AREA) continue;
         if (size_t(L.first_tri) + L.n_tris > d->n_light_tris) return fail(RT_EINVAL, "rt_scene_create: light triangle range out of bounds");
         float area = 0.f; std::vector<float> areas;
@@ -534,7 +535,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         if ((rc = upload(s, flags.data(), flags.size(), &s->light_draw_flags))) return rc;      // (read by the recurrence of a "weighted" frame with lights of mixed RNG use)
     }
 
-    s->dev.n_tris = d->n_tris; s->dev.n_lights = d->n_lights;
+    s->dev.n_tris = d->n_tris; s->dev.n_lights = d->n_lights; s->dev.n_infinite = int(s->n_infinite);
     s->dev.accel_kind = s->accel_kind;
     for (int a = 0; a < 3; ++a) { s->dev.nvox[a] = s->gridacc.nvox[a]; s->dev.gwidth[a] = s->gridacc.width[a]; s->dev.ginv_width[a] = s->gridacc.inv_width[a]; }
     std::memcpy(s->dev.bounds, s->tree.bounds, sizeof s->dev.bounds);

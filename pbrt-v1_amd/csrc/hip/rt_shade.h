@@ -496,7 +496,12 @@ RT_DEV void light_tri(const DevScene &sc, unsigned k, V3 &p1, V3 &p2, V3 &p3) {
 // ---- delta lights: {Point,Spot,Distant}Light::Sample_L(p, &wi, &visibility) (point.cpp:55-60, spot.cpp:61-79,
 // distant.cpp:57-62).  Returns the incident radiance; `sd`, `smax` = the visibility ray's direction and maxt
 // (SetSegment: p -> light position, maxt 1 - eps; SetRay: p along wi, unbounded; light.h:78-83).
-RT_DEV bool light_is_delta(LightRef Lt) { return Lt.type != RT_LIGHT_AREA; }
+// (IsDeltaLight(): the area light says no, and -- in the EXT kernels, the only ones a scene with one runs -- the infinite light, infinite.cpp:45)
+template <bool EXT> RT_DEV bool light_is_infinite(LightRef Lt) { return EXT && Lt.type == RT_LIGHT_INFINITE; }
+template <bool EXT> RT_DEV bool light_is_delta(LightRef Lt) {
+    if constexpr (EXT) return Lt.type != RT_LIGHT_AREA && Lt.type != RT_LIGHT_INFINITE;
+    else return Lt.type != RT_LIGHT_AREA;
+}
 RT_DEV V3 delta_light_sample(LightRef Lt, V3 p, V3 &wi, V3 &sd, float &smax) {
     if (Lt.type == RT_LIGHT_DISTANT) {
         wi = mk3(Lt.dir[0], Lt.dir[1], Lt.dir[2]);
@@ -519,6 +524,47 @@ RT_DEV V3 delta_light_sample(LightRef Lt, V3 p, V3 &wi, V3 &sd, float &smax) {
     else if (costheta > Lt.cos_falloff) fall = 1.f;
     else { const float delta = (costheta - Lt.cos_total) / (Lt.cos_falloff - Lt.cos_total); fall = delta * delta * delta * delta; }
     return div_s(mat_color(Lt.color) * fall, d2);
+}
+
+// ---- the infinite area light with a constant radiance (lights/infinite.cpp; EXT kernels only).  Le(ray) = L for every ray (:83-95, no map).
+// CoordinateSystem geometry.h:324-334
+RT_DEV void coordinate_system(V3 v1, V3 &v2, V3 &v3) {
+    if (fabsf(v1.x) > fabsf(v1.y)) { const float il = 1.f / sqrtf(v1.x * v1.x + v1.z * v1.z); v2 = mk3(-v1.z * il, 0.f, v1.x * il); }
+    else { const float il = 1.f / sqrtf(v1.y * v1.y + v1.z * v1.z); v2 = mk3(0.f, v1.z * il, -v1.y * il); }
+    v3 = cross3(v1, v2);
+}
+// Sample_L(p, n, u1, u2, wi, pdf, vis) :96-116: a cosine-weighted direction about +-n.  ConcentricSampleDisk, z flipped by ONE RandomFloat() drawn
+// here (after the estimate's sample values, before anything the BSDF half draws), pdf = |z| / 2 pi, the frame from CoordinateSystem(Normalize(n))
+// with n itself -- not the normalised copy -- in the third column.  The visibility ray is SetRay(p, wi): mint = RAY_EPSILON, maxt = infinity.
+template <class RNG>
+RT_DEV V3 infinite_sample_cosine(V3 n, float u1, float u2, RNG &rng, float &pdf) {
+    float x, y; concentric_disk(u1, u2, x, y);
+    float z = sqrtf(fmaxf(0.f, 1.f - x * x - y * y));
+    if (rng.next_float() < .5f) z *= -1.f;
+    pdf = fabsf(z) * RT_INV_TWOPI;
+    V3 v1, v2; coordinate_system(normalize3(n), v1, v2);
+    return mk3(v1.x * x + v2.x * y + n.x * z, v1.y * x + v2.y * y + n.y * z, v1.z * x + v2.z * y + n.z * z);
+}
+// Pdf(p, n, wi) :117-120
+RT_DEV float infinite_pdf_cosine(V3 n, V3 wi) { return absdot3(n, wi) * RT_INV_TWOPI; }
+// Sample_L(p, u1, u2, wi, pdf, vis) :121-128: UniformSampleSphere (mc.cpp:74-81), pdf = UniformSpherePdf() = 1 / (4 pi) (mc.cpp:82-84; Pdf(p, wi) :129-131)
+RT_DEV V3 infinite_sample_sphere(float u1, float u2, float &pdf) {
+    const float z = 1.f - 2.f * u1;
+    const float r = sqrtf(fmaxf(0.f, 1.f - z * z));
+    const float phi = 2.f * RT_PI * u2;
+    pdf = 1.f / (4.f * RT_PI);
+    return mk3(r * cosf(phi), r * sinf(phi), z);
+}
+// the sum of Le(ray) over the lights, as the integrators form it for a ray that leaves the scene: `acc` += w * L per infinite light, in light order
+// (every other light's Le is black, light.cpp / light.h:60-62, and adding it changes nothing)
+RT_DEV V3 infinite_le_sum(const DevScene &sc, V3 acc, V3 w, bool weighted) {
+    if (sc.n_infinite == 0) return acc;
+    const int nLights = int(sc.n_lights);
+    for (int i = 0; i < nLights; ++i) {
+        LightRef Lt = RT_LIGHT(sc, i);
+        if (Lt.type == RT_LIGHT_INFINITE) acc = acc + (weighted ? w * mat_color(Lt.color) : mat_color(Lt.color));
+    }
+    return acc;
 }
 
 // ---- area lights on quadrics: {Sphere,Disk,Cylinder}::Sample / ::Pdf / ::Area (sphere.cpp:36-86,:251-253, disk.cpp:37-46,:124-127,

@@ -463,6 +463,15 @@ void PbrtApi::LightSource(const std::string &n, const ParamList &p) {
         float il = 1.f / std::sqrt(wx * wx + wy * wy + wz * wz);
         L.type = RT_LIGHT_DISTANT; L.color[0] = Lr.x; L.color[1] = Lr.y; L.color[2] = Lr.z;
         L.dir[0] = wx * il; L.dir[1] = wy * il; L.dir[2] = wz * il;
+    } else if (n == "infinite") {
+        // CreateLight lights/infinite.cpp:163-169 + InfiniteAreaLight ctor :66-82.  The light-to-world transform only orients the radiance map
+        // (Le, :88-93): with a constant L it has no effect.  No image reader here (nor in the oracle build, whose ReadImage returns NULL: the
+        // light then renders with L alone, :76-81): a map is an Error that says so, and L is kept.
+        Float3 Lr = ps.FindOneSpectrum("L", Float3{1.f, 1.f, 1.f});
+        std::string texmap = ps.FindOneString("mapname", "");
+        L.n_samples = std::max(1, ps.FindOneInt("nsamples", 1));                                  // Light ctor light.h:39
+        if (!texmap.empty()) Error("LightSource \"infinite\": radiance maps are not supported (\"mapname\" \"%s\" ignored, the light renders with L alone)", texmap.c_str());
+        L.type = RT_LIGHT_INFINITE; L.color[0] = Lr.x; L.color[1] = Lr.y; L.color[2] = Lr.z;
     } else { Error("pbrtLightSource: light type \"%s\" unknown.", n.c_str()); return; }
     ps.ReportUnused();
     lights.push_back(L);
@@ -903,6 +912,7 @@ const RtAccelParams *pbrt_host_accel_params(const RtSceneDesc *s) { return &s->a
 const RtVolume *pbrt_host_volume(const RtSceneDesc *s) { return &s->volume; }
 // the parsed material table and what rt_scene_create derives from one entry (include/pbrt_hip_material.h)
 const RtMaterial *pbrt_host_materials(const RtSceneDesc *s) { return s->materials; }
+const RtLight *pbrt_host_lights(const RtSceneDesc *s) { return s->lights; }      // the parsed light table (n_lights of pbrt_host_scene_counts)
 void pbrt_host_material_lobes(const RtMaterial *m, RtMaterialLobes *out) { rt_material_lobes(m, out); }
 // the frame's DensityRegion for rt_scene_set_density, or NULL when its medium (if any) is homogeneous
 const RtDensityRegion *pbrt_host_density_desc(PbrtHostScene *h, int i) {

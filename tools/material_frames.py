@@ -4,7 +4,8 @@
 
 The frame is the Cornell box plus the 1 M-triangle soup of bench.py's workloads, path tracing (maxdepth 5), N x N pixels (default 1024)
 at S x S jittered samples (default 2 x 2).  `plastic`: every soup triangle is plastic (the EXT kernels with the materials they had before);
-`mixed`: the soup's triangles cycle through shinymetal, translucent and matte (triangle index modulo 3).  Each frame is rendered once with
+`mixed`: the soup's triangles cycle through shinymetal, translucent and matte (triangle index modulo 3); `plastic_infinite`: the plastic frame with
+the box's emitter replaced by an infinite light.  Each frame is rendered once with
 the counting kernels (the ray count) and then with the timed kernels; one JSON line per frame gives the GPU milliseconds of every step
 (rt_last_render_stats), their median and Mrays/s at the median.  To compare two builds of the device library, run it once per library
 (PBRT_HIP_TUNE=1 PBRT_HIP_LIB_PATH=<libpbrt_hip_NAME.so>, tools/build_variant.py) alternately in one session."""
@@ -30,11 +31,11 @@ MATERIALS = {
 
 
 def frame_text(scenes, kind, soup, res, side):
-    mats = MATERIALS[kind]
+    mats = MATERIALS["plastic" if kind == "plastic_infinite" else kind]
     cls = np.arange(soup.shape[0]) % len(mats)
     blocks = "".join("AttributeBegin # soup %d\n  %s\n  %sAttributeEnd\n" % (i, m, scenes.soup_shape_text(soup[cls == i])) for i, m in enumerate(mats))
     return scenes.options_block(xres=res, yres=res, integrator="path", maxdepth=5, xsamples=side, ysamples=side, jitter=True) + \
-        scenes.cornell_world(extra=blocks)
+        (scenes.cornell_world(area_light=False, extra='LightSource "infinite" "color L" [.8 .9 1]\n' + blocks) if kind == "plastic_infinite" else scenes.cornell_world(extra=blocks))
 
 
 def main():
