@@ -180,7 +180,9 @@ typedef struct RtSceneDesc {
 } RtSceneDesc;
 
 /* ---- per-frame description ---- */
-enum { RT_INTEGRATOR_WHITTED = 0, RT_INTEGRATOR_DIRECT = 1, RT_INTEGRATOR_PATH = 2 };
+enum { RT_INTEGRATOR_WHITTED = 0, RT_INTEGRATOR_DIRECT = 1, RT_INTEGRATOR_PATH = 2, RT_INTEGRATOR_BIDIRECTIONAL = 3 };
+/* RT_INTEGRATOR_BIDIRECTIONAL: BidirIntegrator (integrators/bidirectional.cpp:80-131), eye and light sub-paths of at most 4 vertices each.  Its factory
+ * reads no parameter (:211-213): max_depth and strategy are ignored.  rt_render refuses it in a participating medium and in a scene without lights. */
 enum { RT_STRATEGY_ALL = 0, RT_STRATEGY_ONE = 1, RT_STRATEGY_WEIGHTED = 2 };
 /* RT_STRATEGY_WEIGHTED: WeightedSampleOneLight (transport.cpp:71-122), a recurrence over every shading point of the frame in program order.
  * rt_render accepts it on one shard (shard_count == 1) with at most 2048 lights of any mix (round 5: emitters of several triangles, which draw one
@@ -201,7 +203,7 @@ enum { RT_VOLUME_NONE = 0, RT_VOLUME_EMISSION = 1, RT_VOLUME_SINGLE = 2 };
 enum { RT_SAMPLER_STRATIFIED = 0, RT_SAMPLER_LOWDISCREPANCY = 1, RT_SAMPLER_RANDOM = 2 };
 
 typedef struct RtRenderDesc {
-    /* SurfaceIntegrator: integrators/{whitted,directlighting,path}.cpp factories */
+    /* SurfaceIntegrator: integrators/{whitted,directlighting,path,bidirectional}.cpp factories */
     int32_t integrator, max_depth, strategy;
     /* VolumeIntegrator: integrators/{emission,single}.cpp */
     int32_t volume_integrator;

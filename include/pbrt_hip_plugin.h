@@ -7,7 +7,7 @@
  * The host library keeps that mechanism for the plugin kinds of the hot path: `SurfaceIntegrator "name"` first looks for <name>.so (or
  * lib<name>.so) in the directories of PBRT_HIP_PLUGIN_PATH and of the scene's SearchPath directives, resolves the factory below and calls
  * it; when no such file exists -- or the file is not a plugin of THIS library -- it falls back to the plugins compiled into the library
- * (whitted, directlighting, path; emission, single; stratified, lowdiscrepancy, random; kdtree, grid).
+ * (whitted, directlighting, path, bidirectional; emission, single; stratified, lowdiscrepancy, random; kdtree, grid).
  * The factories are named PbrtHipCreate<Kind>, NOT Create<Kind>: a SearchPath that points at a pbrt-v1 install holds stratified.so,
  * kdtree.so, ... whose Create<Kind>(const ParamSet &, ...) is another ABI; such an object fails to load here (its core symbols are
  * unresolved) or lacks PbrtHipCreate<Kind>, either way a warning at most and the built-in answers.  PBRT_SEARCHPATH (the reference's
@@ -34,6 +34,7 @@ typedef struct PbrtHipParamsApi {                           /* ParamSet::FindOne
     const char *(*find_string)(const PbrtHipParams *, const char *name, const char *dflt);    /* every string handed out stays valid until the factory returns */
 } PbrtHipParamsApi;
 
+/* kind: RT_INTEGRATOR_WHITTED .. RT_INTEGRATOR_BIDIRECTIONAL (the last ignores max_depth and strategy) */
 typedef struct PbrtHipSurfaceIntegrator { int32_t kind /* RT_INTEGRATOR_* */, max_depth, strategy /* RT_STRATEGY_* (directlighting) */; } PbrtHipSurfaceIntegrator;
 typedef struct PbrtHipVolumeIntegrator { int32_t kind /* RT_VOLUME_* */; float step_size; } PbrtHipVolumeIntegrator;
 typedef struct PbrtHipSampler { int32_t kind /* RT_SAMPLER_* */, xsamples, ysamples, jitter, pixelsamples; uint32_t seed; } PbrtHipSampler;

@@ -6,6 +6,7 @@
 #include "rt_pipeline.h"
 #include "rt_pipe_vertex.h"
 #include "rt_pipe_march.h"
+#include "rt_bidir.h"
 #include "rt_internal.h"
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +43,7 @@ using namespace rt;
 // (EXT: powf and the second lobe cost ~17 VGPRs, one wave per SIMD less for DirectLighting).  `variant` keeps round 1's numbering:
 // ((VOL*2 + ACCEL)*2 + COUNT)*3 + INTEG | 24 + (VOL*2 + ACCEL)*3 + INTEG | 36 + (VOL*2 + ACCEL)*3 + INTEG.
 namespace rt { extern const RenderKernelFn g_render_kernels_whitted[16], g_render_kernels_direct[16], g_render_kernels_path[16], g_render_kernels_weighted[8]; }
+namespace rt { extern const RenderKernelFn g_render_kernels_bidir[4]; }      // rt_mega_b.hip: k = ACCEL*2 + COUNT
 namespace rt { extern const PipeShadeFn g_pipe_shade_whitted[6], g_pipe_shade_direct[6], g_pipe_shade_path[6]; extern const PipeTraceFn g_pipe_trace[8]; extern const PipeShadeFn g_pipe_vertex[3];
                extern const PipeMarchFn g_pipe_march[6]; }
 static inline RenderKernelFn render_kernel_of(int variant) {
@@ -70,7 +72,8 @@ struct RtScene {
     unsigned grid = 0, n_threads = 0;
     unsigned grids[48] = {0};          // resident grid per render_kernel<COUNT, INTEG> instantiation
     unsigned wgrids[8] = {0};          // ... of the DirectLighting "weighted" family (rt_mega_dw.hip)
-    DimReq *light_dims = nullptr; size_t light_dims_cap = 0;      // DirectLighting "all": the per-light sample requests (make_frame)
+    unsigned bgrids[4] = {0};          // ... of the bidirectional integrator's (rt_mega_b.hip)
+    DimReq *light_dims = nullptr; size_t light_dims_cap = 0;      // DirectLighting "all": the per-light sample requests (make_frame); the bidirectional integrator: its BidirTable
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
     unsigned *wt_recbase = nullptr; size_t wt_recbase_cap = 0;

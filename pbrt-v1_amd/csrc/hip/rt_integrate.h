@@ -473,7 +473,9 @@ RT_DEV V3 scene_transmittance(const DevScene &sc, const DevFrame &fr, Lane &ln, 
 
 // ---- EstimateDirect (core/transport.cpp:123-194), split at its two ray casts ------------------------------
 // BSDF-sampling half; returns with either a MIS ray in flight (ST_MIS_DONE) or ST_ED_DONE.
-template <bool EXT, bool DEFER = false>
+// GEOM_N: EstimateDirect's normal argument is the geometric normal (the bidirectional integrator, bidirectional.cpp:119) instead of bsdf->dgShading.nn;
+// the BSDF keeps its own frame either way
+template <bool EXT, bool DEFER = false, bool GEOM_N = false>
 RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
     LightRef Lt = RT_LIGHT(sc, ln.cur_light);
     ln.stage = ST_ED_DONE;
@@ -483,14 +485,14 @@ RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
     V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, ln.bs1, ln.bs2, ln.bcs, bsdfPdf, BX_ALL & ~BX_SPECULAR, sampled);
     if (!is_black(f) && bsdfPdf > 0.f) {
         float lightPdf;
-        if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(ln.v.nn, wi) : area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+        if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(GEOM_N ? ln.v.ng : ln.v.nn, wi) : area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
         else lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);            // (the other kernels' statement, as it was)
         if (lightPdf > 0.f) {
             float fw = 1 * bsdfPdf, gw = 1 * lightPdf;                            // PowerHeuristic mc.h:55-59
             float weight = (fw * fw) / (fw * fw + gw * gw);
             // Li is Lemit iff the closest hit is this emitter seen from its front side -- the infinite light's L iff the ray hits nothing
             // (light->Le(ray), transport.cpp:184-185); decided after the trace
-            ln.pend = div_s(((f * mat_color(Lt.color)) * absdot3(wi, ln.v.nn)) * weight, bsdfPdf);
+            ln.pend = div_s(((f * mat_color(Lt.color)) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn)) * weight, bsdfPdf);
             launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_MIS_DONE);
         }
     }
@@ -507,7 +509,7 @@ RT_DEV size_t weighted_record(const DevFrame &fr, const Lane &ln, int nLights) {
 }
 
 // light-sampling half
-template <bool EXT, bool DEFER = false>
+template <bool EXT, bool DEFER = false, bool GEOM_N = false>
 RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float ls1, float ls2) {
     ln.cur_light = light;
     ln.Ld = mk3(0.f);
@@ -519,7 +521,7 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
         lightPdf = 1.f;
     } else if constexpr (EXT) {                                                 // (discarded in the other kernels: their code is what it was)
         if (light_is_infinite<EXT>(Lt)) {                                       // infinite.cpp:96-116, n = bsdf->dgShading.nn; SetRay(p, wi)
-            wi = infinite_sample_cosine(ln.v.nn, ls1, ls2, ln.rng, lightPdf);
+            wi = infinite_sample_cosine(GEOM_N ? ln.v.ng : ln.v.nn, ls1, ls2, ln.rng, lightPdf);
             Li = mat_color(Lt.color);
             sd = wi; smax = RT_INF;
         } else {                                                                // area.cpp:58-68
@@ -541,12 +543,12 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
     if (lightPdf > 0.f && !is_black(Li)) {
         V3 f = bsdf_f<EXT>(m, ln.v, ln.v.wo, wi);
         if (!is_black(f)) {
-            if (light_is_delta<EXT>(Lt)) ln.pend = div_s((f * Li) * absdot3(wi, ln.v.nn), lightPdf);
+            if (light_is_delta<EXT>(Lt)) ln.pend = div_s((f * Li) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn), lightPdf);
             else {
                 float bsdfPdf = bsdf_pdf<EXT>(m, ln.v, ln.v.wo, wi);
                 float fw = 1 * lightPdf, gw = 1 * bsdfPdf;
                 float weight = (fw * fw) / (fw * fw + gw * gw);
-                ln.pend = div_s(((f * Li) * absdot3(wi, ln.v.nn)) * weight, lightPdf);
+                ln.pend = div_s(((f * Li) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn)) * weight, lightPdf);
             }
             // VisibilityTester::SetSegment / SetRay light.h:78-83
             launch_ray<DEFER>(ln, sc, ln.v.p, sd, RT_RAY_EPSILON, smax, true, ST_SHADOW_DONE);

@@ -174,6 +174,22 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
     return RT_OK;
 }
 
+// The bidirectional integrator: rt::bidir_kernel (rt_bidir.h), k = ACCEL*2 + COUNT, with the eight path vertices of every thread in s->frames
+static int render_bidir(RtScene *s, DevFrame &fr) {
+    int rc = ensure(s, &s->frames, &s->frames_floats, size_t(RT_BD_FRAME_WORDS) * s->n_threads); if (rc) return rc;
+    fr.frames = s->frames;
+    const int bk = (s->accel_kind == RT_ACCEL_GRID ? 2 : 0) + (s->counting ? 1 : 0);
+    if (s->bgrids[bk] == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
+    HIPCHK(hipEventRecord(s->ev0, s->stream));
+    hipLaunchKernelGGL(g_render_kernels_bidir[bk], dim3(s->bgrids[bk]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev1, s->stream));
+    s->last_pipeline = false; s->last_weighted = false;
+    return RT_OK;
+}
+
 extern "C" {
 
 
@@ -236,6 +252,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
             n2.push_back(ns); n2.push_back(ns); n1.push_back(ns); }
     } else if (rd->integrator == RT_INTEGRATOR_DIRECT) { n2 = {1, 1}; n1 = {1, 1}; }
     else if (rd->integrator == RT_INTEGRATOR_PATH) { n1.assign(9, 1); n2.assign(9, 1); }
+    else if (rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL) { n1.assign(4 * RT_BD_MAX_VERTS + 1, 1); n2.assign(4 * RT_BD_MAX_VERTS + 2, 1); }     // bidirectional.cpp:65-79
     else if (rd->integrator != RT_INTEGRATOR_WHITTED) return fail(RT_EINVAL, "unknown integrator");
     n1.push_back(1); n1.push_back(1);                   // the volume integrator's tau / scatter samples
     // The requests in the reference's order (every 1-D request, then every 2-D one: Sample::Sample sampling.cpp:41-70).  DirectLighting "all" asks for
@@ -271,9 +288,26 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
     fr.light_dims = nullptr;
     fr.dims_max_n = 0;
     for (const DimReq &r : d2) fr.dims_max_n = std::max(fr.dims_max_n, int(r.n));
-    if (all_lights) {
-        std::vector<DimReq> tab(size_t(nl) * 3 + 1, DimReq{0, 0, 0, 0});
-        for (int i = 0; i < nl; ++i) { tab[3 * size_t(i)] = d2[2 * size_t(i)]; tab[3 * size_t(i) + 1] = d2[2 * size_t(i) + 1]; tab[3 * size_t(i) + 2] = d1[size_t(i)]; }
+    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL;
+    if (all_lights || bidir) {
+        std::vector<DimReq> tab;
+        if (all_lights) {
+            tab.assign(size_t(nl) * 3 + 1, DimReq{0, 0, 0, 0});
+            for (int i = 0; i < nl; ++i) { tab[3 * size_t(i)] = d2[2 * size_t(i)]; tab[3 * size_t(i) + 1] = d2[2 * size_t(i) + 1]; tab[3 * size_t(i) + 2] = d1[size_t(i)]; }
+        } else {
+            // the bidirectional integrator: its 17 + 18 requests (more than the descriptor's arrays hold) and the world's bounding sphere, one BidirTable
+            BidirTable bt; std::memset(&bt, 0, sizeof bt);
+            for (int i = 0; i < 4 * RT_BD_MAX_VERTS + 1; ++i) bt.one_d[i] = d1[size_t(i)];
+            for (int i = 0; i < 4 * RT_BD_MAX_VERTS + 2; ++i) bt.two_d[i] = d2[size_t(i)];
+            // Scene::WorldBound() (scene.cpp:114-119; a medium is refused, so it is the accelerator's bound) -> BBox::BoundingSphere (geometry.cpp:47-50)
+            const float *b = s->dev.bounds;
+            const float cx = .5f * b[0] + .5f * b[3], cy = .5f * b[1] + .5f * b[4], cz = .5f * b[2] + .5f * b[5];
+            const bool inside = cx >= b[0] && cx <= b[3] && cy >= b[1] && cy <= b[4] && cz >= b[2] && cz <= b[5];
+            const float dx = cx - b[3], dy = cy - b[4], dz = cz - b[5];
+            bt.wc[0] = cx; bt.wc[1] = cy; bt.wc[2] = cz; bt.wr = inside ? std::sqrt(dx * dx + dy * dy + dz * dz) : 0.f;
+            tab.assign((sizeof bt + sizeof(DimReq) - 1) / sizeof(DimReq), DimReq{0, 0, 0, 0});
+            std::memcpy(tab.data(), &bt, sizeof bt);
+        }
         std::vector<DimReq> &up = s->light_dims_host;          // what the device holds: uploaded again only when a frame asks for other requests
         if (!s->light_dims || up.size() != tab.size() || std::memcmp(up.data(), tab.data(), tab.size() * sizeof(DimReq)) != 0) {
             int rc = ensure(s, &s->light_dims, &s->light_dims_cap, tab.size()); if (rc) return rc;
@@ -284,7 +318,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
             HIPCHK(hipMemcpy(s->light_dims, up.data(), up.size() * sizeof(DimReq), hipMemcpyHostToDevice));
         }
         fr.light_dims = s->light_dims;
-        d1.erase(d1.begin(), d1.begin() + nl);              // what stays in the descriptor: the volume integrator's two 1-D requests
+        d1.erase(d1.begin(), d1.begin() + (all_lights ? nl : 4 * RT_BD_MAX_VERTS + 1));     // what stays in the descriptor: the volume integrator's two 1-D requests
         d2.clear();
     }
     if (d1.size() > RT_MAX_DIM_REQ || d2.size() > RT_MAX_DIM_REQ) return fail(RT_ESTATE, "rt_render: sample table overflow");      // (cannot happen: 11 / 9 for the path integrator)
@@ -339,6 +373,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
         if (fr.dims_max_n >= 65535) fr.pipeline = 0;                     // ... and the light / sample cursors in 16 bits each
         if (s->dev.n_lights >= 65535u) fr.pipeline = 0;
         if (rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED) fr.pipeline = 0;    // three megakernel passes (rt_weighted.h)
+        if (bidir) { fr.pipeline = 0; fr.xcd_bands = 0; }   // rt::bidir_kernel (rt_bidir.h): a persistent kernel of its own, one work counter
         if (fr.shard_count == 1 && !fr.pipeline) {
             // One shard: the tiles partition nothing, and the megakernel then renders the sample extent in scanline order.  2-D tiles pad the extent to
             // whole tiles and every dropped padding item idles a lane for about a ray's time: 64 x 64 tiles cost C3 5 % of its frame
@@ -419,8 +454,14 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (!s || !rd) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
     // ---- validation first: a failing call launches nothing and leaves the film and the sample buffer untouched
-    if (rd->integrator < RT_INTEGRATOR_WHITTED || rd->integrator > RT_INTEGRATOR_PATH) return fail(RT_EINVAL, "unknown integrator");
-    if (rd->max_depth < 0) return fail(RT_EINVAL, "rt_render: negative maxdepth");
+    if (rd->integrator < RT_INTEGRATOR_WHITTED || rd->integrator > RT_INTEGRATOR_BIDIRECTIONAL) return fail(RT_EINVAL, "unknown integrator");
+    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL;
+    if (rd->max_depth < 0 && !bidir) return fail(RT_EINVAL, "rt_render: negative maxdepth");
+    if (bidir) {                                              // BidirIntegrator (bidirectional.cpp): rt_bidir.h
+        // the reference's connections ignore the medium's transmittance while EstimateDirect applies it: left for a later change
+        if (s->volume.present) return fail(RT_EINVAL, "rt_render: the bidirectional integrator in a participating medium is not supported");
+        if (s->dev.n_lights == 0) return fail(RT_EINVAL, "rt_render: the bidirectional integrator needs at least one light (the reference indexes lights[-1] in a scene with no lights)");
+    }
     if (!rd->filter_table) return fail(RT_EINVAL, "rt_render: no filter table");
     DevFrame fr; int rc = make_frame(s, rd, fr, true); if (rc) return rc;
     const bool weighted = rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED;
@@ -504,6 +545,8 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (fr.pipeline) {
         rc = render_pipeline(s, rd, fr, vol_levels, vol_nmax, vol_samp_words); if (rc) return rc;
         s->last_weighted = false;
+    } else if (bidir) {                                       // a kernel family of its own, ahead of the variant arithmetic of the three megakernel integrators
+        rc = render_bidir(s, fr); if (rc) return rc;
     } else {
         if (rd->integrator != RT_INTEGRATOR_PATH) {           // recursion frames for whitted / directlighting
             rc = ensure(s, &s->frames, &s->frames_floats, size_t(rd->max_depth + 2) * RT_FRAME_WORDS * s->n_threads); if (rc) return rc;

@@ -560,6 +560,12 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
             s->wgrids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
             mx = s->wgrids[k] > mx ? s->wgrids[k] : mx;
         }
+        for (int k = 0; k < 4; ++k) {
+            int per_cu = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)g_render_kernels_bidir[k], RT_BLOCK, 0));
+            s->bgrids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
+            mx = s->bgrids[k] > mx ? s->bgrids[k] : mx;
+        }
         s->grid = mx;
     }
     s->n_threads = s->grid * RT_BLOCK;

@@ -617,6 +617,10 @@ RT_DEV V3 quadric_sample(const DevScene &sc, unsigned qi, bool ro, V3 p, float u
     if (ro) ns = ns * -1.f;
     return ps;
 }
+RT_DEV float quadric_area(const DevQuadric RT_G &q) {                           // Disk::Area disk.cpp:124-127, Cylinder::Area cylinder.cpp:180-182, Sphere::Area sphere.cpp:251-253
+    return q.type == RT_QUADRIC_DISK ? q.phi_max * 0.5f * (q.radius * q.radius - q.zmax * q.zmax)
+                                     : (q.type == RT_QUADRIC_CYLINDER ? (q.zmax - q.zmin) * q.phi_max * q.radius : q.phi_max * q.radius * (q.zmax - q.zmin));
+}
 RT_DEV float quadric_light_pdf(const DevScene &sc, unsigned qi, V3 p, V3 wi) {   // Shape::Pdf(p, wi) shape.h:96-107; Sphere::Pdf sphere.cpp:73-86
     const DevQuadric RT_G &q = RT_GPTR(const DevQuadric, sc.quadrics)[qi];
     if (q.type == RT_QUADRIC_SPHERE) {
@@ -629,8 +633,7 @@ RT_DEV float quadric_light_pdf(const DevScene &sc, unsigned qi, V3 p, V3 wi) {  
     float thit;
     if (!quadric_test(sc, qi, p, wi, RT_RAY_EPSILON, RT_INF, thit)) return 0.f;
     V3 hp, nn, sn; quadric_frame(sc, qi, false, p, wi, thit, hp, nn, sn);
-    const float area = q.type == RT_QUADRIC_DISK ? q.phi_max * 0.5f * (q.radius * q.radius - q.zmax * q.zmax)
-                     : (q.type == RT_QUADRIC_CYLINDER ? (q.zmax - q.zmin) * q.phi_max * q.radius : q.phi_max * q.radius * (q.zmax - q.zmin));
+    const float area = quadric_area(q);
     float pdf = dist_sq(p, p + wi * thit) / (absdot3(nn, -wi) * area);
     if (absdot3(nn, -wi) == 0.f) pdf = 0.f;
     return pdf;
@@ -681,6 +684,69 @@ RT_DEV V3 area_sample_point(const DevScene &sc, LightRef L, V3 pref, float u1, f
     ns = normalize3(cross3(p2 - p1, p3 - p1));
     if (L.reverse_orientation) ns = ns * -1.f;
     return ps;
+}
+
+// ---- emission sampling: Light::Sample_L(scene, u1, u2, u3, u4, &ray, &pdf), the ray a light path starts with (EXT kernels only).  Only the ray and its
+// pdf are produced: the one caller, the bidirectional integrator, overwrites the returned spectrum (bidirectional.cpp:107-110).
+// `wc`, `wr`: Scene::WorldBound().BoundingSphere (scene.cpp:114-119, geometry.cpp:47-50), evaluated once on the host.
+// UniformSampleCone(u1, u2, costhetamax) mc.cpp:145-153
+RT_DEV V3 uniform_sample_cone(float u1, float u2, float costhetamax) {
+    const float costheta = (1.f - u1) * costhetamax + u1 * 1.f;                     // Lerp
+    const float sintheta = sqrtf(1.f - costheta * costheta);
+    const float phi = u2 * 2.f * RT_PI;
+    return mk3(cosf(phi) * sintheta, sinf(phi) * sintheta, costheta);
+}
+// the 3x3 of LightToWorld from the WorldToLight the light record carries (its inverse by cofactors; the reference keeps both matrices, light.h:39-40, :74)
+RT_DEV V3 light_to_world(LightRef Lt, V3 v) {
+    const float a = Lt.w2l[0], b = Lt.w2l[1], c = Lt.w2l[2], d = Lt.w2l[3], e = Lt.w2l[4], f = Lt.w2l[5], g = Lt.w2l[6], h = Lt.w2l[7], i = Lt.w2l[8];
+    const float A = e * i - f * h, B = c * h - b * i, C = b * f - c * e;
+    const float D = f * g - d * i, E = a * i - c * g, F = c * d - a * f;
+    const float G = d * h - e * g, H = b * g - a * h, I = a * e - b * d;
+    const float inv = 1.f / (a * A + b * D + c * G);
+    return mk3((A * v.x + B * v.y + C * v.z) * inv, (D * v.x + E * v.y + F * v.z) * inv, (G * v.x + H * v.y + I * v.z) * inv);
+}
+template <bool EXT, class RNG>
+RT_DEV void light_sample_emission(const DevScene &sc, LightRef Lt, V3 wc, float wr, float u1, float u2, float u3, float u4, RNG &rng, V3 &o, V3 &d, float &pdf) {
+    if (Lt.type == RT_LIGHT_POINT) {                                            // point.cpp:70-77
+        o = mat_color(Lt.pos);
+        d = infinite_sample_sphere(u1, u2, pdf);                                // UniformSampleSphere, UniformSpherePdf
+    } else if (Lt.type == RT_LIGHT_SPOT) {                                      // spot.cpp:87-95
+        o = mat_color(Lt.pos);
+        d = light_to_world(Lt, uniform_sample_cone(u1, u2, Lt.cos_total));
+        pdf = 1.f / (2.f * RT_PI * (1.f - Lt.cos_total));                       // UniformConePdf mc.cpp:142-144
+    } else if (Lt.type == RT_LIGHT_DISTANT) {                                   // distant.cpp:74-93
+        const V3 lightDir = mat_color(Lt.dir);
+        V3 v1, v2; coordinate_system(lightDir, v1, v2);
+        float d1, d2; concentric_disk(u1, u2, d1, d2);
+        const V3 Pdisk = wc + wr * (d1 * v1 + d2 * v2);
+        o = Pdisk + wr * lightDir;
+        d = -lightDir;
+        pdf = 1.f / (RT_PI * wr * wr);
+    } else if (Lt.type == RT_LIGHT_INFINITE) {                                  // infinite.cpp:132-154
+        const float worldRadius = wr * 1.01f;
+        float unused;
+        const V3 p1 = wc + worldRadius * infinite_sample_sphere(u1, u2, unused);
+        const V3 p2 = wc + worldRadius * infinite_sample_sphere(u3, u4, unused);
+        o = p1;
+        d = normalize3(p2 - p1);
+        const V3 to_center = normalize3(wc - p1);
+        const float costheta = absdot3(to_center, d);
+        pdf = costheta / ((4.f * RT_PI * worldRadius * worldRadius));
+    } else {                                                                    // area.cpp:83-92; Shape::Pdf(Pshape) = 1 / Area() shape.h:89-91
+        V3 ns; float area;
+        if (EXT && Lt.quadric >= 0) {
+            const DevQuadric RT_G &q = RT_GPTR(const DevQuadric, sc.quadrics)[unsigned(Lt.quadric)];
+            o = quadric_sample_uniform(q, Lt.reverse_orientation != 0, u1, u2, ns);
+            area = quadric_area(q);
+        } else {
+            o = area_sample_point<EXT>(sc, Lt, mk3(0.f), u1, u2, rng, ns);      // ShapeSet::Sample's RandomFloat() for an emitter of several triangles
+            area = Lt.area;
+        }
+        float unused;
+        d = infinite_sample_sphere(u3, u4, unused);
+        if (dot3(d, ns) < 0.f) d = d * -1.f;
+        pdf = (1.f / area) * RT_INV_TWOPI;
+    }
 }
 
 }  // namespace rt

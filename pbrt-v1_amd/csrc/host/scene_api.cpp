@@ -226,9 +226,14 @@ SurfaceIntegrator MakeSurfaceIntegrator(const std::string &name, const ParamSet 
     if (void *sym = findPluginSymbol(name, "PbrtHipCreateSurfaceIntegrator")) {            // dynload.cpp:185-199 MakeSurfaceIntegrator
         CParams c{&ps}; PbrtHipSurfaceIntegrator o{};
         if (reinterpret_cast<PbrtHipCreateSurfaceIntegratorFn>(sym)(reinterpret_cast<const PbrtHipParams *>(&c), &kParamsApi, &o) != 0 ||
-            o.kind < RT_INTEGRATOR_WHITTED || o.kind > RT_INTEGRATOR_PATH || (o.strategy < RT_STRATEGY_ALL || o.strategy > RT_STRATEGY_WEIGHTED)) {
+            o.kind < RT_INTEGRATOR_WHITTED || o.kind > RT_INTEGRATOR_BIDIRECTIONAL || (o.strategy < RT_STRATEGY_ALL || o.strategy > RT_STRATEGY_WEIGHTED)) {
             Error("Unable to load plugin \"%s\" (surface integrator)", name.c_str()); *ok = false; si.kind = RT_INTEGRATOR_WHITTED; si.maxDepth = 5;
         } else { si.kind = o.kind; si.maxDepth = o.max_depth; si.strategy = o.strategy; }
+        ps.ReportUnused();
+        return si;
+    }
+    if (name == "bidirectional") {                           // bidirectional.cpp:211-213: the factory reads no parameter, so every one given is reported unused
+        si.kind = RT_INTEGRATOR_BIDIRECTIONAL; si.maxDepth = 5;
         ps.ReportUnused();
         return si;
     }
