@@ -282,6 +282,21 @@ int rt_scene_create_prebuilt(const RtSceneDesc *desc, int device, const RtPrebui
  * nx*ny*nz >= 2^31, null grid), RT_ESTATE (called twice, or after rt_render), RT_EDEVICE (upload failed);
  * rt_last_error() says which. */
 int rt_scene_set_density(RtScene *s, const RtDensityRegion *region);
+/* Textured material parameters (include/pbrt_hip_texture.h has the records, the limits and the evaluation): what MakeMaterial keeps when
+ * TextureParams::GetSpectrumTexture / GetFloatTexture (core/paramset.cpp:434-465) return something other than a ConstantTexture.  Call once,
+ * after rt_scene_create or rt_scene_create_prebuilt and before the first rt_render.  `nodes` is a flat table of n_nodes texture nodes whose
+ * children precede them; `mats` has one record per material of the scene (n_mats == RtSceneDesc.n_materials): the raw parameters and, per
+ * parameter slot, the node that supplies it at every hit or -1.  A material with a textured slot is resolved per hit on the device (the
+ * clamps, Oren-Nayar's A and B, the Blinn exponent, the conductor etas, the products and the lobes present), from `mats[i].raw` with the
+ * textured slots replaced; a material without one keeps what rt_scene_create made of RtSceneDesc.materials[i].  Frames of such a scene run
+ * the EXT kernels.  Both tables are copied.
+ * Returns RT_EINVAL (null argument, n_nodes == 0 or above RT_TEX_MAX_NODES, n_mats != the scene's materials, an unknown kind or mapping, a
+ * child index that is not below its node -- which is how a cycle shows --, a missing child, a child or a slot of the wrong value type, a
+ * material type that differs from the scene's, a parameter graph of more than RT_TEX_MAX_PROGRAM nodes or one that needs more than
+ * RT_TEX_MAX_STACK values at once, more than 65534 materials), RT_ESTATE (called twice, or after rt_render), RT_EDEVICE (upload failed);
+ * rt_last_error() says which.  Nothing is launched. */
+struct RtTexture; struct RtMaterialTextures;
+int rt_scene_set_textures(RtScene *s, const struct RtTexture *nodes, uint32_t n_nodes, const struct RtMaterialTextures *mats, uint32_t n_mats);
 int rt_scene_destroy(RtScene *s);
 int rt_scene_set_stream(RtScene *s, void *hip_stream);
 int rt_scene_accel_info(const RtScene *s, RtAccelInfo *info);

@@ -6,6 +6,11 @@
 #define PBRT_HIP_MATERIAL_H
 #include <math.h>
 #include "pbrt_hip.h"
+#if defined(__HIPCC__)
+#define RT_MAT_FN __host__ __device__ static inline    /* the EXT kernels derive the same values per hit for a textured material */
+#else
+#define RT_MAT_FN static inline
+#endif
 
 typedef struct RtMaterialLobes {
     float eta_ks[3], eta_kr[3];                 /* shinymetal: FresnelApproxEta(Ks), FresnelApproxEta(Kr) (shinymetal.cpp:57-58) */
@@ -14,13 +19,13 @@ typedef struct RtMaterialLobes {
 } RtMaterialLobes;
 
 /* FresnelApproxEta core/reflection.cpp:52-56: Clamp(0, .999), (1 + sqrt) / (1 - sqrt) */
-static inline float rt_fresnel_approx_eta(float fr) {
+RT_MAT_FN float rt_fresnel_approx_eta(float fr) {
     const float reflectance = fr < 0.f ? 0.f : (fr > .999f ? .999f : fr);
     return (1.f + sqrtf(reflectance)) / (1.f - sqrtf(reflectance));
 }
-static inline int rt_color_black(const float *c) { return c[0] == 0.f && c[1] == 0.f && c[2] == 0.f; }   /* Spectrum::Black color.h */
+RT_MAT_FN int rt_color_black(const float *c) { return c[0] == 0.f && c[1] == 0.f && c[2] == 0.f; }   /* Spectrum::Black color.h */
 
-static inline void rt_material_lobes(const RtMaterial *m, RtMaterialLobes *o) {
+RT_MAT_FN void rt_material_lobes(const RtMaterial *m, RtMaterialLobes *o) {
     int c;
     for (c = 0; c < 3; ++c) { o->eta_ks[c] = o->eta_kr[c] = 0.f; o->r_kd[c] = o->t_kd[c] = o->r_ks[c] = o->t_ks[c] = 0.f; }
     o->has_dr = o->has_dt = o->has_gr = o->has_gt = 0;

@@ -50,7 +50,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | No
     headers = [d for d in hip_dep if d.endswith((".h", ".inc"))]
     host_src = [os.path.join(CSRC, "host", "scene_api.cpp")]
     host_dep = [os.path.join(CSRC, "host", f) for f in os.listdir(os.path.join(CSRC, "host"))] + \
-               [os.path.join(_HERE, "..", "include", f) for f in ("pbrt_hip.h", "pbrt_hip_desc.h", "pbrt_hip_plugin.h", "pbrt_hip_material.h")]
+               [os.path.join(_HERE, "..", "include", f) for f in ("pbrt_hip.h", "pbrt_hip_desc.h", "pbrt_hip_plugin.h", "pbrt_hip_material.h", "pbrt_hip_texture.h")]
 
     def stale(out, deps):
         return force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
@@ -164,6 +164,32 @@ class RtMaterialLobes(C.Structure):                # include/pbrt_hip_material.h
                [(n, C.c_int32) for n in ("has_dr", "has_dt", "has_gr", "has_gt")]
 
 
+class RtMaterialParams(C.Structure):               # include/pbrt_hip_texture.h: a material's raw parameters by slot
+    _fields_ = [("type", C.c_int32), ("c", (C.c_float * 3) * 4), ("f", C.c_float)]
+
+
+class RtMaterialTextures(C.Structure):             # ... and per slot the texture node that replaces it at every hit, or -1
+    _fields_ = [("raw", RtMaterialParams), ("tex", C.c_int32 * 5)]
+
+
+class RtMaterialResolved(C.Structure):             # ... and what the kernels read (84 bytes)
+    _fields_ = [("type", C.c_int32), ("r", C.c_float * 3), ("t", C.c_float * 3), ("on_a", C.c_float), ("on_b", C.c_float), ("ior", C.c_float),
+                ("has_r", C.c_int32), ("has_t", C.c_int32), ("ks", C.c_float * 3), ("exponent", C.c_float), ("kr", C.c_float * 3),
+                ("has_g", C.c_int32), ("has_kr", C.c_int32)]
+
+
+class RtTexture(C.Structure):                      # include/pbrt_hip_texture.h: one node of the texture table (168 bytes)
+    _fields_ = [("kind", C.c_int32), ("is_color", C.c_int32), ("mapping", C.c_int32), ("child", C.c_int32 * 3), ("value", C.c_float * 12),
+                ("map", C.c_float * 8), ("world_to_texture", C.c_float * 16)]
+
+
+RT_TEXTURE_NAMES = ("constant", "scale", "mix", "bilerp", "uv", "checkerboard")
+RT_TEXMAP_NAMES = ("uv", "spherical", "cylindrical", "planar")
+# the parameter behind each slot of RtMaterialParams (c[0] .. c[3], f), by material
+RT_MATERIAL_SLOTS = {"matte": ("Kd", None, None, None, "sigma"), "mirror": ("Kr", None, None, None, None), "glass": ("Kr", "Kt", None, None, "index"),
+                     "plastic": ("Kd", "Ks", None, None, "roughness"), "uber": ("Kd", "Ks", "Kr", "opacity", "roughness"),
+                     "shinymetal": (None, "Ks", "Kr", None, "roughness"), "translucent": ("Kd", "Ks", "reflect", "transmit", "roughness")}
+
 RT_DENSITY_NAMES = {1: "exponential", 2: "volumegrid"}
 
 RT_LIGHT_NAMES = ("point", "area", "spot", "distant", "infinite")
@@ -220,10 +246,11 @@ def hip_lib():
                      "rt_counters_reset", "rt_last_render_ms", "rt_last_render_stats", "rt_samples_read", "rt_device_count", "rt_set_counting",
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
-                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density"):
+                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_scene_set_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rt_scene_create_prebuilt.argtypes = [C.c_void_p, C.c_int, C.POINTER(RtPrebuiltAccel), C.POINTER(C.c_void_p)]
         L.rt_scene_destroy.argtypes = [C.c_void_p]
         L.rt_scene_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -305,6 +332,14 @@ def host_lib():
         L.pbrt_host_materials.restype = C.POINTER(RtMaterial)
         L.pbrt_host_materials.argtypes = [C.c_void_p]
         L.pbrt_host_material_lobes.argtypes = [C.POINTER(RtMaterial), C.POINTER(RtMaterialLobes)]
+        L.pbrt_host_textures.restype = C.c_int
+        L.pbrt_host_textures.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(RtTexture)), C.POINTER(C.c_uint), C.POINTER(C.POINTER(RtMaterialTextures)), C.POINTER(C.c_uint)]
+        L.pbrt_host_texture_name.restype = C.c_char_p
+        L.pbrt_host_texture_name.argtypes = [C.c_void_p, C.c_int, C.c_uint]
+        L.pbrt_host_texture_eval.restype = C.c_int
+        L.pbrt_host_texture_eval.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
+        L.pbrt_host_material_resolve.restype = None
+        L.pbrt_host_material_resolve.argtypes = [C.POINTER(RtMaterialParams), C.POINTER(RtMaterial), C.POINTER(RtMaterialResolved)]
         L.pbrt_host_lights.restype = C.POINTER(RtLight)
         L.pbrt_host_lights.argtypes = [C.c_void_p]
         _host = L
@@ -607,7 +642,76 @@ class ParsedScene:
                     d["lobes"] = [n for n, on in (("diffuse_reflection", lb.has_dr), ("diffuse_transmission", lb.has_dt),
                                                   ("glossy_reflection", lb.has_gr), ("glossy_transmission", lb.has_gt)) if on]
             out.append(d)
+        if self.has_textures():                   # slots a texture supplies at every hit: parameter name -> index into textures(); their values above are the literals / defaults
+            _, _, mats, _ = self.texture_table()
+            for i, d in enumerate(out):
+                d["textured"] = {pn: int(mats[i].tex[k]) for k, pn in enumerate(RT_MATERIAL_SLOTS[d["type"]]) if pn is not None and mats[i].tex[k] >= 0}
         return out
+
+    def texture_table(self):
+        """(nodes, n_nodes, mats, n_mats): the frame's RtTexture / RtMaterialTextures arrays as rt_scene_set_textures takes them (owned by this object)."""
+        if getattr(self, "_tex_table", None) is None:
+            nodes = C.POINTER(RtTexture)(); mats = C.POINTER(RtMaterialTextures)(); nn = C.c_uint(); nm = C.c_uint()
+            used = host_lib().pbrt_host_textures(self._h, self.frame, C.byref(nodes), C.byref(nn), C.byref(mats), C.byref(nm))
+            self._tex_table = (nodes, int(nn.value), mats, int(nm.value), bool(used))
+        return self._tex_table[:4]
+
+    def has_textures(self) -> bool:
+        """Does some material have a parameter that a non-constant texture supplies?  Only then is the texture table handed to the device."""
+        self.texture_table()
+        return self._tex_table[4]
+
+    def textures(self) -> list:
+        """The parsed texture table (children before parents) as dictionaries: `name` (of its Texture statement; "" for a literal sub-texture),
+        `class`, `type` ("float" / "color") and per class `value` | `tex1`, `tex2`, `amount` (node indices) | `v00` .. `v11` | `mapping` with
+        its parameters (`uscale`, `vscale`, `udelta`, `vdelta` | `v1`, `v2`, `udelta`, `vdelta` | `world_to_texture`).  Constant textures a
+        Texture statement names are folded into the parameters that use them and do not appear."""
+        if getattr(self, "_tex_list", None) is not None:
+            return self._tex_list
+        nodes, n, _, _ = self.texture_table()
+        f = lambda a: np.array(list(a), np.float32)
+        out = []
+        for i in range(n):
+            t = nodes[i]
+            cls = RT_TEXTURE_NAMES[t.kind]
+            col = bool(t.is_color)
+            val = lambda k: f(t.value[3 * k:3 * k + 3]) if col else float(t.value[3 * k])
+            d = {"name": host_lib().pbrt_host_texture_name(self._h, self.frame, i).decode(), "class": cls, "type": "color" if col else "float"}
+            if cls == "constant":
+                d["value"] = val(0)
+            if cls in ("scale", "mix", "checkerboard"):
+                d.update(tex1=int(t.child[0]), tex2=int(t.child[1]))
+            if cls == "mix":
+                d["amount"] = int(t.child[2])
+            if cls == "bilerp":
+                d.update(v00=val(0), v01=val(1), v10=val(2), v11=val(3))
+            if cls in ("bilerp", "uv", "checkerboard"):
+                mp = RT_TEXMAP_NAMES[t.mapping]
+                d["mapping"] = mp
+                if mp == "uv":
+                    d.update(uscale=float(t.map[0]), vscale=float(t.map[1]), udelta=float(t.map[2]), vdelta=float(t.map[3]))
+                elif mp == "planar":
+                    d.update(v1=f(t.map[0:3]), v2=f(t.map[3:6]), udelta=float(t.map[6]), vdelta=float(t.map[7]))
+                else:
+                    d["world_to_texture"] = f(t.world_to_texture).reshape(4, 4)
+            out.append(d)
+        self._tex_list = out                      # (the parsed table does not change: built once)
+        return out
+
+    def eval_texture(self, which, p, u: float, v: float):
+        """Host evaluation of a texture (index into textures(), or the name of a Texture statement: the last node of that name) at the world
+        point `p` with the surface parameters (u, v) -- the function the device runs (include/pbrt_hip_texture.h), compiled for the host.
+        Returns a float for a float texture, a float32 array of 3 for a colour texture."""
+        tab = self.textures()
+        if isinstance(which, str):
+            idx = [i for i, t in enumerate(tab) if t["name"] == which]
+            if not idx:
+                raise KeyError("no texture named %r" % which)
+            which = idx[-1]
+        pp = (C.c_float * 3)(*[float(x) for x in p]); out = (C.c_float * 3)()
+        if host_lib().pbrt_host_texture_eval(self._h, self.frame, int(which), pp, float(u), float(v), out) != 0:
+            raise RtError("texture %r cannot be evaluated (bad index, or a graph beyond RT_TEX_MAX_PROGRAM / RT_TEX_MAX_STACK)" % (which,))
+        return np.array(list(out), np.float32) if tab[which]["type"] == "color" else float(np.float32(out[0]))
 
     def lights(self) -> list:
         """The parsed light table (RtLight, include/pbrt_hip.h) in scene order as dictionaries: `type` (the light's name), `nsamples` and its
@@ -691,6 +795,13 @@ class DeviceScene:
                 err = hip_lib().rt_last_error().decode(errors="replace")
                 hip_lib().rt_scene_destroy(self._s); self._s = C.c_void_p()
                 raise RtError("rt_scene_set_density failed (%d): %s" % (rc, err))
+        if parsed.has_textures():                 # textured material parameters: the node table and the per-material slots
+            nodes, n_nodes, mats, n_mats = parsed.texture_table()
+            rc = hip_lib().rt_scene_set_textures(self._s, nodes, n_nodes, mats, n_mats)
+            if rc != 0:
+                err = hip_lib().rt_last_error().decode(errors="replace")
+                hip_lib().rt_scene_destroy(self._s); self._s = C.c_void_p()
+                raise RtError("rt_scene_set_textures failed (%d): %s" % (rc, err))
         self._film_bound = False
 
     def accel_info(self) -> RtAccelInfo:

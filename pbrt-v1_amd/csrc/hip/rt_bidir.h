@@ -81,7 +81,9 @@ RT_DEV int bd_generate_path(const DevScene &sc, const DevFrame &fr, const BidirT
             if (ln.tv.hit_prim < 0) alive = false;
             else {
                 BidirVertex b;
+                const int resolved = resolve_hit_material(sc, fr, ln.tv, side * RT_BD_MAX_VERTS + k, gtid);   // a textured material: one resolved record per path vertex (rt_texture.h)
                 make_vertex<true>(sc, ln.tv, b.v);                              // v.p, v.ng = dg.nn, the BSDF's shading frame, v.wi = -ray.d
+                if (resolved >= 0) b.v.mat = resolved;
                 b.wnext = mk3(0.f); b.bsdfWeight = 0.f; b.rrWeight = 1.f;
                 ++nVerts;
                 if (nVerts > 2) {                                               // :151-156

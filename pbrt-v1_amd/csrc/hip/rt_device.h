@@ -2,6 +2,7 @@
 #pragma once
 #include "rt_math.h"
 #include "../../../include/pbrt_hip.h"
+#include "../../../include/pbrt_hip_texture.h"
 
 namespace rt {
 
@@ -20,6 +21,7 @@ struct DevQuadric {          // Sphere (shapes/sphere.cpp:89-99): transforms as 
 
 // per-vertex shading data of one triangle (RtTriShading) plus what Triangle::Intersect derives from its uvs (trianglemesh.cpp:248-268)
 #define RT_PRIM_SHADING (1u << 18)      // tri_shade bits: the triangle has per-vertex N and / or S (DevScene::tri_shading)
+#define RT_PRIM_TEXTURED (1u << 19)     // tri_shade bits: the primitive's material has a textured parameter (set by rt_scene_set_textures; rt_texture.h)
 struct DevTriShading {
     unsigned flags, xform;
     float uv[6];
@@ -28,21 +30,12 @@ struct DevTriShading {
     float pad[3];
 };
 
-struct DevMaterial {
-    int type;
-    float r[3];      // Kd / Kr
-    float t[3];      // Kt
-    float on_a, on_b;  // Oren-Nayar A,B (reflection.h:268-277); on_b < 0 => Lambertian
-    float ior;
-    int has_r, has_t;  // glass.cpp:56-61: a lobe exists only if its colour is not black
-    float ks[3];       // plastic: Microfacet reflectance
-    float exponent;    // plastic / uber: Blinn exponent = 1/roughness, capped at 1000 (reflection.h:313)
-    float kr[3];       // uber: SpecularReflection reflectance (Fresnel 1.5 / 1)
-    int has_g, has_kr; // uber: glossy / specular-reflection lobes present (non-black, uber.cpp:71-86)
-    // shinymetal (shinymetal.cpp:52-61): ks = FresnelApproxEta(Ks), kr = FresnelApproxEta(Kr) (the two FresnelConductor etas, k = 0), exponent
-    // translucent (translucent.cpp:53-80): r = reflect*Kd, t = transmit*Kd, ks = reflect*Ks, kr = transmit*Ks, exponent; the lobes
-    //   present are has_r (diffuse R), has_t (diffuse T), has_g (glossy R), has_kr (glossy T).  Same 84 bytes: no read got wider.
-};
+// The material record the kernels read is what rt_material_resolve() derives (include/pbrt_hip_texture.h: one definition for rt_scene_create, which
+// resolves a material without a textured parameter once, and for the EXT kernels, which resolve a textured one at every hit -- rt_texture.h).  84 bytes.
+typedef RtMaterialResolved DevMaterial;
+// a material of a scene with textures (rt_scene_set_textures): its raw parameters and, per parameter slot, the post-order program (node indices in
+// DevScene::tex_prog) that replaces it at a hit; len 0 = the slot keeps its raw value
+struct DevMatTex { RtMaterialParams raw; int textured; int prog_off[RT_MATSLOT_COUNT], prog_len[RT_MATSLOT_COUNT]; };
 
 struct DevLight {
     int type;
@@ -105,6 +98,14 @@ struct DevScene {
     int dens_n[3];                         // VolumeGrid (volumegrid.cpp:27-84): nx, ny, nz and density[z*nx*ny + y*nx + x]
     const float *dens_grid;
     int n_infinite;                        // RT_LIGHT_INFINITE lights in `lights` (read only by the EXT kernels; last, so that no other field moved)
+    // textured material parameters (rt_scene_set_textures; read only by the EXT kernels, appended for the same reason): n_textured = materials with a
+    // textured slot, 0 in every other scene.  `materials` then has room behind the scene's own records for the ones resolved per hit (DevFrame::mat_pool_base)
+    int n_textured;
+    const RtTexture *tex_nodes;
+    const int *tex_prog;
+    const DevMatTex *mat_tex;              // [n_materials]
+    const int *tex_uv_idx;                 // [n_tris] index into tex_uv or -1 (GetUVs' defaults); null when no mesh has "uv".  Uploaded by rt_scene_set_textures only
+    const float *tex_uv;                   // [n][6] uvs[3][2] of a triangle
 };
 
 #define RT_INTEG_DIRECT_WEIGHTED 3    // device-side template value only: DirectLighting with strategy "weighted" (render_kernel family g_render_kernels_weighted)
@@ -162,6 +163,8 @@ struct DevFrame {
     int wt_mixed;
     unsigned wt_nd;                 // number of drawing lights
     const unsigned *wt_recbase;     // [total_work + 1], float offsets into wt_rec
+    unsigned mat_pool_base;         // scenes with textures: materials[mat_pool_base + level * n_threads + thread] holds the material resolved at the vertex a thread (or
+                                    // pipeline slot) keeps at recursion level `level` (bidirectional: path vertex `level`); Vertex::mat of such a vertex is that index
     int dens_cap;                   // density region: no DensityRegion::Tau march takes more samples (rt_render bounds it by the volume's world diagonal)
 #ifdef RT_TAIL_PROBE
     unsigned long long *probe;      // -DRT_TAIL_PROBE builds (tools/build_variant.py): per megakernel wave {start, work list found empty, end} in 10 ns ticks + samples taken

@@ -95,6 +95,12 @@ struct RtScene {
     int density_kind = RT_DENSITY_NONE;                    // rt_scene_set_density
     double vol_world[6] = {0, 0, 0, 0, 0, 0};             // density region: the volume's world bound (WorldToVolume^-1 of its extent)
     bool rendered = false;                                 // an rt_render has been accepted
+    // textured materials (rt_scene_set_textures): the scene's own resolved records (host copy) and the device array that holds them followed by
+    // mat_pool_cap records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
+    std::vector<DevMaterial> materials_host;
+    std::vector<int> tex_uv_idx_host; std::vector<float> tex_uv_host;   // uvs of the triangles whose mesh has "uv" ([n_tris] index or -1, 6 floats each): host only until rt_scene_set_textures
+    bool has_textures = false;
+    DevMaterial *mat_buf = nullptr; size_t mat_pool_cap = 0;
     int spill_depth = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_timing = false;
@@ -126,6 +132,9 @@ static inline int upload(RtScene *s, const T *host, size_t n, const T **dev) {
     *dev = static_cast<const T *>(p);
     return RT_OK;
 }
+
+// scenes with textures: room for `levels` resolved materials per thread / slot behind the scene's own (fr.mat_pool_base, fr.n_threads); rt_scene.hip
+int ensure_material_pool(RtScene *s, rt::DevFrame &fr, size_t levels, size_t n_slots);
 
 // (re)allocate a scratch buffer that is only ever used inside one rt_render call
 template <class T>

@@ -13,6 +13,7 @@
 // reference consumes draws per sample is reproduced exactly.
 #pragma once
 #include "rt_shade.h"
+#include "rt_texture.h"
 
 namespace rt {
 
@@ -697,7 +698,10 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 else if (EXT && ln.specular) ln.L = infinite_le_sum(sc, ln.L, ln.thr, true);
                 ln.stage = ST_RETURN; return;
             }
+            int resolved = -1;
+            if constexpr (EXT) resolved = resolve_hit_material(sc, fr, ln.tv, 0, gtid);     // a textured material: resolved at this hit (rt_texture.h); a path keeps one vertex
             make_vertex<EXT>(sc, ln.tv, ln.v);
+            if (EXT && resolved >= 0) ln.v.mat = resolved;
 #ifdef RT_DEBUG_PIXEL
             if (int(floorf(ln.image_x)) == fr.dbg_x && int(floorf(ln.image_y)) == fr.dbg_y)
                 printf("DEV depth %d prim %d t %.9g o %.9g %.9g %.9g d %.9g %.9g %.9g p %.9g %.9g %.9g nn %.9g %.9g %.9g sn %.9g %.9g %.9g\n", ln.depth, ln.tv.hit_prim, ln.tv.maxt,
@@ -717,7 +721,10 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 }
                 ln.stage = ST_RETURN; return;
             }
+            int resolved = -1;
+            if constexpr (EXT) resolved = resolve_hit_material(sc, fr, ln.tv, ln.fsp, gtid);   // ... one per level of the specular recursion
             make_vertex<EXT>(sc, ln.tv, ln.v);
+            if (EXT && resolved >= 0) ln.v.mat = resolved;
             if (ln.depth == 0) ln.alpha = 1.f;
             if (VOL) vol_ray_ptr(fr, ln.fsp, gtid)[7 * size_t(fr.n_threads)] = ln.tv.maxt;       // the hit shortens this level's ray
             ln.L = mk3(0.f);

@@ -58,7 +58,8 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
     // ---- pool size: 32 M slots with a medium, 8 M without, unless the frame is smaller or the per-slot scratch would not fit (a fine ray march: 3 floats per step)
     const size_t frame_words = integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) * RT_FRAME_WORDS : 0;
     const size_t vol_words = s->volume.present ? size_t(vol_levels) * 8 + 13 + vol_samp_words : 0;
-    const size_t slot_bytes = size_t(RT_PIPE_VEC) * 16 + 2 * 16 + 3 * 16 + 4 * 16 + 3 * 4 + (frame_words + vol_words) * 4;
+    const size_t mat_bytes = s->has_textures ? (integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1) * sizeof(DevMaterial) : 0;   // the materials resolved per hit
+    const size_t slot_bytes = size_t(RT_PIPE_VEC) * 16 + 2 * 16 + 3 * 16 + 4 * 16 + 3 * 4 + (frame_words + vol_words) * 4 + mat_bytes;
     // (C5, 64 spp with a march per ray: 8 M slots 329 ms, 16 M 311, 32 M 289, 48 M 312, 64 M 326 -- fewer, fuller iterations until the shade passes' state
     // traffic takes over; the by-vertex path frame on the 1 M tree: 8 M 70.6 ms, 16 M 72.1; profiles/r03_c5_knobs.txt)
     unsigned want = s->volume.present ? 1u << 25 : 1u << 23;
@@ -104,6 +105,7 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
         fr.vol_samp = fr.vol_state + size_t(13) * n_slots; fr.vol_nmax = vol_nmax;
     }
     fr.frames = s->frames; fr.n_threads = n_slots;
+    { int rc = ensure_material_pool(s, fr, integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1, n_slots); if (rc) return rc; }   // scenes with textures (rt_texture.h)
     if (s->pipe_ev.empty()) {
         s->pipe_ev.resize(6 * RT_PIPE_TIMED); s->pipe_fence.resize(RT_PIPE_QN / RT_PIPE_BATCH);
         for (auto &e : s->pipe_ev) HIPCHK(hipEventCreate(&e));
@@ -178,6 +180,7 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
 static int render_bidir(RtScene *s, DevFrame &fr) {
     int rc = ensure(s, &s->frames, &s->frames_floats, size_t(RT_BD_FRAME_WORDS) * s->n_threads); if (rc) return rc;
     fr.frames = s->frames;
+    rc = ensure_material_pool(s, fr, 2 * RT_BD_MAX_VERTS, s->n_threads); if (rc) return rc;
     const int bk = (s->accel_kind == RT_ACCEL_GRID ? 2 : 0) + (s->counting ? 1 : 0);
     if (s->bgrids[bk] == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
     HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
@@ -552,6 +555,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
             rc = ensure(s, &s->frames, &s->frames_floats, size_t(rd->max_depth + 2) * RT_FRAME_WORDS * s->n_threads); if (rc) return rc;
             fr.frames = s->frames;
         }
+        rc = ensure_material_pool(s, fr, rd->integrator != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1, s->n_threads); if (rc) return rc;
         if (s->volume.present) {
             rc = ensure(s, &s->vol_buf, &s->vol_cap, (size_t(vol_levels) * 8 + 13 + vol_samp_words) * s->n_threads); if (rc) return rc;
             fr.vol_rays = s->vol_buf; fr.vol_state = s->vol_buf + size_t(vol_levels) * 8 * s->n_threads;

@@ -73,6 +73,15 @@ struct PipeLaunch {
 
 // ---- slot state <-> Lane ----------------------------------------------------------------------------------------
 // ctl word: stage (4 bits) | has_ray << 4 | specular << 5 | any << 6 | depth << 8 | fsp << 16
+// The material index of a slot's vertex travels in 16 bits.  A material resolved at the hit (rt_texture.h) has an index beyond them, but one that the
+// slot and its recursion level determine: 0xffff stands for it (rt_scene_set_textures keeps the scene's own materials below that).
+template <bool EXT> RT_DEV int pipe_mat_unpack(const DevFrame &fr, unsigned m16, int fsp, unsigned slot) {
+    if (EXT && m16 == 0xffffu) return int(fr.mat_pool_base + unsigned(fsp) * fr.n_threads + slot);
+    return int(m16);
+}
+template <bool EXT> RT_DEV unsigned pipe_mat_pack(const DevFrame &fr, int mat) {
+    return (EXT && fr.mat_pool_base != 0u && unsigned(mat) >= fr.mat_pool_base) ? 0xffffu : unsigned(mat);
+}
 template <int INTEG, bool EXT>
 RT_DEV void pipe_load(const PipePool &pl, const DevFrame &fr, unsigned slot, Lane &ln) {
     const float4 RT_G *st = RT_GPTR(const float4, pl.state) + slot;
@@ -92,21 +101,21 @@ RT_DEV void pipe_load(const PipePool &pl, const DevFrame &fr, unsigned slot, Lan
     if (ln.stage == ST_POP) {                                  // back from rt::pipe_march_kernel: Scene::Li of this level is complete in L; everything else the
         const float4 a2 = st[2 * n];                           // slot needs from here on is in the control planes (fsp == 0) or in its recursion frame (frame_pop)
         ln.L = mk3(a2.x, a2.y, a2.z);
-        { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = int(ml & 0xffffu); ln.v.light = int(ml >> 16) - 1; }
+        { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = pipe_mat_unpack<EXT>(fr, ml & 0xffffu, ln.fsp, slot); ln.v.light = int(ml >> 16) - 1; }
         ln.thr = mk3(1.f);
         return;
     }
     if (ln.stage == ST_VERTEX) {                               // waiting for a camera / continuation / specular ray: the next vertex is made from the hit (make_vertex) and
         const float4 a2 = st[2 * n], a3 = st[3 * n];           // every field of the direct-lighting loop is set before it is read (stage_body ST_VERTEX, ST_DIRECT_NEXT): only
         ln.L = mk3(a2.x, a2.y, a2.z);                          // the radiance bookkeeping travels (round 6: 4 planes instead of 11 each way, a quarter of a C5 sample's state traffic)
-        { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = int(ml & 0xffffu); ln.v.light = int(ml >> 16) - 1; }
+        { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = pipe_mat_unpack<EXT>(fr, ml & 0xffffu, ln.fsp, slot); ln.v.light = int(ml >> 16) - 1; }
         ln.thr = mk3(a3.x, a3.y, a3.z);
         { const unsigned lj = __float_as_uint(a3.w); ln.li = int(lj & 0xffffu); ln.lj = int(lj >> 16); }
         return;
     }
     const float4 a2 = st[2 * n], a3 = st[3 * n], a4 = st[4 * n], a5 = st[5 * n], a6 = st[6 * n], a7 = st[7 * n], a8 = st[8 * n], a9 = st[9 * n];
     ln.L = mk3(a2.x, a2.y, a2.z);
-    { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = int(ml & 0xffffu); ln.v.light = int(ml >> 16) - 1; }
+    { const unsigned ml = __float_as_uint(a2.w); ln.v.mat = pipe_mat_unpack<EXT>(fr, ml & 0xffffu, ln.fsp, slot); ln.v.light = int(ml >> 16) - 1; }
     ln.thr = mk3(a3.x, a3.y, a3.z);
     { const unsigned lj = __float_as_uint(a3.w); ln.li = int(lj & 0xffffu); ln.lj = int(lj >> 16); }
     ln.v.p = mk3(a4.x, a4.y, a4.z); ln.cur_light = __float_as_int(a4.w);
@@ -123,7 +132,7 @@ RT_DEV void pipe_load(const PipePool &pl, const DevFrame &fr, unsigned slot, Lan
     if (EXT) { const float4 a11 = st[11 * n]; ln.v.ng = mk3(a11.x, a11.y, a11.z); }
 }
 template <int INTEG, bool EXT>
-RT_DEV void pipe_store(const PipePool &pl, unsigned slot, const Lane &ln) {
+RT_DEV void pipe_store(const PipePool &pl, const DevFrame &fr, unsigned slot, const Lane &ln) {
     float4 RT_G *st = RT_GPTR(float4, pl.state) + slot;
     const size_t n = pl.n_slots;
     const unsigned ctl = unsigned(ln.stage) | (ln.has_ray ? 16u : 0u) | (ln.specular ? 32u : 0u) | (ln.tv.any ? 64u : 0u) |
@@ -131,7 +140,7 @@ RT_DEV void pipe_store(const PipePool &pl, unsigned slot, const Lane &ln) {
     st[0] = make_float4(__uint_as_float(ln.sample_index), __uint_as_float(ln.work), ln.image_x, ln.image_y);
     st[n] = make_float4(__uint_as_float(ln.dim_base), __uint_as_float(ln.rng.ctr), __uint_as_float(ctl), ln.alpha);
     if (ln.stage == ST_EXIT) return;
-    st[2 * n] = make_float4(ln.L.x, ln.L.y, ln.L.z, __uint_as_float(unsigned(ln.v.mat) | (unsigned(ln.v.light + 1) << 16)));
+    st[2 * n] = make_float4(ln.L.x, ln.L.y, ln.L.z, __uint_as_float(pipe_mat_pack<EXT>(fr, ln.v.mat) | (unsigned(ln.v.light + 1) << 16)));
     if (ln.stage == ST_VOL_STEP) return;                       // parked for the march kernel: the surface vertex is dead (see pipe_load)
     st[3 * n] = make_float4(ln.thr.x, ln.thr.y, ln.thr.z, __uint_as_float(unsigned(ln.li) | (unsigned(ln.lj) << 16)));
     if (ln.stage == ST_VERTEX) return;                         // (only ever stored while the slot waits for the ray that leads to its next vertex: see pipe_load)
@@ -151,7 +160,7 @@ RT_DEV void pipe_store(const PipePool &pl, unsigned slot, const Lane &ln) {
 // (the counting EXT kernel of DirectLighting with a medium allocates 170 VGPRs on its own since the infinite light, 2 above the 3-wave step of gfx950: held to
 // 3 waves, without scratch -- DESIGN.md 4.9; a minimum of 1 is what every other instantiation had and keeps)
 template <bool COUNT, int INTEG, bool VOL, bool EXT>
-__global__ __launch_bounds__(RT_BLOCK, (EXT && COUNT && VOL && INTEG == RT_INTEGRATOR_DIRECT) ? 3 : 1) void pipe_shade_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
+__global__ __launch_bounds__(RT_BLOCK, EXT ? 3 : 1) void pipe_shade_kernel(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp,
                                                                const PipePool *__restrict__ plp, PipeLaunch pk) {
     const DevScene &sc = *scp;
     const DevFrame &fr = *frp;
@@ -243,7 +252,7 @@ __global__ __launch_bounds__(RT_BLOCK, (EXT && COUNT && VOL && INTEG == RT_INTEG
             RT_GPTR(float4, pl.ray_o)[slot] = ro; RT_GPTR(float4, pl.ray_d)[slot] = rd;
         }
     }
-    pipe_store<INTEG, EXT>(pl, slot, ln);
+    pipe_store<INTEG, EXT>(pl, fr, slot, ln);
     if (COUNT) {
         unsigned long long v[4] = {c_cam, c_closest, c_any, c_bad};
         const int idx[4] = {0, 1, 2, 6};

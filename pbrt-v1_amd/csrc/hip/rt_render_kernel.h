@@ -46,7 +46,7 @@ RT_DEV unsigned long long band_lo(unsigned long long total, unsigned r, unsigned
 // best when VALU-bound: tiny cache-resident scenes); RT_HIGH_OCC_WAVES = 4 caps at 128 VGPRs (some spills to scratch) for
 // 4 waves/SIMD: +20 % on the memory-latency-bound 100k..1M-triangle scenes, -15 % on Cornell.
 template <bool COUNT, int INTEG, int ACCEL, bool VOL, int MINW, bool EXT>
-__global__ __launch_bounds__(RT_BLOCK, MINW) void render_kernel(const DevScene *__restrict__ scp,
+__global__ __launch_bounds__(RT_BLOCK, (EXT && COUNT && INTEG == RT_INTEGRATOR_PATH && ACCEL == RT_ACCEL_GRID && !VOL && MINW < 3) ? 3 : MINW) void render_kernel(const DevScene *__restrict__ scp,
                                                                        const DevFrame *__restrict__ frp) {
     __shared__ uint2 lds_stack[RT_STACK_LDS * RT_BLOCK];
     constexpr bool POOL = MINW < RT_HIGH_OCC_WAVES;                       // the pooled-leaf scratch (19 KB) is only carried by the kernels that use it

@@ -356,6 +356,11 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
             host_tri_frame_uv(d->tri_verts + size_t(9) * i, r.uv, (d->tri_flags[i] & 1u) != 0, nn, dpdu);
             const float inv = 1.f / sqrtf(dpdu[0] * dpdu[0] + dpdu[1] * dpdu[1] + dpdu[2] * dpdu[2]);
             for (int a = 0; a < 3; ++a) sn[a] = dpdu[a] * inv;
+            if (r.flags & RT_SHADING_UV) {                                        // kept on the host: rt_scene_set_textures uploads the uvs of a scene that gets textures (hit_point_uv)
+                if (s->tex_uv_idx_host.empty()) s->tex_uv_idx_host.assign(d->n_tris, -1);
+                s->tex_uv_idx_host[i] = int(s->tex_uv_host.size() / 6);
+                s->tex_uv_host.insert(s->tex_uv_host.end(), r.uv, r.uv + 6);
+            }
             if (r.flags & (RT_SHADING_N | RT_SHADING_S)) {
                 smooth = true; s->has_ext = true;
                 DevTriShading o; std::memset(&o, 0, sizeof o);
@@ -454,34 +459,12 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     // materials (OrenNayar constants: reflection.h:268-277)
     std::vector<DevMaterial> mats(d->n_materials);
     for (uint32_t i = 0; i < d->n_materials; ++i) {
-        const RtMaterial &m = d->materials[i]; DevMaterial &o = mats[i];
-        o.type = m.type; o.ior = m.ior; o.on_a = 1.f; o.on_b = -1.f;
-        for (int c = 0; c < 3; ++c) { o.r[c] = m.kd[c]; o.t[c] = m.kt[c]; }
-        o.has_r = (m.kd[0] != 0.f || m.kd[1] != 0.f || m.kd[2] != 0.f);
-        o.has_t = (m.kt[0] != 0.f || m.kt[1] != 0.f || m.kt[2] != 0.f);
-        for (int c = 0; c < 3; ++c) o.ks[c] = m.ks[c];
-        o.exponent = 0.f;
-        for (int c = 0; c < 3; ++c) o.kr[c] = m.kr[c];
-        o.has_g = (m.ks[0] != 0.f || m.ks[1] != 0.f || m.ks[2] != 0.f); o.has_kr = (m.kr[0] != 0.f || m.kr[1] != 0.f || m.kr[2] != 0.f);
-        if (m.type == RT_MAT_PLASTIC || m.type == RT_MAT_UBER) { s->has_ext = true; float e = 1.f / m.roughness; if (e > 1000.f || std::isnan(e)) e = 1000.f; o.exponent = e; }
-        if (m.type == RT_MAT_SHINYMETAL || m.type == RT_MAT_TRANSLUCENT) {         // DevMaterial's fields per type: rt_device.h
-            RtMaterialLobes lb; rt_material_lobes(&m, &lb);
-            const bool shiny = m.type == RT_MAT_SHINYMETAL;
-            for (int c = 0; c < 3; ++c) {
-                o.r[c] = lb.r_kd[c]; o.t[c] = lb.t_kd[c];
-                o.ks[c] = shiny ? lb.eta_ks[c] : lb.r_ks[c]; o.kr[c] = shiny ? lb.eta_kr[c] : lb.t_ks[c];
-            }
-            o.has_r = lb.has_dr; o.has_t = lb.has_dt; o.has_g = lb.has_gr; o.has_kr = lb.has_gt;
-            s->has_ext = true; float e = 1.f / m.roughness; if (e > 1000.f || std::isnan(e)) e = 1000.f; o.exponent = e;
-        }
+        const RtMaterial &m = d->materials[i];
         if (m.type < RT_MAT_MATTE || m.type > RT_MAT_TRANSLUCENT) return fail(RT_EINVAL, "rt_scene_create: unknown material type");
-        if (m.type == RT_MAT_MATTE && m.sigma != 0.f) {
-            float sigma = (3.14159265358979323846f / 180.f) * m.sigma;
-            float sigma2 = sigma * sigma;
-            o.on_a = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
-            o.on_b = 0.45f * sigma2 / (sigma2 + 0.09f);
-        }
+        rt_material_resolve(&m, &mats[i]);                                        // include/pbrt_hip_texture.h: what the EXT kernels do per hit for a textured material
+        if (m.type >= RT_MAT_PLASTIC) s->has_ext = true;                           // plastic, uber, shinymetal, translucent: their lobes exist only in the EXT kernels
     }
+    s->materials_host = mats;                                                      // rt_scene_set_textures / rt_render: the records move when room for resolved ones is added
     if ((rc = upload(s, mats.data(), mats.size(), &s->dev.materials))) return rc;
 
     // lights + emitter triangles with ShapeSet area CDF (shape.h:122-135)
@@ -612,6 +595,7 @@ int rt_scene_destroy(RtScene *s) {
     if (s->samples) HIPWARN(hipFree(s->samples));
     if (s->resolve_buf) HIPWARN(hipFree(s->resolve_buf));
     if (s->vol_buf) HIPWARN(hipFree(s->vol_buf));
+    if (s->mat_buf) HIPWARN(hipFree(s->mat_buf));
     if (s->light_dims) HIPWARN(hipFree(s->light_dims));
     if (s->wt_base) HIPWARN(hipFree(s->wt_base));
     if (s->wt_recbase) HIPWARN(hipFree(s->wt_recbase));
@@ -688,6 +672,119 @@ int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
     s->has_ext = true;                                                          // the density code exists only in the EXT kernels
     return RT_OK;
 }
+
+// Textured material parameters (pbrt_hip.h, include/pbrt_hip_texture.h).  Everything is checked before anything is uploaded: every index, kind and
+// mapping, the value type of every child and slot, children strictly below their parents (no cycle can be written that way), and per parameter the
+// length of its post-order program and the stack it needs.
+int rt_scene_set_textures(RtScene *s, const RtTexture *nodes, uint32_t n_nodes, const RtMaterialTextures *mats, uint32_t n_mats) {
+    if (!s || !nodes || !mats) return fail(RT_EINVAL, "rt_scene_set_textures: null argument");
+    if (s->rendered) return fail(RT_ESTATE, "rt_scene_set_textures: the scene has rendered a frame already");
+    if (s->has_textures) return fail(RT_ESTATE, "rt_scene_set_textures: the scene has textures already");
+    if (n_nodes == 0 || n_nodes > RT_TEX_MAX_NODES) return fail(RT_EINVAL, "rt_scene_set_textures: the number of texture nodes must be 1 .. " + std::to_string(RT_TEX_MAX_NODES));
+    if (n_mats != s->materials_host.size()) return fail(RT_EINVAL, "rt_scene_set_textures: n_mats differs from the scene's number of materials");
+    if (n_mats > 65534u) return fail(RT_EINVAL, "rt_scene_set_textures: more than 65534 materials");
+    return guarded("rt_scene_set_textures", [&]() -> int {
+        for (uint32_t i = 0; i < n_nodes; ++i) {
+            const RtTexture &t = nodes[i];
+            const std::string at = "rt_scene_set_textures: node " + std::to_string(i) + ": ";
+            if (t.kind < 0 || t.kind >= RT_TEX_KIND_COUNT) return fail(RT_EINVAL, at + "unknown texture kind");
+            if (t.is_color != 0 && t.is_color != 1) return fail(RT_EINVAL, at + "is_color must be 0 or 1");
+            if (t.kind == RT_TEX_UV && !t.is_color) return fail(RT_EINVAL, at + "the uv texture is a colour texture");
+            const bool mapped = t.kind == RT_TEX_BILERP || t.kind == RT_TEX_UV || t.kind == RT_TEX_CHECKERBOARD;
+            if (mapped && (t.mapping < 0 || t.mapping >= RT_TEXMAP_COUNT)) return fail(RT_EINVAL, at + "unknown mapping");
+            const int n_child = (t.kind == RT_TEX_SCALE || t.kind == RT_TEX_CHECKERBOARD) ? 2 : t.kind == RT_TEX_MIX ? 3 : 0;
+            for (int c = 0; c < 3; ++c) {
+                const int32_t ch = t.child[c];
+                if (c >= n_child) { if (ch != -1) return fail(RT_EINVAL, at + "a child index where the kind takes none (must be -1)"); continue; }
+                if (ch < 0 || uint32_t(ch) >= n_nodes) return fail(RT_EINVAL, at + "child index out of range");
+                if (uint32_t(ch) >= i) return fail(RT_EINVAL, at + "a child must precede its parent in the table (a cycle, or a table out of order)");
+                const int want_color = (c == 2) ? 0 : t.is_color;                  // amount is a float texture; tex1 / tex2 have the node's type
+                if (nodes[ch].is_color != want_color) return fail(RT_EINVAL, at + "child of the wrong value type (float / color)");
+            }
+        }
+        // post-order programs: tree size and stack need per node (children are below their parents, so one forward pass)
+        std::vector<uint32_t> size(n_nodes), need(n_nodes);
+        for (uint32_t i = 0; i < n_nodes; ++i) {
+            const RtTexture &t = nodes[i];
+            uint64_t sz = 1; uint32_t nd = 1, held = 0;
+            for (int c = 0; c < 3; ++c) if (t.child[c] >= 0) { sz += size[t.child[c]]; nd = std::max(nd, held + need[t.child[c]]); ++held; }
+            size[i] = uint32_t(std::min<uint64_t>(sz, 1u << 20)); need[i] = nd;
+        }
+        std::vector<DevMatTex> dm(n_mats);
+        std::vector<int> prog;
+        uint32_t n_textured = 0;
+        for (uint32_t i = 0; i < n_mats; ++i) {
+            const RtMaterialTextures &m = mats[i]; DevMatTex &o = dm[i];
+            const std::string at = "rt_scene_set_textures: material " + std::to_string(i) + ": ";
+            if (m.raw.type != s->materials_host[i].type) return fail(RT_EINVAL, at + "type differs from the scene's material");
+            o.raw = m.raw; o.textured = 0;
+            for (int k = 0; k < RT_MATSLOT_COUNT; ++k) {
+                o.prog_off[k] = 0; o.prog_len[k] = 0;
+                const int32_t root = m.tex[k];
+                if (root == -1) continue;
+                if (root < 0 || uint32_t(root) >= n_nodes) return fail(RT_EINVAL, at + "texture index out of range");
+                if (nodes[root].is_color != (k == RT_MATSLOT_F ? 0 : 1)) return fail(RT_EINVAL, at + "texture of the wrong value type for its slot (float / color)");
+                if (size[root] > RT_TEX_MAX_PROGRAM) return fail(RT_EINVAL, at + "a parameter's texture graph has more than " + std::to_string(RT_TEX_MAX_PROGRAM) + " nodes");
+                if (need[root] > RT_TEX_MAX_STACK) return fail(RT_EINVAL, at + "a parameter's texture graph needs more than " + std::to_string(RT_TEX_MAX_STACK) + " values at once");
+                o.prog_off[k] = int(prog.size());
+                struct Walk { static void go(const RtTexture *nodes, int n, std::vector<int> &out) { for (int c = 0; c < 3; ++c) if (nodes[n].child[c] >= 0) go(nodes, nodes[n].child[c], out); out.push_back(n); } };
+                Walk::go(nodes, root, prog);
+                o.prog_len[k] = int(prog.size()) - o.prog_off[k];
+                o.textured = 1;
+            }
+            n_textured += uint32_t(o.textured);
+        }
+        HIPCHK(hipSetDevice(s->device));
+        const RtTexture *dnodes = nullptr; const int *dprog = nullptr; const DevMatTex *dmt = nullptr;
+        int rc;
+        if ((rc = upload(s, nodes, size_t(n_nodes), &dnodes))) return rc;
+        if ((rc = upload(s, prog.data(), prog.size(), &dprog))) return rc;
+        if ((rc = upload(s, dm.data(), dm.size(), &dmt))) return rc;
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (n_textured && s->n_tris) {                                          // mark the primitives of textured materials (RT_PRIM_TEXTURED in the word make_vertex reads)
+            std::vector<float4> shade(size_t(2) * s->n_tris);
+            HIPCHK(hipMemcpy(shade.data(), s->dev.tri_shade, shade.size() * sizeof(float4), hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < s->n_tris; ++i) {
+                uint32_t bits; std::memcpy(&bits, &shade[2 * size_t(i)].w, 4);
+                if (dm[bits & 0xffffu].textured) { bits |= RT_PRIM_TEXTURED; std::memcpy(&shade[2 * size_t(i)].w, &bits, 4); }
+            }
+            HIPCHK(hipMemcpy(const_cast<float4 *>(s->dev.tri_shade), shade.data(), shade.size() * sizeof(float4), hipMemcpyHostToDevice));
+        }
+        const int *duvi = nullptr; const float *duv = nullptr;                  // the per-vertex uvs of the meshes that have them (6 floats per triangle)
+        if (n_textured && !s->tex_uv_idx_host.empty()) {
+            if ((rc = upload(s, s->tex_uv_idx_host.data(), s->tex_uv_idx_host.size(), &duvi))) return rc;
+            if ((rc = upload(s, s->tex_uv_host.data(), s->tex_uv_host.size(), &duv))) return rc;
+        }
+        std::vector<int>().swap(s->tex_uv_idx_host); std::vector<float>().swap(s->tex_uv_host);   // (the call is made once)
+        DevScene &d = s->dev;
+        d.n_textured = int(n_textured); d.tex_nodes = dnodes; d.tex_prog = dprog; d.mat_tex = dmt; d.tex_uv_idx = duvi; d.tex_uv = duv;
+        HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
+        s->has_textures = true;
+        s->has_ext = true;                                                      // the evaluator exists only in the EXT kernels
+        return RT_OK;
+    });
+}
+}  // extern "C"
+// room for the per-hit records: [the scene's materials | levels * n_slots resolved ones].  Called by rt_render before its first launch.
+int ensure_material_pool(RtScene *s, DevFrame &fr, size_t levels, size_t n_slots) {
+    fr.mat_pool_base = 0;
+    if (!s->has_textures || s->dev.n_textured == 0) return RT_OK;
+    const size_t base = s->materials_host.size(), need = levels * n_slots;
+    if (base + need >= (size_t(1) << 31)) return fail(RT_EINVAL, "rt_render: more than 2^31 resolved-material records (threads x recursion levels)");
+    if (!s->mat_buf || need > s->mat_pool_cap) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        DevMaterial *nb = nullptr;
+        HIPCHK(hipMalloc((void **)&nb, (base + need) * sizeof(DevMaterial)));
+        if (s->mat_buf) HIPWARN(hipFree(s->mat_buf));
+        s->mat_buf = nb; s->mat_pool_cap = need;
+        HIPCHK(hipMemcpy(nb, s->materials_host.data(), base * sizeof(DevMaterial), hipMemcpyHostToDevice));
+        s->dev.materials = nb;
+        HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
+    }
+    fr.mat_pool_base = unsigned(base);
+    return RT_OK;
+}
+extern "C" {
 
 int rt_scene_accel_info(const RtScene *s, RtAccelInfo *info) {
     if (!s || !info) return fail(RT_EINVAL, "null argument");

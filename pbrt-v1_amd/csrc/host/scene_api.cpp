@@ -412,16 +412,106 @@ void PbrtApi::TransformEnd() {
     if (xfStack.empty()) { Error("Unmatched pbrtTransformEnd() encountered. Ignoring it."); return; }
     ctm = xfStack.back(); xfStack.pop_back();
 }
+int PbrtApi::constantNode(bool color, Float3 v) {                                   // ConstantTexture (texture.h:113-123)
+    RtTexture t; std::memset(&t, 0, sizeof t);
+    t.kind = RT_TEX_CONSTANT; t.is_color = color ? 1 : 0; t.child[0] = t.child[1] = t.child[2] = -1;
+    t.value[0] = v.x; t.value[1] = v.y; t.value[2] = v.z;
+    texNodes.push_back(t); texNames.push_back(std::string());
+    return int(texNodes.size()) - 1;
+}
+// a sub-texture of a Texture statement: TextureParams(params, params, ...).Get{Float,Spectrum}Texture(n, d) (api.cpp:310-312)
+int PbrtApi::subTexture(const ParamSet &ps, const std::string &n, bool color, float d) {
+    const std::string tex = ps.FindTexture(n);
+    if (!tex.empty()) {
+        if (color) {
+            if (gs.spectrumTexNodes.count(tex)) return gs.spectrumTexNodes[tex];
+            if (gs.spectrumTextures.count(tex)) return constantNode(true, gs.spectrumTextures[tex]);
+            Error("Couldn't find spectrumtexture named \"%s\"", n.c_str());
+        } else {
+            if (gs.floatTexNodes.count(tex)) return gs.floatTexNodes[tex];
+            if (gs.floatTextures.count(tex)) { const float f = gs.floatTextures[tex]; return constantNode(false, Float3{f, f, f}); }
+            Error("Couldn't find float texture named \"%s\"", n.c_str());
+        }
+    }
+    if (color) return constantNode(true, ps.FindOneSpectrum(n, Float3{d, d, d}));
+    const float f = ps.FindOneFloat(n, d);
+    return constantNode(false, Float3{f, f, f});
+}
+// the 2-D mapping of bilerp / uv / checkerboard (bilerp.cpp:63-81 and its copies): names and defaults of the factories
+bool PbrtApi::textureMapping(const ParamSet &ps, RtTexture &t) {
+    const std::string type = ps.FindOneString("mapping", "");
+    t.mapping = RT_TEXMAP_UV; t.map[0] = 1.f; t.map[1] = 1.f; t.map[2] = 0.f; t.map[3] = 0.f;
+    if (type == "" || type == "uv") {
+        t.map[0] = ps.FindOneFloat("uscale", 1.f); t.map[1] = ps.FindOneFloat("vscale", 1.f);
+        t.map[2] = ps.FindOneFloat("udelta", 0.f); t.map[3] = ps.FindOneFloat("vdelta", 0.f);
+    } else if (type == "spherical" || type == "cylindrical") {                     // tex2world.GetInverse(): the CTM at the statement
+        t.mapping = type == "spherical" ? RT_TEXMAP_SPHERICAL : RT_TEXMAP_CYLINDRICAL;
+        std::memcpy(t.world_to_texture, ctm.inv.m, sizeof t.world_to_texture);
+    } else if (type == "planar") {
+        const Float3 v1 = ps.FindOneVector("v1", Float3{1, 0, 0}), v2 = ps.FindOneVector("v2", Float3{0, 1, 0});
+        t.mapping = RT_TEXMAP_PLANAR;
+        t.map[0] = v1.x; t.map[1] = v1.y; t.map[2] = v1.z; t.map[3] = v2.x; t.map[4] = v2.y; t.map[5] = v2.z;
+        t.map[6] = ps.FindOneFloat("udelta", 0.f); t.map[7] = ps.FindOneFloat("vdelta", 0.f);
+    } else Error("2D texture mapping \"%s\" unknown", type.c_str());                // ... and the default UVMapping2D
+    return true;
+}
 void PbrtApi::Texture(const std::string &name, const std::string &type, const std::string &cls, const ParamList &p) {
     if (!verifyWorld("Texture")) return;
     ParamSet ps(p);
-    if (cls != "constant") {                 // textures/*.cpp other than constant.cpp are out of scope
-        Error("Unable to load plugin \"%s\" (texture): only \"constant\" textures are on the accelerated path", cls.c_str());
+    if (type != "float" && type != "color") { Error("Texture type \"%s\" unknown.", type.c_str()); return; }
+    const bool color = type == "color";
+    if (cls == "constant") {                                                        // textures/constant.cpp: folded to its value, as every scene so far
+        if (!color) { gs.floatTextures[name] = ps.FindOneFloat("value", 1.f); gs.floatTexNodes.erase(name); }
+        else { gs.spectrumTextures[name] = ps.FindOneSpectrum("value", Float3{1.f, 1.f, 1.f}); gs.spectrumTexNodes.erase(name); }
         return;
     }
-    if (type == "float") gs.floatTextures[name] = ps.FindOneFloat("value", 1.f);            // textures/constant.cpp
-    else if (type == "color") gs.spectrumTextures[name] = ps.FindOneSpectrum("value", Float3{1.f, 1.f, 1.f});
-    else Error("Texture type \"%s\" unknown.", type.c_str());
+    // classes whose value needs more than the hit itself stay errors; the name stays undefined (MakeFloatTexture returning NULL, api.cpp:320)
+    if (cls == "imagemap") { Error("Texture \"%s\": class \"imagemap\" is not supported (no image reader, and its lookup is filtered with ray differentials)", name.c_str()); return; }
+    if (cls == "fbm" || cls == "wrinkled" || cls == "marble" || cls == "windy") {
+        Error("Texture \"%s\": class \"%s\" is not supported (it needs the noise table and ray differentials)", name.c_str(), cls.c_str()); return;
+    }
+    if (cls == "dots") { Error("Texture \"%s\": class \"dots\" is not supported (it needs the noise function)", name.c_str()); return; }
+    if (cls != "scale" && cls != "mix" && cls != "bilerp" && cls != "uv" && cls != "checkerboard") {
+        Error("Unable to load plugin \"%s\" (texture)", cls.c_str()); return;
+    }
+    RtTexture t; std::memset(&t, 0, sizeof t);
+    t.is_color = color ? 1 : 0; t.child[0] = t.child[1] = t.child[2] = -1;
+    if (cls == "checkerboard") {                                                    // checkerboard.cpp:177-257
+        const int dim = ps.FindOneInt("dimension", 2);
+        if (dim != 2 && dim != 3) { Error("%d dimensional checkerboard texture not supported", dim); return; }
+        if (dim == 3) { Error("Texture \"%s\": a 3 dimensional checkerboard is not supported (it is supersampled with ray differentials and the sampler-independent RNG)", name.c_str()); return; }
+        const std::string aamode = ps.FindOneString("aamode", "");
+        if (aamode == "") { Error("Texture \"%s\": checkerboard without \"aamode\" takes the reference's default \"closedform\", which needs ray differentials; only \"string aamode\" \"none\" is supported", name.c_str()); return; }
+        if (aamode != "none") { Error("Texture \"%s\": checkerboard aamode \"%s\" is not supported (it needs ray differentials); only \"none\" is", name.c_str(), aamode.c_str()); return; }
+        t.kind = RT_TEX_CHECKERBOARD;
+        t.child[0] = subTexture(ps, "tex1", color, 1.f); t.child[1] = subTexture(ps, "tex2", color, 0.f);
+        textureMapping(ps, t);
+    } else if (cls == "scale") {                                                    // scale.cpp
+        t.kind = RT_TEX_SCALE;
+        t.child[0] = subTexture(ps, "tex1", color, 1.f); t.child[1] = subTexture(ps, "tex2", color, 1.f);
+    } else if (cls == "mix") {                                                      // mix.cpp
+        t.kind = RT_TEX_MIX;
+        t.child[0] = subTexture(ps, "tex1", color, 0.f); t.child[1] = subTexture(ps, "tex2", color, 1.f); t.child[2] = subTexture(ps, "amount", false, .5f);
+    } else if (cls == "bilerp") {                                                   // bilerp.cpp
+        t.kind = RT_TEX_BILERP;
+        textureMapping(ps, t);
+        const char *names[4] = {"v00", "v01", "v10", "v11"}; const float defs[4] = {0.f, 1.f, 0.f, 1.f};
+        for (int k = 0; k < 4; ++k) {
+            Float3 v;
+            if (color) v = ps.FindOneSpectrum(names[k], Float3{defs[k], defs[k], defs[k]});
+            else { const float f = ps.FindOneFloat(names[k], defs[k]); v = Float3{f, f, f}; }
+            t.value[3 * k] = v.x; t.value[3 * k + 1] = v.y; t.value[3 * k + 2] = v.z;
+        }
+    } else {                                                                        // uv.cpp: colour only (CreateFloatTexture returns NULL)
+        if (!color) { ps.ReportUnused(); return; }
+        t.kind = RT_TEX_UV;
+        textureMapping(ps, t);
+    }
+    ps.ReportUnused();                                                              // MakeFloatTexture / MakeSpectrumTexture dynload.cpp:319-341
+    texNodes.push_back(t); texNames.push_back(name);
+    const int node = int(texNodes.size()) - 1;
+    if (color) { gs.spectrumTexNodes[name] = node; gs.spectrumTextures.erase(name); }
+    else { gs.floatTexNodes[name] = node; gs.floatTextures.erase(name); }
 }
 void PbrtApi::Material(const std::string &n, const ParamList &p) { if (verifyWorld("Material")) { gs.material = n; gs.materialParams = ParamSet(p); } }
 void PbrtApi::AreaLightSource(const std::string &n, const ParamList &p) { if (verifyWorld("AreaLightSource")) { gs.areaLight = n; gs.areaLightParams = ParamSet(p); } }
@@ -482,26 +572,32 @@ void PbrtApi::LightSource(const std::string &n, const ParamList &p) {
     lights.push_back(L);
 }
 
-Float3 PbrtApi::spectrumParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, Float3 d) {   // paramset.cpp:434-449
+Float3 PbrtApi::spectrumParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, Float3 d, int *node) {   // paramset.cpp:434-449
+    if (node) *node = -1;
     std::string tex = geom.FindTexture(n); if (tex.empty()) tex = mat.FindTexture(n);
     if (!tex.empty()) {
         if (gs.spectrumTextures.count(tex)) return gs.spectrumTextures[tex];
-        Error("Couldn't find spectrumtexture named \"%s\"", n.c_str());
+        if (gs.spectrumTexNodes.count(tex)) {
+            if (node) *node = gs.spectrumTexNodes[tex];
+            else Error("Parameter \"%s\": the non-constant texture \"%s\" is not supported here; the literal or default value is used", n.c_str(), tex.c_str());
+        } else Error("Couldn't find spectrumtexture named \"%s\"", n.c_str());
     }
     return geom.FindOneSpectrum(n, mat.FindOneSpectrum(n, d));
 }
-float PbrtApi::floatParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, float d) {         // paramset.cpp:450-465
+float PbrtApi::floatParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, float d, int *node) {         // paramset.cpp:450-465
+    if (node) *node = -1;
     std::string tex = geom.FindTexture(n); if (tex.empty()) tex = mat.FindTexture(n);
     if (!tex.empty()) {
         if (gs.floatTextures.count(tex)) return gs.floatTextures[tex];
-        Error("Couldn't find float texture named \"%s\"", n.c_str());
+        if (gs.floatTexNodes.count(tex)) {
+            if (node) *node = gs.floatTexNodes[tex];
+            else Error("Parameter \"%s\": the non-constant texture \"%s\" is not supported here (bump mapping is not on the accelerated path) and is not applied", n.c_str(), tex.c_str());
+        } else Error("Couldn't find float texture named \"%s\"", n.c_str());
     }
     return geom.FindOneFloat(n, mat.FindOneFloat(n, d));
 }
 
 int PbrtApi::makeMaterial(const ParamSet &shapeParams) {
-    auto clamp0 = [](Float3 c) { Float3 r = {c.x < 0.f ? 0.f : c.x, c.y < 0.f ? 0.f : c.y, c.z < 0.f ? 0.f : c.z}; return r; };
-    RtMaterial m; std::memset(&m, 0, sizeof m);
     std::string name = gs.material;
     if (name != "matte" && name != "mirror" && name != "glass" && name != "plastic" && name != "uber" && name != "shinymetal" && name != "translucent") {
         Error("Unable to load plugin \"%s\" (material); using \"matte\" (api.cpp:376-379)", name.c_str());
@@ -510,52 +606,35 @@ int PbrtApi::makeMaterial(const ParamSet &shapeParams) {
     const ParamSet &mp = gs.materialParams;
     if (floatParam(shapeParams, mp, "bumpmap", 0.f) != 0.f)
         Warning("Non-zero constant \"bumpmap\" displaces uniformly and leaves the shading frame unchanged");
+    // the raw parameters by slot (include/pbrt_hip_texture.h RtMaterialParams) and the texture node of every textured one; what the material makes of
+    // them -- clamps, uber's products -- is rt_material_from_params, the definition the device applies per hit to a textured material
+    RtMaterialTextures mt; std::memset(&mt, 0, sizeof mt);
+    for (int k = 0; k < RT_MATSLOT_COUNT; ++k) mt.tex[k] = -1;
+    RtMaterialParams &P = mt.raw;
+    auto color = [&](int slot, const char *pn, float d) {
+        const Float3 v = spectrumParam(shapeParams, mp, pn, Float3{d, d, d}, &mt.tex[slot]);
+        P.c[slot][0] = v.x; P.c[slot][1] = v.y; P.c[slot][2] = v.z;
+    };
+    auto scalar = [&](const char *pn, float d) { P.f = floatParam(shapeParams, mp, pn, d, &mt.tex[RT_MATSLOT_F]); };
     if (name == "matte") {                                                          // matte.cpp:46-71
-        Float3 kd = clamp0(spectrumParam(shapeParams, mp, "Kd", Float3{1.f, 1.f, 1.f}));
-        float sig = floatParam(shapeParams, mp, "sigma", 0.f); sig = sig < 0.f ? 0.f : (sig > 90.f ? 90.f : sig);
-        m.type = RT_MAT_MATTE; m.kd[0] = kd.x; m.kd[1] = kd.y; m.kd[2] = kd.z; m.sigma = sig; m.ior = 1.f;
+        P.type = RT_MAT_MATTE; color(0, "Kd", 1.f); scalar("sigma", 0.f);
     } else if (name == "plastic") {                                                 // plastic.cpp:47-77
-        Float3 kd = clamp0(spectrumParam(shapeParams, mp, "Kd", Float3{1.f, 1.f, 1.f}));
-        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
-        m.type = RT_MAT_PLASTIC; m.kd[0] = kd.x; m.kd[1] = kd.y; m.kd[2] = kd.z; m.ks[0] = ks.x; m.ks[1] = ks.y; m.ks[2] = ks.z;
-        m.roughness = floatParam(shapeParams, mp, "roughness", .1f); m.ior = 1.f;
+        P.type = RT_MAT_PLASTIC; color(0, "Kd", 1.f); color(1, "Ks", 1.f); scalar("roughness", .1f);
     } else if (name == "uber") {                                                    // uber.cpp:52-100
-        Float3 kd = clamp0(spectrumParam(shapeParams, mp, "Kd", Float3{1.f, 1.f, 1.f}));
-        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
-        Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{0.f, 0.f, 0.f}));
-        Float3 op = clamp0(spectrumParam(shapeParams, mp, "opacity", Float3{1.f, 1.f, 1.f}));
-        m.type = RT_MAT_UBER; m.ior = 1.f;
-        m.kt[0] = -op.x + 1.f; m.kt[1] = -op.y + 1.f; m.kt[2] = -op.z + 1.f;        // SpecularTransmission(-op + Spectrum(1.), 1., 1.)
-        m.kd[0] = op.x * kd.x; m.kd[1] = op.y * kd.y; m.kd[2] = op.z * kd.z;
-        m.ks[0] = op.x * ks.x; m.ks[1] = op.y * ks.y; m.ks[2] = op.z * ks.z;
-        m.kr[0] = op.x * kr.x; m.kr[1] = op.y * kr.y; m.kr[2] = op.z * kr.z;
-        m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
+        P.type = RT_MAT_UBER; color(0, "Kd", 1.f); color(1, "Ks", 1.f); color(2, "Kr", 0.f); color(3, "opacity", 1.f); scalar("roughness", .1f);
     } else if (name == "shinymetal") {                                              // shinymetal.cpp:43-73; the etas: include/pbrt_hip_material.h
-        Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{1.f, 1.f, 1.f}));
-        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
-        m.type = RT_MAT_SHINYMETAL; m.ior = 1.f;
-        m.ks[0] = ks.x; m.ks[1] = ks.y; m.ks[2] = ks.z; m.kr[0] = kr.x; m.kr[1] = kr.y; m.kr[2] = kr.z;
-        m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
-    } else if (name == "translucent") {                                             // translucent.cpp:45-94; kr = reflect, kt = transmit
-        Float3 kd = clamp0(spectrumParam(shapeParams, mp, "Kd", Float3{1.f, 1.f, 1.f}));
-        Float3 ks = clamp0(spectrumParam(shapeParams, mp, "Ks", Float3{1.f, 1.f, 1.f}));
-        Float3 rf = clamp0(spectrumParam(shapeParams, mp, "reflect", Float3{.5f, .5f, .5f}));
-        Float3 tr = clamp0(spectrumParam(shapeParams, mp, "transmit", Float3{.5f, .5f, .5f}));
-        m.type = RT_MAT_TRANSLUCENT; m.ior = 1.f;
-        m.kd[0] = kd.x; m.kd[1] = kd.y; m.kd[2] = kd.z; m.ks[0] = ks.x; m.ks[1] = ks.y; m.ks[2] = ks.z;
-        m.kr[0] = rf.x; m.kr[1] = rf.y; m.kr[2] = rf.z; m.kt[0] = tr.x; m.kt[1] = tr.y; m.kt[2] = tr.z;
-        m.roughness = floatParam(shapeParams, mp, "roughness", .1f);
+        P.type = RT_MAT_SHINYMETAL; color(2, "Kr", 1.f); color(1, "Ks", 1.f); scalar("roughness", .1f);
+    } else if (name == "translucent") {                                             // translucent.cpp:45-94
+        P.type = RT_MAT_TRANSLUCENT; color(0, "Kd", 1.f); color(1, "Ks", 1.f); color(2, "reflect", .5f); color(3, "transmit", .5f); scalar("roughness", .1f);
     } else if (name == "mirror") {                                                  // mirror.cpp:42-61
-        Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{1.f, 1.f, 1.f}));
-        m.type = RT_MAT_MIRROR; m.kd[0] = kr.x; m.kd[1] = kr.y; m.kd[2] = kr.z; m.ior = 1.f;
+        P.type = RT_MAT_MIRROR; color(0, "Kr", 1.f);
     } else {                                                                        // glass.cpp:46-70
-        Float3 kr = clamp0(spectrumParam(shapeParams, mp, "Kr", Float3{1.f, 1.f, 1.f}));
-        Float3 kt = clamp0(spectrumParam(shapeParams, mp, "Kt", Float3{1.f, 1.f, 1.f}));
-        m.type = RT_MAT_GLASS; m.kd[0] = kr.x; m.kd[1] = kr.y; m.kd[2] = kr.z; m.kt[0] = kt.x; m.kt[1] = kt.y; m.kt[2] = kt.z;
-        m.ior = floatParam(shapeParams, mp, "index", 1.5f);
+        P.type = RT_MAT_GLASS; color(0, "Kr", 1.f); color(1, "Kt", 1.f); scalar("index", 1.5f);
     }
+    RtMaterial m; std::memset(&m, 0, sizeof m);
+    rt_material_from_params(&P, &m);
     if (m.type == RT_MAT_SHINYMETAL || m.type == RT_MAT_TRANSLUCENT) mp.ReportUnused();     // MakeMaterial dynload.cpp:314 (the shape's own parameters were reported by the shape)
-    materials.push_back(m);
+    materials.push_back(m); materialTextures.push_back(mt);
     return int(materials.size()) - 1;
 }
 
@@ -810,6 +889,7 @@ void PbrtApi::resetWorld() {
     meshes.clear(); materials.clear(); lights.clear(); light_tris.clear(); quadrics.clear();
     std::memset(&volume, 0, sizeof volume); nVolumes = 0;
     std::memset(&density, 0, sizeof density); densityValues.clear();
+    texNodes.clear(); texNames.clear(); materialTextures.clear();
 }
 
 void PbrtApi::WorldEnd() {                                                          // api.cpp:458-529
@@ -849,6 +929,8 @@ void PbrtApi::WorldEnd() {                                                      
     sd->materials = materials; sd->lights = lights; sd->light_tris = light_tris; sd->quadrics = quadrics;
     sd->scene.volume = volume; sd->scene.accel = acc.params;
     sd->density = density; sd->density_values.swap(densityValues);
+    for (const RtMaterialTextures &mt : materialTextures) for (int k = 0; k < RT_MATSLOT_COUNT; ++k) sd->has_textures = sd->has_textures || mt.tex[k] >= 0;
+    sd->textures = texNodes; sd->texture_names = texNames; sd->material_textures = materialTextures;
     RtRenderDesc &r = sd->render;
     r.integrator = si.kind; r.max_depth = si.maxDepth; r.strategy = si.strategy;
     r.volume_integrator = vi.kind; r.step_size = vi.stepSize;
@@ -913,6 +995,7 @@ void pbrt_host_film_dims(const RtRenderDesc *r, int *out8) {
 void pbrt_host_scene_counts(const RtSceneDesc *s, unsigned *out4) { out4[0] = s->n_tris; out4[1] = s->n_materials; out4[2] = s->n_lights; out4[3] = s->n_light_tris; }
 const float *pbrt_host_camera(const RtSceneDesc *s) { return s->camera.raster_to_camera; }
 const float *pbrt_host_tri_verts(const RtSceneDesc *s) { return s->tri_verts; }
+const uint16_t *pbrt_host_tri_material(const RtSceneDesc *s) { return s->tri_material; }
 const RtAccelParams *pbrt_host_accel_params(const RtSceneDesc *s) { return &s->accel; }
 const RtVolume *pbrt_host_volume(const RtSceneDesc *s) { return &s->volume; }
 // the parsed material table and what rt_scene_create derives from one entry (include/pbrt_hip_material.h)
@@ -924,6 +1007,40 @@ const RtDensityRegion *pbrt_host_density_desc(PbrtHostScene *h, int i) {
     const SceneDescription *sd = h->api.frames[i];
     return sd->density.kind != RT_DENSITY_NONE && sd->scene.volume.present ? &sd->density : nullptr;
 }
+// the frame's texture table for rt_scene_set_textures (include/pbrt_hip_texture.h).  Returns 1 when some material has a textured slot -- only then is
+// the table handed to the device --, 0 otherwise; the arrays are there either way (a scene may define textures that no material uses).
+int pbrt_host_textures(PbrtHostScene *h, int i, const RtTexture **nodes, unsigned *n_nodes, const RtMaterialTextures **mats, unsigned *n_mats) {
+    const SceneDescription *sd = h->api.frames[i];
+    *nodes = sd->textures.data(); *n_nodes = unsigned(sd->textures.size());
+    *mats = sd->material_textures.data(); *n_mats = unsigned(sd->material_textures.size());
+    return sd->has_textures ? 1 : 0;
+}
+const char *pbrt_host_texture_name(PbrtHostScene *h, int i, unsigned node) {
+    const SceneDescription *sd = h->api.frames[i];
+    return node < sd->texture_names.size() ? sd->texture_names[node].c_str() : "";
+}
+// host evaluation of node `node` at (p, u, v): its post-order program run by rt_texture_eval_program, the function the device runs.
+// Returns 0, or -1 for a bad index or a graph beyond the limits of rt_scene_set_textures.
+int pbrt_host_texture_eval(PbrtHostScene *h, int i, unsigned node, const float *p, float u, float v, float *out3) {
+    const SceneDescription *sd = h->api.frames[i];
+    if (node >= sd->textures.size()) return -1;
+    std::vector<int32_t> prog;
+    struct Walk {
+        static int go(const std::vector<RtTexture> &t, int n, std::vector<int32_t> &out) {      // returns the stack the subtree needs
+            int need = 1, held = 0;
+            for (int c = 0; c < 3; ++c) if (t[n].child[c] >= 0) { const int k = go(t, t[n].child[c], out); need = std::max(need, held + k); ++held; }
+            out.push_back(n);
+            return need;
+        }
+    };
+    const int need = Walk::go(sd->textures, int(node), prog);
+    if (need > RT_TEX_MAX_STACK || prog.size() > size_t(RT_TEX_MAX_PROGRAM)) return -1;
+    RtTexHit hit; hit.p[0] = p[0]; hit.p[1] = p[1]; hit.p[2] = p[2]; hit.u = u; hit.v = v;
+    for (int ch = 0; ch < 3; ++ch) out3[ch] = rt_texture_eval_program(sd->textures.data(), prog.data(), int(prog.size()), &hit, ch);
+    return 0;
+}
+// the per-hit resolve on the host: parameters -> RtMaterial -> the record the kernels read
+void pbrt_host_material_resolve(const RtMaterialParams *p, RtMaterial *m, RtMaterialResolved *r) { rt_material_from_params(p, m); rt_material_resolve(m, r); }
 // canonical byte image of a frame's descriptors (include/pbrt_hip_desc.h); returns the size, writes when the buffer is large enough
 long long pbrt_host_serialize(PbrtHostScene *h, int i, unsigned char *out, long long cap) {
     const size_t n = rt_desc_serialize(&h->api.frames[i]->scene, &h->api.frames[i]->render, nullptr);

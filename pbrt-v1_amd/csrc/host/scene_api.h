@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../../include/pbrt_hip.h"
+#include "../../../include/pbrt_hip_texture.h"
 #include "host_math.h"
 #include "paramset.h"
 
@@ -48,6 +49,9 @@ struct SceneDescription {
     std::vector<int32_t> tri_shading; std::vector<RtTriShading> shading; std::vector<float> xforms;   // per-vertex uv / N / S (trianglemesh)
     RtSceneDesc scene; RtRenderDesc render;
     RtDensityRegion density; std::vector<float> density_values;   // the medium's DensityRegion (kind RT_DENSITY_NONE: none), rt_scene_set_density
+    // textured material parameters (rt_scene_set_textures): the node table (children before parents; the name a Texture statement gave a node, "" for a
+    // literal sub-texture) and one record per material.  has_textures: some material has a textured slot -- otherwise nothing is handed over
+    std::vector<RtTexture> textures; std::vector<std::string> texture_names; std::vector<RtMaterialTextures> material_textures; bool has_textures = false;
     Film film;
     bool valid = false;
     void finalize_pointers();
@@ -113,8 +117,9 @@ class PbrtApi : public DirectiveSink {
     Named filterOpt, filmOpt, samplerOpt, accelOpt, surfOpt, volOpt, cameraOpt;
     Xform worldToCamera;
     struct GraphicsState {
-        std::map<std::string, float> floatTextures;            // constant textures only (texture.h:113-123)
+        std::map<std::string, float> floatTextures;            // constant textures (texture.h:113-123): folded to their value
         std::map<std::string, Float3> spectrumTextures;
+        std::map<std::string, int> floatTexNodes, spectrumTexNodes;   // every other class: index into PbrtApi::texNodes (a name lives in one of the two maps of its type)
         ParamSet materialParams; std::string material = "matte";
         ParamSet areaLightParams; std::string areaLight;
         bool reverseOrientation = false;
@@ -129,12 +134,17 @@ class PbrtApi : public DirectiveSink {
     std::vector<RtMaterial> materials; std::vector<RtLight> lights; std::vector<float> light_tris;
     RtVolume volume; int nVolumes;
     RtDensityRegion density; std::vector<float> densityValues;
+    std::vector<RtTexture> texNodes; std::vector<std::string> texNames; std::vector<RtMaterialTextures> materialTextures;
     bool inObject;
     bool verifyOptions(const char *fn); bool verifyWorld(const char *fn);
     int makeMaterial(const ParamSet &shapeParams);
     void quadricShape(const std::string &name, const ParamSet &ps);
-    Float3 spectrumParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, Float3 d);
-    float floatParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, float d);
+    // TextureParams::GetSpectrumTexture / GetFloatTexture (paramset.cpp:434-465): the value, and in *node the texture node that replaces it per hit (-1: a constant)
+    Float3 spectrumParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, Float3 d, int *node = nullptr);
+    float floatParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, float d, int *node = nullptr);
+    int constantNode(bool color, Float3 v);
+    int subTexture(const ParamSet &ps, const std::string &n, bool color, float d);
+    bool textureMapping(const ParamSet &ps, RtTexture &t);
     void resetWorld();
 };
 

@@ -4,7 +4,7 @@
 
 The frame is the Cornell box plus the 1 M-triangle soup of bench.py's workloads, path tracing (maxdepth 5), N x N pixels (default 1024)
 at S x S jittered samples (default 2 x 2).  `plastic`: every soup triangle is plastic (the EXT kernels with the materials they had before);
-`mixed`: the soup's triangles cycle through shinymetal, translucent and matte (triangle index modulo 3); `plastic_infinite`: the plastic frame with
+`plastic_checker`: the same with a checkered Kd; `mixed`: the soup's triangles cycle through shinymetal, translucent and matte (triangle index modulo 3); `plastic_infinite`: the plastic frame with
 the box's emitter replaced by an infinite light.  Each frame is rendered once with
 the counting kernels (the ray count) and then with the timed kernels; one JSON line per frame gives the GPU milliseconds of every step
 (rt_last_render_stats), their median and Mrays/s at the median.  To compare two builds of the device library, run it once per library
@@ -24,6 +24,9 @@ import __graft_entry__ as g  # noqa: E402
 
 MATERIALS = {
     "plastic": ['Material "plastic" "color Kd" [.5 .45 .4] "color Ks" [.4 .4 .4] "float roughness" [.15]'],
+    # the plastic frame with Kd from a checkerboard over every triangle's default uvs: evaluated and resolved per hit
+    "plastic_checker": ['Texture "chk" "color" "checkerboard" "color tex1" [.5 .45 .4] "color tex2" [.2 .3 .5] "string aamode" ["none"] "float uscale" [4] "float vscale" [4]\n'
+                        '  Material "plastic" "texture Kd" "chk" "color Ks" [.4 .4 .4] "float roughness" [.15]'],
     "mixed": ['Material "shinymetal" "color Ks" [.8 .7 .4] "color Kr" [.7 .7 .7] "float roughness" [.15]',
               'Material "translucent" "color Kd" [.6 .7 .5] "color Ks" [.3 .3 .3] "float roughness" [.15]',
               'Material "matte" "color Kd" [.6 .55 .5]'],
