@@ -602,11 +602,11 @@ int rt_film_bind(RtScene *s, void *device_accum, int32_t w, int32_t h) {
     if (!s || w < 1 || h < 1) return fail(RT_EINVAL, "rt_film_bind: bad argument");
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipStreamSynchronize(s->stream));                  // a frame may still be accumulating into the film being replaced
-    if (s->own_accum && s->accum) { HIPWARN(hipFree(s->accum)); s->accum = nullptr; }
-    s->film_w = w; s->film_h = h;
-    if (device_accum) { s->accum = static_cast<float *>(device_accum); s->own_accum = false; }
-    else {
-        HIPCHK(hipMalloc((void **)&s->accum, size_t(5) * w * h * sizeof(float))); s->own_accum = true;
+    s->own_accum.reset();
+    s->film_w = w; s->film_h = h; s->accum = static_cast<float *>(device_accum);
+    if (!device_accum) {
+        if (int rc = s->own_accum.grow(size_t(5) * w * h)) return rc;
+        s->accum = s->own_accum;
         HIPCHK(hipMemsetAsync(s->accum, 0, size_t(5) * w * h * sizeof(float), s->stream));   // ordered before the first gather on this stream
     }
     return RT_OK;
@@ -631,10 +631,7 @@ int rt_film_resolve(RtScene *s, int premultiply, float *rgb_out, float *alpha_ou
     if (!s->accum) return fail(RT_ESTATE, "no film bound");
     HIPCHK(hipSetDevice(s->device));
     const size_t n = size_t(s->film_w) * s->film_h;
-    if (s->resolve_cap < n) {
-        if (s->resolve_buf) HIPWARN(hipFree(s->resolve_buf));
-        HIPCHK(hipMalloc((void **)&s->resolve_buf, n * 4 * sizeof(float))); s->resolve_cap = n;
-    }
+    if (int rc = ensure(s, s->resolve_buf, n * 4)) return rc;
     hipLaunchKernelGGL(film_resolve_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s->stream, s->accum, n, premultiply,
                        s->resolve_buf, s->resolve_buf + 3 * n);
     HIPCHK(hipGetLastError());
@@ -688,14 +685,13 @@ int rt_samples_read(RtScene *s, uint64_t first, uint64_t count, float *out) {
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (count == 0) return RT_OK;
-    float4 *tmp = nullptr;
-    HIPCHK(hipMalloc((void **)&tmp, size_t(count) * 2 * sizeof(float4)));
+    DevBuf<float4> tmp;
+    if (int rc = tmp.grow(size_t(count) * 2)) return rc;
     hipLaunchKernelGGL(samples_unpack_kernel, dim3(unsigned((count + 255) / 256)), dim3(256), 0, s->stream, (const float4 *)s->samples,
-                       (unsigned long long)first, (unsigned long long)count, s->samples_spp, tmp);
+                       (unsigned long long)first, (unsigned long long)count, s->samples_spp, tmp.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e == hipSuccess) e = hipMemcpy(out, tmp, size_t(count) * 2 * sizeof(float4), hipMemcpyDeviceToHost);
-    HIPWARN(hipFree(tmp));
     if (e != hipSuccess) return fail(RT_EDEVICE, std::string("rt_samples_read: ") + hipGetErrorString(e));
     return RT_OK;
 }

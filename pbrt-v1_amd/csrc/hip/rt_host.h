@@ -1,5 +1,5 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
-// device-buffer helpers.  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
+// the owners of its device memory, events and stream.  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
 // rt_kernels.hip renders (make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
 #include "rt_render_kernel.h"
@@ -8,6 +8,7 @@
 #include "rt_pipe_march.h"
 #include "rt_bidir.h"
 #include "rt_internal.h"
+#include "rt_devbuf.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +18,7 @@
 #include <chrono>
 #include <atomic>
 #include <thread>
+#include <type_traits>
 
 namespace rt {
 // Experiment / test knobs (PBRT_HIP_*: kernel flavour, pipeline form, film-gather kernel, layout switches, logs) are read only when
@@ -51,99 +53,115 @@ static inline RenderKernelFn render_kernel_of(int variant) {
     return t[variant < 24 ? variant / 3 : variant < 36 ? 8 + (variant - 24) / 3 : 12 + (variant - 36) / 3];
 }
 
+// ---- owners (rt_devbuf.h).  A device block is a DevBuf<T>; the same template with another release function owns page-locked memory, an event and the
+// stream a scene created itself.  rt_kernels.hip defines the release functions, next to rt::dev_alloc / rt::dev_free.
+namespace rt { void host_free(void *p); void event_free(void *e); void stream_free(void *st); }
+template <class T> using Pinned = rt::DevBuf<T, rt::host_free>;
+using Event = rt::DevBuf<std::remove_pointer_t<hipEvent_t>, rt::event_free>;
+using OwnedStream = rt::DevBuf<std::remove_pointer_t<hipStream_t>, rt::stream_free>;
+
+// The slot-indexed planes of the queue pipeline's pool (rt_pipeline.h PipePool is the kernels' view of them, filled once per frame).  each() is the
+// ONE list of their elements per slot: the allocation sizes, the per-slot cost and what the pool holds (render_pipeline's memory budget) all walk it.
+struct PipePlanes {
+    DevBuf<float4> state, ray_o, hit, q_o; DevBuf<unsigned> q_slot;
+    template <class F> void each(F &&f) { f(state, size_t(RT_PIPE_VEC)); f(ray_o, size_t(2)); f(hit, size_t(3)); f(q_o, size_t(4)); f(q_slot, size_t(3)); }   // hit: [kind][slot] in the by-vertex form
+};
+
+// Members are destroyed in reverse order of declaration: every buffer, then the events, then the stream (rt_scene_destroy has synchronised it).
 struct RtScene {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    hipStream_t stream = nullptr;      // what every call uses: own_stream's, or the caller's (rt_scene_set_stream: not destroyed with the scene)
+    OwnedStream own_stream;
+    Event ev0, ev1, ev2;
+    Event wt_ev[6];
+    std::vector<Event> pipe_ev;                         // [6 * RT_PIPE_TIMED]: per iteration, around the trace, the shade and the march launch
+    std::vector<Event> pipe_fence;
     KdTree tree;
     GridAccelData gridacc;
     int accel_kind = RT_ACCEL_KDTREE;
     double per_leaf = -1.0;             // average primitives per non-empty kd leaf (traversal heuristics), computed on first use
     bool has_ext = false;               // plastic materials or quadrics present: use the kernels that carry that code (EXT)
     DevScene dev{};
-    std::vector<void *> allocs;
+    std::vector<DevBuf<char>> allocs;   // what was uploaded once and lives as long as the scene (scene_alloc)
     // film
-    float *accum = nullptr; bool own_accum = false; int film_w = 0, film_h = 0;
-    float *filter_dev = nullptr;
+    float *accum = nullptr; DevBuf<float> own_accum; int film_w = 0, film_h = 0;      // accum: own_accum's block, or the caller's (rt_film_bind)
+    DevBuf<float> filter_dev;
     // per-launch scratch
-    unsigned long long *work_counter = nullptr, *counters = nullptr;
-    uint2 *spill = nullptr; size_t spill_entries = 0;
-    float *frames = nullptr; size_t frames_floats = 0;
+    DevBuf<unsigned long long> work_counter, counters;
+    DevBuf<uint2> spill;
+    DevBuf<float> frames;
     unsigned grid = 0, n_threads = 0;
     unsigned grids[48] = {0};          // resident grid per render_kernel<COUNT, INTEG> instantiation
     unsigned wgrids[8] = {0};          // ... of the DirectLighting "weighted" family (rt_mega_dw.hip)
     unsigned bgrids[4] = {0};          // ... of the bidirectional integrator's (rt_mega_b.hip)
-    DimReq *light_dims = nullptr; size_t light_dims_cap = 0;      // DirectLighting "all": the per-light sample requests (make_frame); the bidirectional integrator: its BidirTable
+    DevBuf<DimReq> light_dims;         // DirectLighting "all": the per-light sample requests (make_frame); the bidirectional integrator: its BidirTable
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
-    unsigned *wt_recbase = nullptr; size_t wt_recbase_cap = 0;
+    DevBuf<unsigned> wt_recbase;
     unsigned n_infinite = 0;           // RT_LIGHT_INFINITE lights (each estimate draws one RandomFloat(), infinite.cpp:104: refused with strategy "weighted")
     int light_draws = 0;               // RandomFloat()s one EstimateDirect draws: the same for every light (0 / 1), or -1 when the lights differ
-    unsigned *wt_base = nullptr; size_t wt_base_cap = 0; float *wt_rec = nullptr; size_t wt_rec_cap = 0; float2 *wt_pick = nullptr; size_t wt_pick_cap = 0;
-    unsigned long long *wt_sums = nullptr;                     // per-block sums of the point-count scan
-    unsigned long long *wt_total = nullptr;                    // page-locked: the frame's shading points (weighted_scan_top_kernel)
+    DevBuf<unsigned> wt_base; DevBuf<float> wt_rec; DevBuf<float2> wt_pick;
+    DevBuf<unsigned long long> wt_sums;                        // per-block sums of the point-count scan
+    Pinned<unsigned long long> wt_total;                       // page-locked: the frame's shading points (weighted_scan_top_kernel)
     unsigned long long wt_points = 0; bool last_weighted = false;
-    hipEvent_t wt_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevScene *dev_scene = nullptr; DevFrame *dev_frame = nullptr;   // descriptors in HBM (read with scalar loads)
-    float4 *samples = nullptr; size_t samples_cap = 0;          // per-shard sample buffer
+    DevBuf<DevScene> dev_scene; DevBuf<DevFrame> dev_frame;     // descriptors in HBM (read with scalar loads)
+    DevBuf<float4> samples;                                    // per-shard sample buffer
     int samples_spp = 1;
     unsigned long long samples_last = 0;                       // camera samples the LAST rt_render wrote (rt_samples_read's range)
-    float ms_render = 0.f, ms_gather = 0.f; hipEvent_t ev2 = nullptr;
-    float *resolve_buf = nullptr; size_t resolve_cap = 0;
-    float *vol_buf = nullptr; size_t vol_cap = 0;          // volume scratch: rays | state | samp
+    DevBuf<float> resolve_buf;
+    DevBuf<float> vol_buf;                                 // volume scratch: rays | state | samp
     RtVolume volume{};
     int density_kind = RT_DENSITY_NONE;                    // rt_scene_set_density
     double vol_world[6] = {0, 0, 0, 0, 0, 0};             // density region: the volume's world bound (WorldToVolume^-1 of its extent)
     bool rendered = false;                                 // an rt_render has been accepted
     // textured materials (rt_scene_set_textures): the scene's own resolved records (host copy) and the device array that holds them followed by
-    // mat_pool_cap records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
+    // the records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
     std::vector<DevMaterial> materials_host;
     std::vector<int> tex_uv_idx_host; std::vector<float> tex_uv_host;   // uvs of the triangles whose mesh has "uv" ([n_tris] index or -1, 6 floats each): host only until rt_scene_set_textures
     bool has_textures = false;
-    DevMaterial *mat_buf = nullptr; size_t mat_pool_cap = 0;
+    DevBuf<DevMaterial> mat_buf;
     int spill_depth = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_timing = false;
     bool counting = true;
     uint32_t n_tris = 0;
-    size_t n_leaf_tri_units = 0, n_leaf_entries = 0;
     // queue pipeline (rt_pipeline.h)
-    PipePool pool{}; unsigned pool_cap = 0; int pool_vec = 0; PipePool *dev_pool = nullptr;
-    unsigned *h_qcount = nullptr;                       // page-locked mirror of pool.q_count (termination test)
+    PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
+    Pinned<unsigned> h_qcount;                          // page-locked mirror of q_count (termination test)
     unsigned trace_grids[8] = {0}, march_grids[6] = {0};
-    std::vector<hipEvent_t> pipe_ev;                    // [6 * RT_PIPE_TIMED]: per iteration, around the trace, the shade and the march launch
-    std::vector<hipEvent_t> pipe_fence;
     bool last_pipeline = false, last_marches = false; int pipe_iters = 0, pipe_timed = 0; unsigned pipe_slots = 0;
-    float4 *trace_buf = nullptr; size_t trace_cap = 0;   // rt_trace_*: rays (2 x float4) and hits, reused across calls
+    DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;
-    unsigned *trace_qc = nullptr;
+    DevBuf<unsigned> trace_qc;
 };
 #define RT_PIPE_QN 4096          // ring of per-iteration queue counters
 #define RT_PIPE_TIMED 256        // iterations whose trace launch is bracketed by events
 #define RT_PIPE_BATCH 4          // iterations launched between two termination checks
 
+// a device block that lives as long as the scene
+static inline int scene_alloc(RtScene *s, size_t bytes, void **p) {
+    DevBuf<char> b;
+    if (int rc = b.grow(bytes)) return rc;
+    *p = b.p; s->allocs.push_back(std::move(b));
+    return RT_OK;
+}
 template <class T>
 static inline int upload(RtScene *s, const T *host, size_t n, const T **dev) {
     void *p = nullptr;
-    size_t bytes = (n ? n : 1) * sizeof(T);
-    HIPCHK(hipMalloc(&p, bytes));
-    s->allocs.push_back(p);
+    if (int rc = scene_alloc(s, (n ? n : 1) * sizeof(T), &p)) return rc;
     if (n) HIPCHK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
     *dev = static_cast<const T *>(p);
     return RT_OK;
 }
 
-// scenes with textures: room for `levels` resolved materials per thread / slot behind the scene's own (fr.mat_pool_base, fr.n_threads); rt_scene.hip
+// scenes with textures: room for `levels` resolved materials per thread / slot behind the scene's own (fr.mat_pool_base); rt_scene.hip
 int ensure_material_pool(RtScene *s, rt::DevFrame &fr, size_t levels, size_t n_slots);
 
-// (re)allocate a scratch buffer that is only ever used inside one rt_render call
+// (re)allocate a scratch buffer that work queued on the scene's stream may still be using: wait for the stream before the old block goes
 template <class T>
-static inline int ensure(RtScene *s, T **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return RT_OK;
-    if (*buf) { HIPCHK(hipStreamSynchronize(s->stream)); HIPWARN(hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    HIPCHK(hipMalloc((void **)buf, need * sizeof(T)));
-    *cap = need;
-    return RT_OK;
+static inline int ensure(RtScene *s, DevBuf<T> &b, size_t need) {
+    if (need <= b.cap) return RT_OK;
+    if (b.p) HIPCHK(hipStreamSynchronize(s->stream));
+    return b.grow(need);
 }
 
 // No C++ exception crosses the C boundary: the host builders allocate gigabytes and start worker threads (every group of them is joined while the

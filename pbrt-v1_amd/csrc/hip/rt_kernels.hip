@@ -45,28 +45,64 @@ const char *last_error() { return g_err.c_str(); }
 void hip_warn(hipError_t e, const char *what) {
     if (e != hipSuccess) std::fprintf(stderr, "libpbrt_hip: %s failed: %s\n", what, hipGetErrorString(e));
 }
+// what the owners of rt_devbuf.h / rt_host.h allocate and release through
+int dev_alloc(void **p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return RT_OK;
+    *p = nullptr;
+    return fail(RT_EDEVICE, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+}
+void dev_free(void *p) { HIPWARN(hipFree(p)); }
+void host_free(void *p) { HIPWARN(hipHostFree(p)); }
+void event_free(void *e) { HIPWARN(hipEventDestroy(static_cast<hipEvent_t>(e))); }
+void stream_free(void *st) { HIPWARN(hipStreamDestroy(static_cast<hipStream_t>(st))); }
 }  // namespace rt
+
+// The scratch of the state machine per thread (megakernel) or slot (pipeline), in words: recursion frames (whitted / directlighting; the bidirectional
+// integrator: its path vertices), the medium's [vol_levels x 8 rays | 13 state | the single-scattering march samples], and the levels of materials
+// resolved per hit (rt_texture.h).  fr.vol_nmax is what rt_render's validation found.
+struct ScratchWords { size_t frame = 0, vol_levels = 0, vol = 0, mat_levels = 0; };
+static ScratchWords scratch_words(const RtScene *s, const RtRenderDesc *rd, const DevFrame &fr) {
+    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL, path = rd->integrator == RT_INTEGRATOR_PATH;
+    ScratchWords w;
+    w.frame = bidir ? size_t(RT_BD_FRAME_WORDS) : path ? 0 : size_t(rd->max_depth + 2) * RT_FRAME_WORDS;
+    w.mat_levels = bidir ? size_t(2 * RT_BD_MAX_VERTS) : path ? 1 : size_t(rd->max_depth + 2);
+    if (s->volume.present) {
+        w.vol_levels = path ? 1 : size_t(rd->max_depth + 2);
+        w.vol = w.vol_levels * 8 + 13 + (rd->volume_integrator == RT_VOLUME_SINGLE ? size_t(3) * fr.vol_nmax : 0);
+    }
+    return w;
+}
+// ... grown for n threads / slots and bound to the frame
+static int bind_scratch(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, size_t n) {
+    const ScratchWords w = scratch_words(s, rd, fr);
+    int rc;
+    if ((rc = ensure(s, s->frames, w.frame * n))) return rc;
+    if ((rc = ensure(s, s->vol_buf, w.vol * n))) return rc;
+    fr.frames = s->frames; fr.n_threads = unsigned(n);
+    if (w.vol) { fr.vol_rays = s->vol_buf; fr.vol_state = fr.vol_rays + w.vol_levels * 8 * n; fr.vol_samp = fr.vol_state + size_t(13) * n; }
+    return ensure_material_pool(s, fr, w.mat_levels, n);
+}
 
 // The queue pipeline: alternate a shade kernel (pipe_shade_kernel, or pipe_vertex_kernel for a path without a medium) and pipe_trace_kernel
 // until a shade pass enqueues no ray.  The host learns the queue sizes RT_PIPE_BATCH iterations late (page-locked copy + fence event per
 // batch), so the GPU never waits for it; the iterations launched after the last productive one find every slot in ST_EXIT and return at once.
-static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int vol_levels, int vol_nmax, size_t vol_samp_words) {
+static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     const int integ = rd->integrator;
     // PathIntegrator without a medium: one shade pass per path vertex, all of a vertex's rays in one trace launch (rt_pipe_vertex.h)
     bool by_vertex = integ == RT_INTEGRATOR_PATH && !s->volume.present;
     if (const char *e = knob("PBRT_HIP_PIPE_VERTEX")) by_vertex = by_vertex && std::atoi(e) != 0;
     // ---- pool size: 32 M slots with a medium, 8 M without, unless the frame is smaller or the per-slot scratch would not fit (a fine ray march: 3 floats per step)
-    const size_t frame_words = integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) * RT_FRAME_WORDS : 0;
-    const size_t vol_words = s->volume.present ? size_t(vol_levels) * 8 + 13 + vol_samp_words : 0;
-    const size_t mat_bytes = s->has_textures ? (integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1) * sizeof(DevMaterial) : 0;   // the materials resolved per hit
-    const size_t slot_bytes = size_t(RT_PIPE_VEC) * 16 + 2 * 16 + 3 * 16 + 4 * 16 + 3 * 4 + (frame_words + vol_words) * 4 + mat_bytes;
+    const ScratchWords w = scratch_words(s, rd, fr);
+    size_t slot_bytes = (w.frame + w.vol) * 4 + (s->has_textures ? w.mat_levels * sizeof(DevMaterial) : 0);   // ... and the materials resolved per hit
+    size_t held = s->frames.bytes() + s->vol_buf.bytes();                        // what this scene's pool already holds
+    s->pool.each([&](auto &b, size_t per_slot) { slot_bytes += per_slot * sizeof(*b.p); held += b.bytes(); });
     // (C5, 64 spp with a march per ray: 8 M slots 329 ms, 16 M 311, 32 M 289, 48 M 312, 64 M 326 -- fewer, fuller iterations until the shade passes' state
     // traffic takes over; the by-vertex path frame on the 1 M tree: 8 M 70.6 ms, 16 M 72.1; profiles/r03_c5_knobs.txt)
     unsigned want = s->volume.present ? 1u << 25 : 1u << 23;
     {
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t held = size_t(s->pool_cap) * (size_t(RT_PIPE_VEC) * 16 + 9 * 16 + 12) + (s->frames_floats + s->vol_cap) * 4;   // what this scene's pool already holds
         size_t budget = (free_b + held) / 2;                                      // leave half of what is free to the caller (film, other scenes)
         if (const char *e = knob("PBRT_HIP_PIPE_MEM_MB")) budget = size_t(std::max(1, std::atoi(e))) << 20;      // tests: a small budget
         if (slot_bytes * want > budget) want = unsigned(std::max<size_t>(budget / slot_bytes, 2 * RT_BLOCK));
@@ -76,40 +112,21 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
     unsigned n_slots = unsigned(std::min<unsigned long long>(want, tw));
     n_slots = (n_slots + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK;
     if (n_slots >= (1u << 30)) return fail(RT_EINVAL, "rt_render: more than 2^30 pipeline slots");
-    const int vec = RT_PIPE_VEC;
-    if (n_slots > s->pool_cap) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPWARN(hipFree(s->pool.state)); HIPWARN(hipFree(s->pool.ray_o)); HIPWARN(hipFree(s->pool.hit)); HIPWARN(hipFree(s->pool.q_o)); HIPWARN(hipFree(s->pool.q_slot));
-        { unsigned *qc = s->pool.q_count; unsigned long long *ww = s->pool.wave_work; s->pool = PipePool{}; s->pool.q_count = qc; s->pool.wave_work = ww; }
-        s->pool_cap = 0;
-        HIPCHK(hipMalloc((void **)&s->pool.state, size_t(vec) * n_slots * sizeof(float4)));
-        HIPCHK(hipMalloc((void **)&s->pool.ray_o, size_t(2) * n_slots * sizeof(float4)));
-        HIPCHK(hipMalloc((void **)&s->pool.hit, size_t(3) * n_slots * sizeof(float4)));              // [kind][slot] in the by-vertex form
-        HIPCHK(hipMalloc((void **)&s->pool.q_o, size_t(4) * n_slots * sizeof(float4)));
-        HIPCHK(hipMalloc((void **)&s->pool.q_slot, size_t(3) * n_slots * sizeof(unsigned)));
-        HIPWARN(hipFree(s->pool.wave_work)); s->pool.wave_work = nullptr;
-        HIPCHK(hipMalloc((void **)&s->pool.wave_work, size_t(n_slots / 64 + 1) * 2 * sizeof(unsigned long long)));
-        s->pool_cap = n_slots;
-    }
-    if (!s->pool.q_count) HIPCHK(hipMalloc((void **)&s->pool.q_count, size_t(RT_PIPE_QN) * RT_QC_STRIDE * sizeof(unsigned)));
-    PipePool pl = s->pool;
-    pl.n_slots = n_slots; pl.ray_d = pl.ray_o + n_slots; pl.q_d = pl.q_o + size_t(2) * n_slots; pl.q_march = pl.q_slot + size_t(2) * n_slots;
+    int rc = RT_OK;
+    s->pool.each([&](auto &b, size_t per_slot) { if (!rc) rc = ensure(s, b, per_slot * n_slots); });
+    if (!rc) rc = ensure(s, s->wave_work, size_t(n_slots / 64 + 1) * 2);
+    if (!rc) rc = s->q_count.grow(size_t(RT_PIPE_QN) * RT_QC_STRIDE);
+    if (rc) return rc;
+    PipePool pl{};                                                          // the kernels' view of the pool
+    pl.n_slots = n_slots; pl.state = s->pool.state; pl.hit = s->pool.hit; pl.q_count = s->q_count; pl.wave_work = s->wave_work;
+    pl.ray_o = s->pool.ray_o; pl.ray_d = pl.ray_o + n_slots; pl.q_o = s->pool.q_o; pl.q_d = pl.q_o + size_t(2) * n_slots;
+    pl.q_slot = s->pool.q_slot; pl.q_march = pl.q_slot + size_t(2) * n_slots;
     if (by_vertex) pl.ray_d = pl.q_o;                                       // directions [3][n_slots] (the compacted ray copies are not used)
-    // per-slot scratch of the state machine: recursion frames (whitted / directlighting), volume march state
-    if (integ != RT_INTEGRATOR_PATH) {
-        int rc = ensure(s, &s->frames, &s->frames_floats, frame_words * n_slots); if (rc) return rc;
-    }
-    if (s->volume.present) {
-        int rc = ensure(s, &s->vol_buf, &s->vol_cap, vol_words * n_slots); if (rc) return rc;
-        fr.vol_rays = s->vol_buf; fr.vol_state = s->vol_buf + size_t(vol_levels) * 8 * n_slots;
-        fr.vol_samp = fr.vol_state + size_t(13) * n_slots; fr.vol_nmax = vol_nmax;
-    }
-    fr.frames = s->frames; fr.n_threads = n_slots;
-    { int rc = ensure_material_pool(s, fr, integ != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1, n_slots); if (rc) return rc; }   // scenes with textures (rt_texture.h)
+    if ((rc = bind_scratch(s, rd, fr, n_slots))) return rc;
     if (s->pipe_ev.empty()) {
         s->pipe_ev.resize(6 * RT_PIPE_TIMED); s->pipe_fence.resize(RT_PIPE_QN / RT_PIPE_BATCH);
-        for (auto &e : s->pipe_ev) HIPCHK(hipEventCreate(&e));
-        for (auto &e : s->pipe_fence) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : s->pipe_ev) HIPCHK(hipEventCreate(&e.p));
+        for (auto &e : s->pipe_fence) HIPCHK(hipEventCreateWithFlags(&e.p, hipEventDisableTiming));
     }
     const int f = s->counting ? 1 : (s->has_ext ? 2 : 0);
     const PipeShadeFn *st = integ == RT_INTEGRATOR_WHITTED ? g_pipe_shade_whitted : integ == RT_INTEGRATOR_DIRECT ? g_pipe_shade_direct : g_pipe_shade_path;
@@ -177,10 +194,8 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, int
 }
 
 // The bidirectional integrator: rt::bidir_kernel (rt_bidir.h), k = ACCEL*2 + COUNT, with the eight path vertices of every thread in s->frames
-static int render_bidir(RtScene *s, DevFrame &fr) {
-    int rc = ensure(s, &s->frames, &s->frames_floats, size_t(RT_BD_FRAME_WORDS) * s->n_threads); if (rc) return rc;
-    fr.frames = s->frames;
-    rc = ensure_material_pool(s, fr, 2 * RT_BD_MAX_VERTS, s->n_threads); if (rc) return rc;
+static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+    int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
     const int bk = (s->accel_kind == RT_ACCEL_GRID ? 2 : 0) + (s->counting ? 1 : 0);
     if (s->bgrids[bk] == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
     HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
@@ -313,7 +328,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
         }
         std::vector<DimReq> &up = s->light_dims_host;          // what the device holds: uploaded again only when a frame asks for other requests
         if (!s->light_dims || up.size() != tab.size() || std::memcmp(up.data(), tab.data(), tab.size() * sizeof(DimReq)) != 0) {
-            int rc = ensure(s, &s->light_dims, &s->light_dims_cap, tab.size()); if (rc) return rc;
+            int rc = ensure(s, s->light_dims, tab.size()); if (rc) return rc;
             up.swap(tab);
             // rt_render is asynchronous: a frame queued earlier may still be reading the table, and the source is pageable host memory that the next make_frame
             // may swap away -- wait for the stream, then copy synchronously (36 bytes per light; only when a frame asks for other requests than the last one)
@@ -404,14 +419,13 @@ int rt_camera_rays(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t 
     if (!s || !rd || !rays_out) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
     DevFrame fr; int rc = make_frame(s, rd, fr, false); if (rc) return rc;
-    RtRay *dev = nullptr;
-    HIPCHK(hipMalloc((void **)&dev, size_t(count ? count : 1) * sizeof(RtRay)));
+    DevBuf<RtRay> dev;
+    if ((rc = dev.grow(count ? count : 1))) return rc;
     hipLaunchKernelGGL(camera_kernel, dim3((count + 255) / 256), dim3(256), 0, s->stream, s->dev, fr,
-                       (unsigned long long)first, count, dev);
+                       (unsigned long long)first, count, dev.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(rays_out, dev, size_t(count) * sizeof(RtRay), hipMemcpyDeviceToHost));
-    HIPWARN(hipFree(dev));
     return RT_OK;
 }
 
@@ -421,10 +435,7 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
     if (!s || !rays || (!hits && !occ)) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
     if (n == 0) return RT_OK;
-    if (size_t(n) > s->trace_cap) {
-        if (s->trace_buf) { HIPCHK(hipStreamSynchronize(s->stream)); HIPWARN(hipFree(s->trace_buf)); s->trace_buf = nullptr; s->trace_cap = 0; }
-        HIPCHK(hipMalloc((void **)&s->trace_buf, size_t(n) * 3 * sizeof(float4))); s->trace_cap = n;
-    }
+    if (int rc = ensure(s, s->trace_buf, size_t(n) * 3)) return rc;
     std::vector<float4> host(size_t(n) * 2);
     for (uint32_t i = 0; i < n; ++i) {
         host[i] = make_float4(rays[i].o[0], rays[i].o[1], rays[i].o[2], rays[i].mint);
@@ -489,7 +500,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     }
     const bool skip_film = knob("PBRT_HIP_DEBUG_NOFILM") != nullptr;   // perf experiments only
     FilmGather fg; rc = film_gather_plan(s, fr, fg); if (rc) return rc;
-    int vol_levels = 0, vol_nmax = 0; size_t vol_samp_words = 0;
+    int vol_nmax = 0;
     fr.dens_cap = 0;
     if (s->volume.present) {
         if (!(rd->step_size > 0.f)) return fail(RT_EINVAL, "rt_render: volume integrator stepsize must be positive");
@@ -526,41 +537,30 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
             vol_nmax = std::max(vol_nmax, int(std::ceil(wdiag / rd->step_size)) + 2);     // march steps along a world-space ray (a scaled volume)
             if (vol_nmax > 65536) return fail(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
         }
-        vol_levels = (rd->integrator == RT_INTEGRATOR_PATH) ? 1 : rd->max_depth + 2;
-        vol_samp_words = rd->volume_integrator == RT_VOLUME_SINGLE ? size_t(3) * vol_nmax : 0;
+        fr.vol_nmax = vol_nmax;                                  // (bind_scratch sizes the march samples from it)
     }
     // ---- scratch
     {
-        size_t cap = s->samples_cap;
+        const size_t cap = s->samples.cap;
         const size_t local_pixels = size_t(fr.total_work / fr.spp);                     // sample_slot(): whole 64-pixel chunks
         const size_t need = ((local_pixels + 63) / 64 * 64 + 64) * size_t(fr.spp) * 2;
-        rc = ensure(s, &s->samples, &cap, need); if (rc) return rc;
+        rc = ensure(s, s->samples, need); if (rc) return rc;
         // A fresh buffer is zeroed once: the film gathers weigh the records of lanes without a column of their own (film_march_kernel: record 0)
         // and of dropped border items with +0, which is only a zero if the record is finite -- from here on sample_write keeps it so; a rank
         // that owns no tile at all writes nothing, ever.  For dropped items rt_samples_read returns zeros or what an earlier frame left there.
-        if (cap != s->samples_cap) HIPCHK(hipMemsetAsync(s->samples, 0, cap * sizeof(float4), s->stream));
-        s->samples_cap = cap;
+        if (cap != s->samples.cap) HIPCHK(hipMemsetAsync(s->samples, 0, s->samples.bytes(), s->stream));
     }
     fr.samples = s->samples; s->samples_last = fr.total_work; s->samples_spp = fr.spp;
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
     s->rendered = true;
     if (fr.pipeline) {
-        rc = render_pipeline(s, rd, fr, vol_levels, vol_nmax, vol_samp_words); if (rc) return rc;
+        rc = render_pipeline(s, rd, fr); if (rc) return rc;
         s->last_weighted = false;
     } else if (bidir) {                                       // a kernel family of its own, ahead of the variant arithmetic of the three megakernel integrators
-        rc = render_bidir(s, fr); if (rc) return rc;
+        rc = render_bidir(s, rd, fr); if (rc) return rc;
     } else {
-        if (rd->integrator != RT_INTEGRATOR_PATH) {           // recursion frames for whitted / directlighting
-            rc = ensure(s, &s->frames, &s->frames_floats, size_t(rd->max_depth + 2) * RT_FRAME_WORDS * s->n_threads); if (rc) return rc;
-            fr.frames = s->frames;
-        }
-        rc = ensure_material_pool(s, fr, rd->integrator != RT_INTEGRATOR_PATH ? size_t(rd->max_depth + 2) : 1, s->n_threads); if (rc) return rc;
-        if (s->volume.present) {
-            rc = ensure(s, &s->vol_buf, &s->vol_cap, (size_t(vol_levels) * 8 + 13 + vol_samp_words) * s->n_threads); if (rc) return rc;
-            fr.vol_rays = s->vol_buf; fr.vol_state = s->vol_buf + size_t(vol_levels) * 8 * s->n_threads;
-            fr.vol_samp = fr.vol_state + size_t(13) * s->n_threads; fr.vol_nmax = vol_nmax;
-        }
+        rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
         int variant = (((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 2 + (s->counting ? 1 : 0)) * 3 + rd->integrator;
         if (fr.high_occupancy && !s->counting) variant = 24 + ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 3 + rd->integrator;
         if (s->has_ext && !s->counting) variant = 36 + ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 3 + rd->integrator;
@@ -570,8 +570,10 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
             // rt_weighted.h: count -> scan -> survey -> recurrence -> the frame.  ev0 .. ev1 bracket all of it (kernel_ms of a weighted frame is the five together)
             const int wk = ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 2 + (s->counting ? 1 : 0);
             const int nL = int(s->dev.n_lights), R = 1 + 2 * nL;
-            if (!s->wt_total) { HIPCHK(hipHostMalloc((void **)&s->wt_total, sizeof(unsigned long long), hipHostMallocDefault)); HIPCHK(hipMalloc((void **)&s->wt_sums, RT_WSCAN_BLOCKS * sizeof(unsigned long long))); for (hipEvent_t &e : s->wt_ev) HIPCHK(hipEventCreate(&e)); }
-            rc = ensure(s, &s->wt_base, &s->wt_base_cap, size_t(fr.total_work) + 1); if (rc) return rc;
+            if (!s->wt_total) HIPCHK(hipHostMalloc((void **)&s->wt_total.p, sizeof(unsigned long long), hipHostMallocDefault));
+            if ((rc = s->wt_sums.grow(RT_WSCAN_BLOCKS))) return rc;
+            for (Event &e : s->wt_ev) if (!e) HIPCHK(hipEventCreate(&e.p));
+            rc = ensure(s, s->wt_base, size_t(fr.total_work) + 1); if (rc) return rc;
             fr.wt_base = s->wt_base;
             auto pass = [&](int phase) -> int {
                 fr.weighted_phase = phase;
@@ -609,7 +611,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
                     if (at_least >= 4294967295.0) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\" with lights of mixed RNG use: the survey's records exceed 2^32 floats (quadratic in a sample's shading points)");
                 }
                 // where every sample's records start: per-sample sizes from the point counts (P * A + nD * P * (P + 1)), scanned like the counts were
-                rc = ensure(s, &s->wt_recbase, &s->wt_recbase_cap, size_t(fr.total_work) + 1); if (rc) return late_fail(rc, rt_last_error());
+                rc = ensure(s, s->wt_recbase, size_t(fr.total_work) + 1); if (rc) return late_fail(rc, rt_last_error());
                 const unsigned long long nw = fr.total_work;
                 if (nw) hipLaunchKernelGGL(weighted_sizes_kernel, dim3(unsigned((nw + 255) / 256)), dim3(256), 0, s->stream, (const unsigned *)s->wt_base, nw, unsigned(1 + 2 * (nL - nD)), unsigned(nD), s->wt_recbase);
                 hipLaunchKernelGGL(weighted_scan_sums_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, (const unsigned *)s->wt_recbase, nw, s->wt_sums);
@@ -621,8 +623,8 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
                 rec_floats = size_t(*s->wt_total);
                 fr.wt_recbase = s->wt_recbase;
             }
-            rc = ensure(s, &s->wt_rec, &s->wt_rec_cap, rec_floats + 1); if (rc) return late_fail(rc, rt_last_error());
-            rc = ensure(s, &s->wt_pick, &s->wt_pick_cap, size_t(n_points) + 1); if (rc) return late_fail(rc, rt_last_error());
+            rc = ensure(s, s->wt_rec, rec_floats + 1); if (rc) return late_fail(rc, rt_last_error());
+            rc = ensure(s, s->wt_pick, size_t(n_points) + 1); if (rc) return late_fail(rc, rt_last_error());
             fr.wt_rec = s->wt_rec; fr.wt_pick = s->wt_pick;
             if (n_points > 0) {
                 if ((rc = pass(2))) return rc;

@@ -263,13 +263,13 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(RT_EDEVICE, "rt_scene_create: no HIP device visible (the product path has no CPU fallback)");
-    // every error exit below goes through the guard: rt_scene_destroy frees whatever has been created so far
+    // every error exit below goes through the guard: rt_scene_destroy deletes the scene, whose members release whatever has been created so far
     struct Guard { RtScene *p; ~Guard() { if (p) rt_scene_destroy(p); } } guard{new RtScene()};
     RtScene *s = guard.p;
     if (device >= 0) { hipError_t e = hipSetDevice(device); if (e != hipSuccess) return fail(RT_EDEVICE, "hipSetDevice failed"); }
     HIPCHK(hipGetDevice(&s->device));
-    HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true;
-    HIPCHK(hipEventCreate(&s->ev0)); HIPCHK(hipEventCreate(&s->ev1));
+    HIPCHK(hipStreamCreateWithFlags(&s->own_stream.p, hipStreamNonBlocking)); s->stream = s->own_stream;
+    HIPCHK(hipEventCreate(&s->ev0.p)); HIPCHK(hipEventCreate(&s->ev1.p));
     s->n_tris = d->n_tris;
 
     const bool tlog = knob("PBRT_HIP_CREATE_LOG") != nullptr;           // where a scene create spends its time (10 M triangles: a minute)
@@ -402,8 +402,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     // nodes (+ one node of padding: the traversal may fetch node i+1 together with node i) and the leaf lists
     auto upload_nodes = [&](const NodeVec &v, const uint2 **dev) -> int {
         void *p = nullptr;
-        HIPCHK(hipMalloc(&p, (v.size() + 1) * sizeof(uint2)));
-        s->allocs.push_back(p);
+        if (int rc = scene_alloc(s, (v.size() + 1) * sizeof(uint2), &p)) return rc;
         if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(uint2), hipMemcpyHostToDevice));
         const uint2 pad = make_uint2(3u, 0u);
         HIPCHK(hipMemcpy((uint2 *)p + v.size(), &pad, sizeof pad, hipMemcpyHostToDevice));
@@ -430,8 +429,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
             if ((rc = upload(s, ll.slot_prim.data(), ll.slot_prim.size(), &slot_prim_dev))) return rc;
             const size_t units = ll.n_slots * RT_TRI_STRIDE + 4;            // (+ one record of padding: a lane without a primitive never loads, but the array is never empty)
             void *p = nullptr;
-            HIPCHK(hipMalloc(&p, units * sizeof(float4)));
-            s->allocs.push_back(p);
+            if ((rc = scene_alloc(s, units * sizeof(float4), &p))) return rc;
             s->dev.ltris = (const float4 *)p;
             HIPCHK(hipMemsetAsync(p, 0, units * sizeof(float4), s->stream));
             if (ll.n_slots) hipLaunchKernelGGL(derive_leaf_records_kernel, dim3(unsigned((ll.n_slots + 255) / 256)), dim3(256), 0, s->stream, slot_prim_dev,
@@ -443,8 +441,6 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
                 HIPCHK(hipMemcpy(back.data(), p, units * sizeof(float4), hipMemcpyDeviceToHost));
                 if (lt.size() != units || std::memcmp(back.data(), lt.data(), units * sizeof(float4)) != 0) return fail(RT_ESTATE, "rt_scene_create: the device-built primitive records differ from the host fill");
             }
-            s->n_leaf_tri_units = units;
-            s->n_leaf_entries = ll.lrefs.size();
         }
         tick("primitive records (device)");
         std::vector<uint4> pairs;
@@ -528,56 +524,33 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, s->device));
     s->n_cus = prop.multiProcessorCount;
-    {
-        unsigned mx = 0;
-        for (int k = 0; k < 48; ++k) {
-            int per_cu = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)render_kernel_of(k), RT_BLOCK, 0));
-            if (per_cu < 1) per_cu = 1;
-            s->grids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu);
-            mx = s->grids[k] > mx ? s->grids[k] : mx;
-        }
-        for (int k = 0; k < 8; ++k) {
-            int per_cu = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)g_render_kernels_weighted[k], RT_BLOCK, 0));
-            s->wgrids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
-            mx = s->wgrids[k] > mx ? s->wgrids[k] : mx;
-        }
-        for (int k = 0; k < 4; ++k) {
-            int per_cu = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)g_render_kernels_bidir[k], RT_BLOCK, 0));
-            s->bgrids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
-            mx = s->bgrids[k] > mx ? s->bgrids[k] : mx;
-        }
-        s->grid = mx;
-    }
-    s->n_threads = s->grid * RT_BLOCK;
+    unsigned trace_per_cu = ~0u;
+    if (const char *e = knob("PBRT_HIP_TRACE_BLOCKS_PER_CU")) trace_per_cu = unsigned(std::max(1, std::atoi(e)));   // occupancy experiments
+    unsigned mx = 0;                                            // the largest grid of a family
+    auto resident = [&](const void *kernel, unsigned &grid, unsigned at_most = ~0u) -> int {      // kernel -> resident blocks x CUs
+        int per_cu = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RT_BLOCK, 0));
+        grid = unsigned(prop.multiProcessorCount) * std::max(1u, std::min(unsigned(std::max(per_cu, 0)), at_most));
+        mx = std::max(mx, grid);
+        return RT_OK;
+    };
+    for (int k = 0; k < 48; ++k) if ((rc = resident((const void *)render_kernel_of(k), s->grids[k]))) return rc;
+    for (int k = 0; k < 8; ++k) if ((rc = resident((const void *)g_render_kernels_weighted[k], s->wgrids[k]))) return rc;
+    for (int k = 0; k < 4; ++k) if ((rc = resident((const void *)g_render_kernels_bidir[k], s->bgrids[k]))) return rc;
+    s->grid = mx;                                               // ... of the megakernels
+    for (int k = 0; k < 8; ++k) if ((rc = resident((const void *)g_pipe_trace[k], s->trace_grids[k], trace_per_cu))) return rc;
+    for (int k = 0; k < 6; ++k) if ((rc = resident((const void *)g_pipe_march[k], s->march_grids[k]))) return rc;
+    s->n_threads = mx * RT_BLOCK;                               // ... of all: the spill area is shared
     s->spill_depth = s->tree.max_depth > RT_TRACE_STACK ? s->tree.max_depth - RT_TRACE_STACK + 1 : 1;     // RT_TRACE_STACK <= RT_STACK_LDS
-    HIPCHK(hipMalloc((void **)&s->work_counter, 64 * sizeof(unsigned long long)));      // 8 band counters, one 64-byte line each (the pipeline uses the first)
-    HIPCHK(hipMalloc((void **)&s->counters, 64 * sizeof(unsigned long long)));        // 8 RtCounters, 16 RT_PROFILE, 2 x 16 RT_PROFILE_STAGES
+    if ((rc = s->work_counter.grow(64))) return rc;             // 8 band counters, one 64-byte line each (the pipeline uses the first)
+    if ((rc = s->counters.grow(64))) return rc;                 // 8 RtCounters, 16 RT_PROFILE, 2 x 16 RT_PROFILE_STAGES
     HIPCHK(hipMemsetAsync(s->counters, 0, 64 * sizeof(unsigned long long), s->stream));
-    HIPCHK(hipMalloc((void **)&s->filter_dev, 256 * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&s->dev_scene, sizeof(DevScene)));
-    HIPCHK(hipMalloc((void **)&s->dev_frame, sizeof(DevFrame)));
+    if ((rc = s->filter_dev.grow(256)) || (rc = s->dev_scene.grow(1)) || (rc = s->dev_frame.grow(1))) return rc;
     HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
-    HIPCHK(hipEventCreate(&s->ev2));
-    for (int k = 0; k < 8; ++k) {
-        int per_cu = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)g_pipe_trace[k], RT_BLOCK, 0));
-        if (const char *e = knob("PBRT_HIP_TRACE_BLOCKS_PER_CU")) per_cu = std::min(per_cu, std::max(1, std::atoi(e)));   // occupancy experiments
-        s->trace_grids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
-        if (s->trace_grids[k] * RT_BLOCK > s->n_threads) s->n_threads = s->trace_grids[k] * RT_BLOCK;      // the spill area is shared
-    }
-    for (int k = 0; k < 6; ++k) {
-        int per_cu = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)g_pipe_march[k], RT_BLOCK, 0));
-        s->march_grids[k] = unsigned(prop.multiProcessorCount) * unsigned(per_cu < 1 ? 1 : per_cu);
-        if (s->march_grids[k] * RT_BLOCK > s->n_threads) s->n_threads = s->march_grids[k] * RT_BLOCK;
-    }
-    HIPCHK(hipMalloc((void **)&s->spill, size_t(s->spill_depth) * s->n_threads * sizeof(uint4)));     // uint4 entries in the pair form, uint2 otherwise
-    HIPCHK(hipMalloc((void **)&s->dev_pool, sizeof(PipePool)));
-    HIPCHK(hipMalloc((void **)&s->trace_qc, RT_QC_STRIDE * sizeof(unsigned)));
-    HIPCHK(hipHostMalloc((void **)&s->h_qcount, size_t(RT_PIPE_QN) * RT_QC_STRIDE * sizeof(unsigned), hipHostMallocDefault));
+    HIPCHK(hipEventCreate(&s->ev2.p));
+    if ((rc = s->spill.grow(size_t(s->spill_depth) * s->n_threads * 2))) return rc;        // uint4 entries in the pair form, uint2 otherwise
+    if ((rc = s->dev_pool.grow(1)) || (rc = s->trace_qc.grow(RT_QC_STRIDE))) return rc;
+    HIPCHK(hipHostMalloc((void **)&s->h_qcount.p, size_t(RT_PIPE_QN) * RT_QC_STRIDE * sizeof(unsigned), hipHostMallocDefault));
     HIPCHK(hipStreamSynchronize(s->stream));
     guard.p = nullptr;
     *out = s;
@@ -588,41 +561,14 @@ int rt_scene_destroy(RtScene *s) {
     if (!s) return RT_OK;
     HIPWARN(hipSetDevice(s->device));
     if (s->stream) hipStreamSynchronize(s->stream);
-    for (void *p : s->allocs) HIPWARN(hipFree(p));
-    if (s->own_accum && s->accum) HIPWARN(hipFree(s->accum));
-    HIPWARN(hipFree(s->spill)); HIPWARN(hipFree(s->work_counter)); HIPWARN(hipFree(s->counters)); HIPWARN(hipFree(s->filter_dev));
-    if (s->frames) HIPWARN(hipFree(s->frames));
-    if (s->samples) HIPWARN(hipFree(s->samples));
-    if (s->resolve_buf) HIPWARN(hipFree(s->resolve_buf));
-    if (s->vol_buf) HIPWARN(hipFree(s->vol_buf));
-    if (s->mat_buf) HIPWARN(hipFree(s->mat_buf));
-    if (s->light_dims) HIPWARN(hipFree(s->light_dims));
-    if (s->wt_base) HIPWARN(hipFree(s->wt_base));
-    if (s->wt_recbase) HIPWARN(hipFree(s->wt_recbase));
-    if (s->wt_rec) HIPWARN(hipFree(s->wt_rec));
-    if (s->wt_pick) HIPWARN(hipFree(s->wt_pick));
-    if (s->wt_total) HIPWARN(hipHostFree(s->wt_total));
-    if (s->wt_sums) HIPWARN(hipFree(s->wt_sums));
-    for (hipEvent_t e : s->wt_ev) if (e) HIPWARN(hipEventDestroy(e));
-    HIPWARN(hipFree(s->dev_scene)); HIPWARN(hipFree(s->dev_frame));
-    HIPWARN(hipFree(s->pool.state)); HIPWARN(hipFree(s->pool.ray_o)); HIPWARN(hipFree(s->pool.hit)); HIPWARN(hipFree(s->pool.q_o));
-    HIPWARN(hipFree(s->pool.q_slot)); HIPWARN(hipFree(s->pool.q_count)); HIPWARN(hipFree(s->pool.wave_work)); HIPWARN(hipFree(s->dev_pool));
-    HIPWARN(hipFree(s->trace_buf)); HIPWARN(hipFree(s->trace_qc));
-    if (s->h_qcount) HIPWARN(hipHostFree(s->h_qcount));
-    for (hipEvent_t e : s->pipe_ev) HIPWARN(hipEventDestroy(e));
-    for (hipEvent_t e : s->pipe_fence) HIPWARN(hipEventDestroy(e));
-    if (s->ev2) HIPWARN(hipEventDestroy(s->ev2));
-    if (s->ev0) HIPWARN(hipEventDestroy(s->ev0));
-    if (s->ev1) HIPWARN(hipEventDestroy(s->ev1));
-    if (s->own_stream && s->stream) HIPWARN(hipStreamDestroy(s->stream));
     delete s;
     return RT_OK;
 }
 
 int rt_scene_set_stream(RtScene *s, void *hip_stream) {
     if (!s) return fail(RT_EINVAL, "null scene");
-    if (s->own_stream && s->stream) { HIPWARN(hipStreamSynchronize(s->stream)); HIPWARN(hipStreamDestroy(s->stream)); }
-    s->stream = static_cast<hipStream_t>(hip_stream); s->own_stream = false;
+    if (s->own_stream) { HIPWARN(hipStreamSynchronize(s->own_stream)); s->own_stream.reset(); }
+    s->stream = static_cast<hipStream_t>(hip_stream);
     return RT_OK;
 }
 
@@ -771,14 +717,13 @@ int ensure_material_pool(RtScene *s, DevFrame &fr, size_t levels, size_t n_slots
     if (!s->has_textures || s->dev.n_textured == 0) return RT_OK;
     const size_t base = s->materials_host.size(), need = levels * n_slots;
     if (base + need >= (size_t(1) << 31)) return fail(RT_EINVAL, "rt_render: more than 2^31 resolved-material records (threads x recursion levels)");
-    if (!s->mat_buf || need > s->mat_pool_cap) {
+    if (base + need > s->mat_buf.cap) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        DevMaterial *nb = nullptr;
-        HIPCHK(hipMalloc((void **)&nb, (base + need) * sizeof(DevMaterial)));
-        if (s->mat_buf) HIPWARN(hipFree(s->mat_buf));
-        s->mat_buf = nb; s->mat_pool_cap = need;
-        HIPCHK(hipMemcpy(nb, s->materials_host.data(), base * sizeof(DevMaterial), hipMemcpyHostToDevice));
-        s->dev.materials = nb;
+        DevBuf<DevMaterial> nb;                                // (the old block goes once the new one exists: dev.materials never dangles)
+        if (int rc = nb.grow(base + need)) return rc;
+        s->mat_buf = std::move(nb);
+        HIPCHK(hipMemcpy(s->mat_buf, s->materials_host.data(), base * sizeof(DevMaterial), hipMemcpyHostToDevice));
+        s->dev.materials = s->mat_buf;
         HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
     }
     fr.mat_pool_base = unsigned(base);
