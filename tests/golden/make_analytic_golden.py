@@ -1,0 +1,78 @@
+"""Generate the per-sample analytic fixtures in tests/golden/analytic/ by running the UNMODIFIED reference (oracle/_ref/pbrt_ref, the
+non-keyed build: no random number enters these frames) on the cases of tests/analytic_cases.py, the way tests/golden/make_materials_golden.py
+does for the material fixtures.  Runs only where the reference sources exist.
+
+    python tests/golden/make_analytic_golden.py [name ...]
+
+Every scene is rendered with a box filter of width .5 and one unjittered sample per pixel, so the film IS the per-sample radiance at the
+pixel centres.  For each case the float64 form (tests/analytic_forms.py) is evaluated at the same positions, the exclusion band is built
+(analytic_forms.band: float64 geometry only) and <name>.npz stores the scene text, the film (rgb, alpha), the band mask, `ref_err` (the
+reference's largest error e outside the band, analytic_forms.sample_error) and `band_share`.  The generator refuses a fixture whose band
+exceeds 3 % of the samples, one whose spot light puts too few samples into the falloff zone, and one that is insensitive: the case's
+wrong twin must put at least 5 % of the included samples beyond 10 x the case's bar (analytic_cases.bar) against the reference's film.
+probe_ortho_quadrics.npz, probe_env_quadrics.npz and probe_lens_quadrics.npz hold the records of the probe integrator plugin (oracle/ref/probe_integrator.cpp: camera ray
+and closest hit t, p, n, u, v per camera sample) for an orthographic camera with a screen window, an environment camera and a thin-lens perspective camera that look at one of
+every quadric, the band of analytic_forms.ray_band and the reference's deviations from the float64 camera and intersectors.
+Fixtures are DATA (scene text, arrays, measured numbers); no reference source text is stored."""
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+import __graft_entry__ as g  # noqa: E402
+import analytic_cases as A  # noqa: E402
+
+OUT = os.path.join(HERE, "analytic")
+
+
+def main():
+    REF = g.load_ref_runner()
+    only = set(sys.argv[1:])
+    os.makedirs(OUT, exist_ok=True)
+    for name in A.PROBES:
+        # the camera probes: the existing "probe" integrator plugin, the existing 20-float record per camera ray
+        if only and name not in only:
+            continue
+        d = tempfile.mkdtemp()
+        dump = os.path.join(d, "rays.bin")
+        REF.run_reference(A.scene_text(name, probe_dump=dump), keyed=False, workdir=d)
+        rec = np.fromfile(dump, np.float32).reshape(-1, 20)
+        m = A.measure_probe(name, rec)
+        print(name, rec.shape, {k: v for k, v in m.items() if k != "band"})
+        assert m["band_share"] <= A.BAND_CAP and m["hit_equal"] and m["mint_equal"] and len(m["kinds_hit"]) == 6, name
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), scene=np.array(A.scene_text(name)), records=rec, band=m["band"],
+                            **{k: np.array(m[k]) for k in ("dev_o", "dev_d", "dev_t", "dev_p", "dev_n", "dev_uv", "band_share")})
+    done = {}
+    for name in A.CASES:
+        if only and name not in only:
+            continue
+        text = A.scene_text(name)
+        rgb, alpha, st = REF.run_reference(text, keyed=False)
+        assert np.isfinite(rgb).all() and st["stderr_lines"] == 0, name
+        m = A.measure(name, rgb, alpha)
+        print("%-28s ref_err %.3g  band %.4f  hits %.3f  Lcase %.3g  film max %.3g  far roots %.3f  falloff share %.3f" %
+              (name, m["ref_err"], m["band_share"], m["hit_share"], m["lcase"], float(rgb.max()), m["far_root_share"], m["falloff_share"]))
+        assert m["alpha_equal"], "%s: alpha differs from the form's hit mask outside the band" % name
+        assert m["band_share"] <= A.BAND_CAP, "%s: band %.4f" % (name, m["band_share"])
+        assert m["falloff_share"] >= A.CASES[name].get("min_falloff_share", 0), name
+        done[name] = (text, rgb, alpha, m)
+    # the bars need every case's ref_err (the family median): the cases not regenerated now come from their fixtures
+    ref_errs = {n: float(np.load(os.path.join(OUT, n + ".npz"))["ref_err"]) for n in A.CASES if n not in done and os.path.exists(os.path.join(OUT, n + ".npz"))}
+    ref_errs.update({n: d[3]["ref_err"] for n, d in done.items()})
+    for name, (text, rgb, alpha, m) in done.items():
+        bar = A.bar(name, ref_errs)
+        share = A.twin_share(name, rgb, m["band"], bar)
+        print("%-28s bar %.3g  twin %-26s beyond 10 x bar on %.3f" % (name, bar, A.CASES[name]["twin"], share))
+        assert share >= A.MIN_TWIN_SHARE, "%s: the wrong twin %s differs on only %.3f of the samples" % (name, A.CASES[name]["twin"], share)
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), scene=np.array(text), rgb=rgb, alpha=alpha, band=m["band"], ref_err=np.array(m["ref_err"]),
+                            band_share=np.array(m["band_share"]), twin_share=np.array(share), stats=np.array(json.dumps(st)))
+
+
+if __name__ == "__main__":
+    main()
