@@ -17,16 +17,12 @@ import pytest
 import analytic_cases as A
 import analytic_forms as F
 from conftest import GOLDEN, film_metrics
+from gpu_checks import need_gpu
 
 pytestmark = pytest.mark.gpu
 
 NAMES = list(A.CASES)
 FLAVOUR_CASES = ["plastic_rough_.02", "quadric_hyperboloid", "medium_homogeneous"]      # one lobe, one quadric, the medium
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
 
 
 def load(name):

@@ -6,43 +6,19 @@ Bars: every direction here passes through the device's sinf / co
 >= 99.5 % of the pixels with per-pixel L2 < 1e-4 and mean L2 < 1e-4, alpha off on <= 0.5 % of the pixels, ray counts within max(4, 2e-4 * n),
 camera rays exact, no bad samples.  There is no strict-bar case and no allow-list."""
 import ctypes as C
-import glob
-import os
 import re
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g_entry
-from conftest import GOLDEN, film_metrics, load_golden, stat_int
+from conftest import film_metrics, load_golden
+from gpu_checks import assert_prebuilt_agrees, assert_two_shards_agree, check_bar, check_counts, differing_share, fixture_names, need_gpu
 
 pytestmark = pytest.mark.gpu
 
-ALL = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "bidir", "*.npz")))
+ALL = fixture_names("bidir")
 BIDIR_RE = re.compile(r'^SurfaceIntegrator "bidirectional"[^\n]*\n', re.M)
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
-
-
-def check_bar(name, rgb, alpha, ref_rgb, ref_alpha):
-    m = film_metrics(rgb, ref_rgb)
-    print(name, m, "alpha maxabs %.3g off on %.4f" % (float(np.abs(alpha - ref_alpha).max()), float((np.abs(alpha - ref_alpha) > 1e-5).mean())))
-    assert np.isfinite(rgb).all(), name
-    assert m["frac"] >= 0.995 and m["mean_l2"] < 1e-4, (name, m)
-    assert (np.abs(alpha - ref_alpha) > 1e-5).mean() <= 0.005, name
-    return m
-
-
-def check_counts(name, cnt, st):
-    print(name, "device", cnt["closest_rays"], cnt["any_rays"], "reference", st["closest_rays"], st["any_rays"])
-    tol_c = max(4, int(2e-4 * st["closest_rays"]))
-    tol_a = max(4, int(2e-4 * st["any_rays"]))
-    assert abs(cnt["closest_rays"] - st["closest_rays"]) <= tol_c and abs(cnt["any_rays"] - st["any_rays"]) <= tol_a, (name, cnt, st["closest_rays"], st["any_rays"])
-    cam, exact = stat_int(st["stats"]["Camera Rays Traced"])          # StatsPrint writes 17424 as "17.4k": equal where it is exact, else equal as printed
-    assert (cnt["camera_rays"] == cam if exact else abs(cnt["camera_rays"] - cam) <= .0005 * cam + 50) and cnt["bad_samples"] == 0, (cnt["camera_rays"], cam)
 
 
 def as_path(text):
@@ -82,9 +58,9 @@ def test_bidir_film_matches_reference_fixture(pkg, name):
     ds.set_counting(False); ds.clear_film(); ds.render()
     trgb, talpha = ds.film()
     ds.close()
-    check_bar(name, rgb, alpha, g["rgb"], g["alpha"])
-    check_bar(name + " timed", trgb, talpha, g["rgb"], g["alpha"])
-    check_counts(name, cnt, g["stats"])
+    check_bar(name, rgb, alpha, g["rgb"], g["alpha"], True)
+    check_bar(name + " timed", trgb, talpha, g["rgb"], g["alpha"], True)
+    check_counts(name, cnt, g["stats"], True)
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -94,7 +70,7 @@ def test_the_path_film_is_another_film(pkg, name):
     g = load_golden("bidir/" + name)
     assert float(g["path_share"]) >= 0.05
     rgb, _, _, _ = pkg.render_text(as_path(g["scene"]))
-    share = float((np.sqrt(((rgb.astype(np.float64) - g["rgb"]) ** 2).sum(-1)) > 1e-3).mean())
+    share = differing_share(rgb, g["rgb"])
     print(name, "differs on", share)
     assert share >= 0.05, (name, share)
 
@@ -160,30 +136,14 @@ def test_bidir_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
 def test_two_shards_and_prebuilt_scene_give_the_same_film(pkg, name):
     """Two shards of 8 x 8-pixel tiles, summed, and rt_scene_create_prebuilt (the multi-rank path) give the film of one rt_scene_create frame."""
     need_gpu(pkg)
-    g = load_golden("bidir/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
+    ps = pkg.ParsedScene(text=load_golden("bidir/" + name)["scene"])
     a = pkg.DeviceScene(ps)
     a.render()
-    ref = a.film_accum()
-    nodes, refs = a.accel_arrays()
-    info = a.accel_info()
+    ref, cnt_ref = a.film_accum(), a.counters()
     a.close()
-    b = pkg.DeviceScene(ps, prebuilt=(nodes, refs, info))
-    b.render()
-    got = b.film_accum()
-    assert np.array_equal(got, ref), float(np.abs(got - ref).max())
-    b.reset_counters(); b.clear_film(); b.render(); cnt_ref = b.counters()
-    b.reset_counters(); b.clear_film()
-    for shard in range(2):                                  # both shards into one film, as the ranks' films are summed
-        ps.set_shard(shard, 2, (8, 8))
-        b.render()
-    parts = b.film_accum(); cnt = b.counters()
-    ps.set_shard(0, 1, 64)
+    b = assert_prebuilt_agrees(pkg, ps, ref, cnt_ref)
+    assert_two_shards_agree(ps, b, ref, cnt_ref)          # (the box filter of these frames)
     b.close()
-    # the box filter of these frames gives every sample to the one pixel it lies in, and a tile holds whole pixels: a pixel's sum is formed by one shard
-    assert np.array_equal(parts, ref), float(np.abs(parts - ref).max())
-    for k in ("camera_rays", "closest_rays", "any_rays"):
-        assert cnt[k] == cnt_ref[k], (k, cnt[k], cnt_ref[k])
 
 
 def test_samples_read_back(pkg):
@@ -255,5 +215,5 @@ def test_live_reference_bidir_frame(pkg, scenes):
     except FileNotFoundError:
         pytest.skip("oracle/_ref not on this box")
     rgb, alpha, cnt, _ = pkg.render_text(text)
-    check_bar("live", rgb, alpha, ref_rgb, ref_alpha)
-    check_counts("live", cnt, st)
+    check_bar("live", rgb, alpha, ref_rgb, ref_alpha, True)
+    check_counts("live", cnt, st, True)

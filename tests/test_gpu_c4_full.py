@@ -8,7 +8,7 @@ The frame at all 256 spp (1.07 G camera samples, a 34 GB sample buffer) is bench
 One scene create (about half a minute on the GPU box) serves the module."""
 import numpy as np
 import pytest
-from test_gpu_parity import need_gpu
+from gpu_checks import need_gpu
 from test_gpu_configs import accel_of, COUNTERS
 
 pytestmark = pytest.mark.gpu

@@ -8,7 +8,8 @@ Everything goes through the C ABI (pbrt_hip.h); the oracle is the checker only."
 import numpy as np
 import pytest
 from conftest import film_metrics
-from test_gpu_parity import need_gpu, check_film, record_case
+from gpu_checks import need_gpu
+from test_gpu_parity import check_film, record_case
 
 pytestmark = pytest.mark.gpu
 

@@ -1,37 +1,19 @@
 """Density media on the device (DensityRegion with ExponentialDensity / VolumeGrid, rt_scene_set_density), against the unmodified
 reference: the fixtures of tests/golden/density/ (tests/golden/make_density_golden.py), one live frame when oracle/_ref travelled with
 the tree, the kernel flavours and both scene-creation paths against each other, and rt_render's refusal of a march that cannot advance.
-Bars are those of tests/test_gpu_parity.py: Whitted / DirectLighting every pixel within 1e-5; path >= 99.5 % of the pixels with
-per-pixel L2 < 1e-4 and mean L2 < 1e-4; ray counts equal to the reference's."""
-import glob
-import os
-
+Bars are those of tests/gpu_checks.py: Whitted / DirectLighting the strict one, path the loose one; ray counts equal to the reference's
+under both."""
 import numpy as np
 import pytest
 
 import __graft_entry__ as g_entry
-from conftest import GOLDEN, film_metrics, load_golden
+from conftest import film_metrics, load_golden
+from gpu_checks import PIPELINE_ENVS, assert_flavours_agree, assert_prebuilt_agrees, check_bar, check_counts, fixture_names, need_gpu, render_both
 
 pytestmark = pytest.mark.gpu
 
-DENSITY = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "density", "*.npz")))
+DENSITY = fixture_names("density")
 PATH = 2
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
-
-
-def check_bar(name, rgb, alpha, ref_rgb, ref_alpha, integrator):
-    m = film_metrics(rgb, ref_rgb)
-    assert np.isfinite(rgb).all(), name
-    if integrator == PATH:
-        assert m["frac"] >= 0.995 and m["mean_l2"] < 1e-4, (name, m)
-    else:
-        assert m["maxabs"] <= 1e-5, (name, m)
-        assert float(np.abs(alpha - ref_alpha).max()) <= 1e-5, name
-    return m
 
 
 def test_fixtures_present():
@@ -42,20 +24,11 @@ def test_fixtures_present():
 def test_density_film_matches_reference_fixture(pkg, name):
     need_gpu(pkg)
     g = load_golden("density/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    assert ps.valid and ps.volume()["density"] is not None
-    ds = pkg.DeviceScene(ps)
-    ds.render()
-    rgb, alpha = ds.film()
-    cnt = ds.counters()
-    ds.set_counting(False); ds.clear_film(); ds.render()           # the timed kernels, against the reference directly
-    trgb, talpha = ds.film()
-    ds.close()
-    check_bar(name, rgb, alpha, g["rgb"], g["alpha"], ps.integrator)
-    check_bar(name + " timed", trgb, talpha, g["rgb"], g["alpha"], ps.integrator)
-    st = g["stats"]
-    assert cnt["closest_rays"] == st["closest_rays"] and cnt["any_rays"] == st["any_rays"], (name, cnt, st["closest_rays"], st["any_rays"])
-    assert cnt["camera_rays"] == int(st["stats"]["Camera Rays Traced"]) and cnt["bad_samples"] == 0
+    ps, rgb, alpha, cnt, trgb, talpha = render_both(pkg, g["scene"])           # (the timed kernels too against the reference directly)
+    assert ps.volume()["density"] is not None
+    check_bar(name, rgb, alpha, g["rgb"], g["alpha"], ps.integrator == PATH)
+    check_bar(name + " timed", trgb, talpha, g["rgb"], g["alpha"], ps.integrator == PATH)
+    check_counts(name, cnt, g["stats"], False)                                  # exact also under path tracing
 
 
 def test_density_without_the_region_differs(pkg):
@@ -71,36 +44,13 @@ def test_density_without_the_region_differs(pkg):
 
 @pytest.mark.parametrize("name", ["dens_exp_single_whitted", "dens_grid_single_direct_grid", "dens_grid_xform_path", "dens_exp_emission_path",
                                   "dens_grid_emission_whitted_ld"])
-def test_density_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
+def test_density_kernel_flavours_give_the_same_film(pkg, name):
     """Counting twins, timed kernels (both occupancy flavours) and the queue pipeline (per ray, and with 512 slots so that every slot is
-    refilled many times) give the bit-identical film, and the pipeline's counting twin the same ray counts."""
+    refilled many times; the by-vertex setting changes nothing for a frame with a medium) give the bit-identical film, and the counting
+    twins the same ray counts."""
     need_gpu(pkg)
-    g = load_golden("density/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    ds = pkg.DeviceScene(ps)
-    monkeypatch.setenv("PBRT_HIP_PIPELINE", "0")
-    ds.render()
-    ref = ds.film_accum()
-    cnt_ref = ds.counters()
-    for occ in ("0", "1"):
-        monkeypatch.setenv("PBRT_HIP_HIGH_OCC", occ)
-        ds.set_counting(False); ds.clear_film(); ds.render()
-        got = ds.film_accum()
-        assert np.array_equal(got, ref), (name, occ, float(np.abs(got - ref).max()))
-    monkeypatch.delenv("PBRT_HIP_HIGH_OCC")
-    for env in (dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512")):
-        with pytest.MonkeyPatch.context() as mp:
-            for k, v in env.items():
-                mp.setenv(k, v)
-            for counting in (False, True):
-                ds.set_counting(counting); ds.reset_counters(); ds.clear_film(); ds.render()
-                assert ds.last_stats()["pipeline"] == 1
-                got = ds.film_accum()
-                assert np.array_equal(got, ref), (name, env, counting, float(np.abs(got - ref).max()))
-                if counting:
-                    c = ds.counters()
-                    for k in ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples"):
-                        assert c[k] == cnt_ref[k], (name, env, k, c[k], cnt_ref[k])
+    ds = pkg.DeviceScene(pkg.ParsedScene(text=load_golden("density/" + name)["scene"]))
+    assert_flavours_agree(ds, name, PIPELINE_ENVS)
     ds.close()
 
 
@@ -108,19 +58,12 @@ def test_density_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
 def test_prebuilt_scene_takes_the_density_region(pkg, name):
     """rt_scene_create_prebuilt (the multi-rank path) + rt_scene_set_density gives the film of rt_scene_create."""
     need_gpu(pkg)
-    g = load_golden("density/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
+    ps = pkg.ParsedScene(text=load_golden("density/" + name)["scene"])
     a = pkg.DeviceScene(ps)
     a.render()
     ref = a.film_accum()
-    nodes, refs = a.accel_arrays()
-    info = a.accel_info()
     a.close()
-    b = pkg.DeviceScene(ps, prebuilt=(nodes, refs, info))
-    b.render()
-    got = b.film_accum()
-    b.close()
-    assert np.array_equal(got, ref), float(np.abs(got - ref).max())
+    assert_prebuilt_agrees(pkg, ps, ref).close()
 
 
 def test_set_density_is_refused_out_of_order(pkg, scenes):
@@ -181,5 +124,5 @@ def test_live_reference_density_frame(pkg, scenes):
     except FileNotFoundError:
         pytest.skip("oracle/_ref not on this box")
     rgb, alpha, cnt, _ = pkg.render_text(text)
-    check_bar("live", rgb, alpha, ref_rgb, ref_alpha, 1)
+    check_bar("live", rgb, alpha, ref_rgb, ref_alpha, False)
     assert cnt["closest_rays"] == st["closest_rays"] and cnt["any_rays"] == st["any_rays"]

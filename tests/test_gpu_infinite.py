@@ -5,63 +5,22 @@ when oracle/_ref travelled with the tree.
 Bars: every direction this light samples passes through the device's sinf / cosf / sqrtf, so the fixture frames are held
 to the loose bar -- >= 99.5 % of the pixels with per-pixel L2 < 1e-4 and mean L2 < 1e-4, alpha off on <= 0.5 % of the pixels, ray counts within
 max(4, 2e-4 * n), camera rays exact.  The empty-world frames involve no libm: every pixel within 1e-5, alpha 1 everywhere, no shadow rays."""
-import glob
-import os
 import re
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g_entry
-from conftest import GOLDEN, film_metrics, load_golden, stat_int
+from conftest import film_metrics, load_golden
+from gpu_checks import (PIPELINE_ENVS, assert_flavours_agree, assert_prebuilt_agrees, assert_two_shards_agree, check_bar, check_counts, differing_share,
+                        fixture_names, need_gpu, render_both)
 
 pytestmark = pytest.mark.gpu
 
-ALL = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "infinite", "*.npz")))
+ALL = fixture_names("infinite")
 EXACT = ["inf_empty_whitted", "inf_empty_direct"]
 LOOSE = [n for n in ALL if n not in EXACT]
 INF_RE = re.compile(r'^LightSource "infinite".*\n', re.M)
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
-
-
-def check_bar(name, rgb, alpha, ref_rgb, ref_alpha, loose):
-    m = film_metrics(rgb, ref_rgb)
-    print(name, "loose" if loose else "strict", m, "alpha maxabs %.3g off on %.4f" % (float(np.abs(alpha - ref_alpha).max()), float((np.abs(alpha - ref_alpha) > 1e-5).mean())))
-    assert np.isfinite(rgb).all(), name
-    if loose:
-        assert m["frac"] >= 0.995 and m["mean_l2"] < 1e-4, (name, m)
-        assert (np.abs(alpha - ref_alpha) > 1e-5).mean() <= 0.005, name
-    else:
-        assert m["maxabs"] <= 1e-5, (name, m)
-        assert float(np.abs(alpha - ref_alpha).max()) <= 1e-5, name
-    return m
-
-
-def check_counts(name, cnt, st, loose):
-    print(name, "device", cnt["closest_rays"], cnt["any_rays"], "reference", st["closest_rays"], st["any_rays"])
-    tol_c = max(4, int(2e-4 * st["closest_rays"])) if loose else 0
-    tol_a = max(4, int(2e-4 * st["any_rays"])) if loose else 0
-    assert abs(cnt["closest_rays"] - st["closest_rays"]) <= tol_c and abs(cnt["any_rays"] - st["any_rays"]) <= tol_a, (name, cnt, st["closest_rays"], st["any_rays"])
-    cam, exact = stat_int(st["stats"]["Camera Rays Traced"])          # StatsPrint writes 17424 as "17.4k": equal where it is exact, else equal as printed
-    assert (cnt["camera_rays"] == cam if exact else abs(cnt["camera_rays"] - cam) <= .0005 * cam + 50) and cnt["bad_samples"] == 0, (cnt["camera_rays"], cam)
-
-
-def render_both(pkg, text):
-    """counting kernels (film + counters) and timed kernels of one scene text"""
-    ps = pkg.ParsedScene(text=text)
-    assert ps.valid and ps.errors == 0
-    ds = pkg.DeviceScene(ps)
-    ds.render()
-    rgb, alpha = ds.film()
-    cnt = ds.counters()
-    ds.set_counting(False); ds.clear_film(); ds.render()
-    trgb, talpha = ds.film()
-    ds.close()
-    return ps, rgb, alpha, cnt, trgb, talpha
 
 
 def without_light(text):
@@ -108,7 +67,7 @@ def test_the_scene_without_the_light_is_another_film(pkg, name):
     g = load_golden("infinite/" + name)
     assert float(g["dark_share"]) >= 0.05
     rgb, _, _, _ = pkg.render_text(without_light(g["scene"]))
-    share = float((np.sqrt(((rgb.astype(np.float64) - g["rgb"]) ** 2).sum(-1)) > 1e-3).mean())
+    share = differing_share(rgb, g["rgb"])
     print(name, "differs on", share)
     assert share >= 0.05, (name, share)
 
@@ -130,36 +89,12 @@ FLAVOUR_CASES = ["inf_path", "inf_direct_all_ns4_grid_ld", "inf_medium_single_di
 
 
 @pytest.mark.parametrize("name", FLAVOUR_CASES)
-def test_infinite_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
+def test_infinite_kernel_flavours_give_the_same_film(pkg, name):
     """Counting twins, timed kernels (both occupancy flavours) and the queue pipeline (per ray, by path vertex where the frame takes that form, and
-    with 512 slots so that every slot is refilled many times) give the bit-identical film, and the pipeline's counting twin the same ray counts."""
+    with 512 slots so that every slot is refilled many times) give the bit-identical film, and the counting twins the same ray counts."""
     need_gpu(pkg)
-    g = load_golden("infinite/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    ds = pkg.DeviceScene(ps)
-    monkeypatch.setenv("PBRT_HIP_PIPELINE", "0")
-    ds.render()
-    ref = ds.film_accum()
-    cnt_ref = ds.counters()
-    for occ in ("0", "1"):
-        monkeypatch.setenv("PBRT_HIP_HIGH_OCC", occ)
-        ds.set_counting(False); ds.clear_film(); ds.render()
-        got = ds.film_accum()
-        assert np.array_equal(got, ref), (name, occ, float(np.abs(got - ref).max()))
-    monkeypatch.delenv("PBRT_HIP_HIGH_OCC")
-    for env in (dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="1"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512")):
-        with pytest.MonkeyPatch.context() as mp:
-            for k, v in env.items():
-                mp.setenv(k, v)
-            for counting in (False, True):
-                ds.set_counting(counting); ds.reset_counters(); ds.clear_film(); ds.render()
-                assert ds.last_stats()["pipeline"] == 1
-                got = ds.film_accum()
-                assert np.array_equal(got, ref), (name, env, counting, float(np.abs(got - ref).max()))
-                if counting:
-                    c = ds.counters()
-                    for k in ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples"):
-                        assert c[k] == cnt_ref[k], (name, env, k, c[k], cnt_ref[k])
+    ds = pkg.DeviceScene(pkg.ParsedScene(text=load_golden("infinite/" + name)["scene"]))
+    assert_flavours_agree(ds, name, PIPELINE_ENVS)
     ds.close()
 
 
@@ -167,31 +102,14 @@ def test_infinite_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
 def test_two_shards_and_prebuilt_scene_give_the_same_film(pkg, name):
     """Two shards of 8 x 8-pixel tiles, summed, and rt_scene_create_prebuilt (the multi-rank path) give the film of one rt_scene_create frame."""
     need_gpu(pkg)
-    g = load_golden("infinite/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
+    ps = pkg.ParsedScene(text=load_golden("infinite/" + name)["scene"])
     a = pkg.DeviceScene(ps)
     a.render()
-    ref = a.film_accum()
-    nodes, refs = a.accel_arrays()
-    info = a.accel_info()
+    ref, cnt_ref = a.film_accum(), a.counters()
     a.close()
-    b = pkg.DeviceScene(ps, prebuilt=(nodes, refs, info))
-    b.render()
-    got = b.film_accum()
-    assert np.array_equal(got, ref), float(np.abs(got - ref).max())
-    cnt_ref = None
-    b.reset_counters(); b.clear_film(); b.render(); cnt_ref = b.counters()
-    b.reset_counters(); b.clear_film()
-    for shard in range(2):                                  # both shards into one film, as the ranks' films are summed
-        ps.set_shard(shard, 2, (8, 8))
-        b.render()
-    parts = b.film_accum(); cnt = b.counters()
-    ps.set_shard(0, 1, 64)
+    b = assert_prebuilt_agrees(pkg, ps, ref, cnt_ref)
+    assert_two_shards_agree(ps, b, ref, cnt_ref)          # (the box filter of these frames)
     b.close()
-    # the box filter of these frames gives every sample to the one pixel it lies in, and a tile holds whole pixels: a pixel's sum is formed by one shard
-    assert np.array_equal(parts, ref), float(np.abs(parts - ref).max())
-    for k in ("camera_rays", "closest_rays", "any_rays"):
-        assert cnt[k] == cnt_ref[k], (k, cnt[k], cnt_ref[k])
 
 
 def test_weighted_with_an_infinite_light_is_refused(pkg, scenes):

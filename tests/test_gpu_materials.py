@@ -2,71 +2,28 @@
 unmodified reference: the fixtures of tests/golden/materials/ (tests/golden/make_materials_golden.py), light through a translucent sheet,
 the matte fall-back as a different film, the kernel flavours and both scene-creation paths against each other, one live frame when
 oracle/_ref travelled with the tree, and rt_scene_create's refusal of an unknown material type.
-Bars are those of tests/test_gpu_parity.py: Whitted / DirectLighting on triangle-only scenes every pixel within 1e-5 (colour and alpha) with
-equal ray counts; path tracing and frames with a quadric >= 99.5 % of the pixels with per-pixel L2 < 1e-4 and mean L2 < 1e-4, ray counts
-within max(4, 2e-4 * closest_rays)."""
-import ctypes as C
-import glob
+Bars are those of tests/gpu_checks.py: Whitted / DirectLighting on triangle-only scenes the strict one, path tracing and frames with a quadric
+the loose one."""
 import json
-import os
 import re
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as g_entry
-from conftest import GOLDEN, film_metrics, load_golden, stat_int
+from conftest import film_metrics, load_golden
+from gpu_checks import PIPELINE_ENVS, assert_flavours_agree, assert_prebuilt_agrees, check_bar, check_counts, fixture_names, need_gpu, render_both
 
 pytestmark = pytest.mark.gpu
 
-MATERIALS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "materials", "*.npz")))
+MATERIALS = fixture_names("materials")
 PATH = 2
 T_ONLY_SHEET = '"translucent" "color reflect" [0 0 0] "color transmit" [.8 .8 .8] "float roughness" [.2]'
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
 
 
 def loose_bar(scene_text, integrator):
     """path tracing, or a quadric in the frame (device libm in the geometry): the 99.5 % bar"""
     return integrator == PATH or re.search(r'Shape "(sphere|disk|cylinder|cone|paraboloid|hyperboloid)"', scene_text) is not None
-
-
-def check_bar(name, rgb, alpha, ref_rgb, ref_alpha, loose):
-    m = film_metrics(rgb, ref_rgb)
-    print(name, "loose" if loose else "strict", m, "alpha maxabs %.3g" % float(np.abs(alpha - ref_alpha).max()))
-    assert np.isfinite(rgb).all(), name
-    if loose:
-        assert m["frac"] >= 0.995 and m["mean_l2"] < 1e-4, (name, m)
-        assert (np.abs(alpha - ref_alpha) > 1e-5).mean() <= 0.005, name
-    else:
-        assert m["maxabs"] <= 1e-5, (name, m)
-        assert float(np.abs(alpha - ref_alpha).max()) <= 1e-5, name
-    return m
-
-
-def check_counts(name, cnt, st, loose):
-    print(name, "device", cnt["closest_rays"], cnt["any_rays"], "reference", st["closest_rays"], st["any_rays"])
-    tol = max(4, int(2e-4 * st["closest_rays"])) if loose else 0
-    assert abs(cnt["closest_rays"] - st["closest_rays"]) <= tol and abs(cnt["any_rays"] - st["any_rays"]) <= tol, (name, cnt, st["closest_rays"], st["any_rays"])
-    cam, exact = stat_int(st["stats"]["Camera Rays Traced"])          # StatsPrint writes 17424 as "17.4k": equal where it is exact, else equal as printed
-    assert (cnt["camera_rays"] == cam if exact else abs(cnt["camera_rays"] - cam) <= .0005 * cam + 50) and cnt["bad_samples"] == 0, (cnt["camera_rays"], cam)
-
-
-def render_both(pkg, text):
-    """counting kernels (film + counters) and timed kernels of one scene text"""
-    ps = pkg.ParsedScene(text=text)
-    assert ps.valid and ps.errors == 0
-    ds = pkg.DeviceScene(ps)
-    ds.render()
-    rgb, alpha = ds.film()
-    cnt = ds.counters()
-    ds.set_counting(False); ds.clear_film(); ds.render()
-    trgb, talpha = ds.film()
-    ds.close()
-    return ps, rgb, alpha, cnt, trgb, talpha
 
 
 def as_matte(text):
@@ -132,37 +89,13 @@ FLAVOUR_CASES = ["shiny_mesh_direct_all_grid_ld", "shiny_mesh_path", "sheet_whit
 
 
 @pytest.mark.parametrize("name", FLAVOUR_CASES)
-def test_material_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
+def test_material_kernel_flavours_give_the_same_film(pkg, name):
     """Counting twins, timed kernels (both occupancy flavours) and the queue pipeline (per ray, and with 512 slots so that every slot is
-    refilled many times; by path vertex where the frame takes that form) give the bit-identical film, and the pipeline's counting twin the
-    same ray counts."""
+    refilled many times; by path vertex where the frame takes that form) give the bit-identical film, and the counting twins the same
+    ray counts."""
     need_gpu(pkg)
-    g = load_golden("materials/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    ds = pkg.DeviceScene(ps)
-    monkeypatch.setenv("PBRT_HIP_PIPELINE", "0")
-    ds.render()
-    ref = ds.film_accum()
-    cnt_ref = ds.counters()
-    for occ in ("0", "1"):
-        monkeypatch.setenv("PBRT_HIP_HIGH_OCC", occ)
-        ds.set_counting(False); ds.clear_film(); ds.render()
-        got = ds.film_accum()
-        assert np.array_equal(got, ref), (name, occ, float(np.abs(got - ref).max()))
-    monkeypatch.delenv("PBRT_HIP_HIGH_OCC")
-    for env in (dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="1"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512")):
-        with pytest.MonkeyPatch.context() as mp:
-            for k, v in env.items():
-                mp.setenv(k, v)
-            for counting in (False, True):
-                ds.set_counting(counting); ds.reset_counters(); ds.clear_film(); ds.render()
-                assert ds.last_stats()["pipeline"] == 1
-                got = ds.film_accum()
-                assert np.array_equal(got, ref), (name, env, counting, float(np.abs(got - ref).max()))
-                if counting:
-                    c = ds.counters()
-                    for k in ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples"):
-                        assert c[k] == cnt_ref[k], (name, env, k, c[k], cnt_ref[k])
+    ds = pkg.DeviceScene(pkg.ParsedScene(text=load_golden("materials/" + name)["scene"]))
+    assert_flavours_agree(ds, name, PIPELINE_ENVS)
     ds.close()
 
 
@@ -170,19 +103,12 @@ def test_material_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
 def test_prebuilt_scene_renders_the_materials(pkg, name):
     """rt_scene_create_prebuilt (the multi-rank path) gives the film of rt_scene_create."""
     need_gpu(pkg)
-    g = load_golden("materials/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
+    ps = pkg.ParsedScene(text=load_golden("materials/" + name)["scene"])
     a = pkg.DeviceScene(ps)
     a.render()
     ref = a.film_accum()
-    nodes, refs = a.accel_arrays()
-    info = a.accel_info()
     a.close()
-    b = pkg.DeviceScene(ps, prebuilt=(nodes, refs, info))
-    b.render()
-    got = b.film_accum()
-    b.close()
-    assert np.array_equal(got, ref), float(np.abs(got - ref).max())
+    assert_prebuilt_agrees(pkg, ps, ref).close()
 
 
 def test_unknown_material_type_is_refused(pkg, scenes):

@@ -13,15 +13,11 @@ import numpy as np
 import pytest
 import __graft_entry__ as g_entry
 from conftest import golden_names, load_golden, film_metrics
+from gpu_checks import assert_flavours_agree, need_gpu
 
 pytestmark = pytest.mark.gpu
 
 FILMS = [n for n in golden_names() if not n.startswith("probe_")]
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
 
 
 def libm_bound(name, integrator):
@@ -480,41 +476,25 @@ def test_errors_are_loud(pkg, scenes):
     ds.close()
 
 
+# PBRT_HIP_PIPE_VERTEX left at its default, the per-ray form forced, and so few slots that every slot is refilled many times
+FLAVOUR_PIPELINE_ENVS = (dict(PBRT_HIP_PIPELINE="1"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512"))
+
+
 @pytest.mark.parametrize("name", ["path_soup2k", "direct_soup5k_seed7", "whitted_glass_mirror", "grid_path_soup3k_eager", "vol_single_path_grid",
                                   "plastic_path", "sphere_whitted", "qlight_path", "path_jitter_mitchell_4spp"])
-def test_timed_kernels_produce_the_same_film_as_the_counting_twins(pkg, name, monkeypatch):
+def test_timed_kernels_produce_the_same_film_as_the_counting_twins(pkg, name):
     """bench.py times the COUNT=false kernels (and, on large scenes, the register-capped high-occupancy flavour); the parity
     tests above render with the counting twins.  Scheduling never changes a sample's arithmetic and the film gather is
-    deterministic, so every flavour must give the bit-identical film."""
+    deterministic, so every flavour must give the bit-identical film.
+    The queue pipeline: by vertex (rt_pipe_vertex.h: path integrator without a medium; every other frame takes the per-ray form), per
+    ray, and with so few slots that every slot is refilled many times; its counting twin must also reproduce the ray counts."""
     need_gpu(pkg)
-    g = load_golden(name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    ds = pkg.DeviceScene(ps)
-    ds.render()
-    ref = ds.film_accum()
-    for occ in ("0", "1"):
-        monkeypatch.setenv("PBRT_HIP_HIGH_OCC", occ)
-        ds.set_counting(False)
-        ds.clear_film(); ds.render()
-        got = ds.film_accum()
-        assert np.array_equal(got, ref), (name, occ, float(np.abs(got - ref).max()))
-    monkeypatch.delenv("PBRT_HIP_HIGH_OCC")
-    # the queue pipeline: by vertex (rt_pipe_vertex.h: path integrator without a medium; every other frame takes the per-ray form), per
-    # ray, and with so few slots that every slot is refilled many times; its counting twin must also reproduce the ray counts
-    cnt_ref = ds.counters()
-    for env in (dict(PBRT_HIP_PIPELINE="1"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512")):
-        with pytest.MonkeyPatch.context() as mp:
-            for k, v in env.items():
-                mp.setenv(k, v)
-            for counting in (False, True):
-                ds.set_counting(counting); ds.reset_counters(); ds.clear_film(); ds.render()
-                got = ds.film_accum()
-                assert np.array_equal(got, ref), (name, env, counting, float(np.abs(got - ref).max()))
-                if counting:
-                    c = ds.counters()
-                    for k in ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples"):
-                        assert c[k] == cnt_ref[k], (name, env, k, c[k], cnt_ref[k])
+    ds = pkg.DeviceScene(pkg.ParsedScene(text=load_golden(name)["scene"]))
+    ref, _ = assert_flavours_agree(ds, name, FLAVOUR_PIPELINE_ENVS, expect_pipeline=None)
+    ds.set_counting(True); ds.clear_film(); ds.render()                 # and the flavour that rt_render chooses for the frame by itself
+    got = ds.film_accum()
     ds.close()
+    assert np.array_equal(got, ref), (name, "default", float(np.abs(got - ref).max()))
 
 
 def _random_scene(scenes, rng):

@@ -5,15 +5,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_checks import need_gpu
 
 pytestmark = pytest.mark.gpu
 
 COUNTERS = ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples")
-
-
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
 
 
 def parsed(pkg, name):

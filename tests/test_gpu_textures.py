@@ -2,71 +2,29 @@
 evaluated and resolved per hit by the EXT kernels), against the unmodified reference: the fixtures of tests/golden/textures/
 (tests/golden/make_textures_golden.py), the scene without its textures as a different film, the per-hit resolve against the host's, the kernel
 flavours and both scene-creation paths against each other, and rt_scene_set_textures' refusals.
-Bars are those of tests/test_gpu_parity.py: Whitted / DirectLighting on triangle-only scenes with uv or planar mapping every pixel within 1e-5
-(colour and alpha) with equal ray counts; path tracing, the bidirectional integrator, a quadric, a spherical / cylindrical mapping or a textured
-sigma >= 99.5 % of the pixels with per-pixel L2 < 1e-4 and mean L2 < 1e-4, ray counts within max(4, 2e-4 * closest_rays)."""
+Bars are those of tests/gpu_checks.py: Whitted / DirectLighting on triangle-only scenes with uv or planar mapping the strict one; path tracing,
+the bidirectional integrator, a quadric, a spherical / cylindrical mapping or a textured sigma the loose one."""
 import ctypes as C
-import glob
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, film_metrics, load_golden, stat_int
+from conftest import film_metrics, load_golden
+from gpu_checks import PIPELINE_ENVS, assert_flavours_agree, assert_prebuilt_agrees, check_bar, check_counts, fixture_names, need_gpu, render_both
 
 pytestmark = pytest.mark.gpu
 
-TEXTURES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "textures", "*.npz")))
+TEXTURES = fixture_names("textures")
 PATH, BIDIR = 2, 3
 NONE = '"string aamode" ["none"]'
 PANEL = 'Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [60 20 300 500 20 300 500 460 420 60 460 420]\n'
 POINT = 'LightSource "point" "point from" [278 300 100] "color I" [90000 85000 70000]\n'
 
 
-def need_gpu(pkg):
-    if pkg.device_count() < 1:
-        pytest.fail("no HIP device visible: the product path has no CPU fallback")
-
-
 def loose_bar(scene_text, integrator):
     return (integrator in (PATH, BIDIR) or re.search(r'Shape "(sphere|disk|cylinder|cone|paraboloid|hyperboloid)"', scene_text) is not None or
             re.search(r'"string mapping" \["(spherical|cylindrical)"\]', scene_text) is not None or '"texture sigma"' in scene_text)
-
-
-def check_bar(name, rgb, alpha, ref_rgb, ref_alpha, loose):
-    m = film_metrics(rgb, ref_rgb)
-    print(name, "loose" if loose else "strict", m, "alpha maxabs %.3g" % float(np.abs(alpha - ref_alpha).max()))
-    assert np.isfinite(rgb).all(), name
-    if loose:
-        assert m["frac"] >= 0.995 and m["mean_l2"] < 1e-4, (name, m)
-        assert (np.abs(alpha - ref_alpha) > 1e-5).mean() <= 0.005, name
-    else:
-        assert m["maxabs"] <= 1e-5, (name, m)
-        assert float(np.abs(alpha - ref_alpha).max()) <= 1e-5, name
-    return m
-
-
-def check_counts(name, cnt, st, loose):
-    print(name, "device", cnt["closest_rays"], cnt["any_rays"], "reference", st["closest_rays"], st["any_rays"])
-    tol = max(4, int(2e-4 * st["closest_rays"])) if loose else 0
-    assert abs(cnt["closest_rays"] - st["closest_rays"]) <= tol and abs(cnt["any_rays"] - st["any_rays"]) <= tol, (name, cnt, st["closest_rays"], st["any_rays"])
-    cam, exact = stat_int(st["stats"]["Camera Rays Traced"])
-    assert (cnt["camera_rays"] == cam if exact else abs(cnt["camera_rays"] - cam) <= .0005 * cam + 50) and cnt["bad_samples"] == 0, (cnt["camera_rays"], cam)
-
-
-def render_both(pkg, text):
-    """counting kernels (film + counters) and timed kernels of one scene text"""
-    ps = pkg.ParsedScene(text=text)
-    assert ps.valid and ps.errors == 0
-    ds = pkg.DeviceScene(ps)
-    ds.render()
-    rgb, alpha = ds.film()
-    cnt = ds.counters()
-    ds.set_counting(False); ds.clear_film(); ds.render()
-    trgb, talpha = ds.film()
-    ds.close()
-    return ps, rgb, alpha, cnt, trgb, talpha
 
 
 def flat(text):
@@ -144,37 +102,13 @@ FLAVOUR_CASES = ["nested_mix_plastic_direct", "uber_opacity_path", "glass_checke
 
 
 @pytest.mark.parametrize("name", FLAVOUR_CASES)
-def test_texture_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
+def test_texture_kernel_flavours_give_the_same_film(pkg, name):
     """Counting twins, timed kernels (both occupancy flavours) and the queue pipeline (per ray, and with 512 slots so that every slot is
-    refilled many times; by path vertex where the frame takes that form) give the bit-identical film, and the pipeline's counting twin the
-    same ray counts."""
+    refilled many times; by path vertex where the frame takes that form) give the bit-identical film, and the counting twins the same
+    ray counts."""
     need_gpu(pkg)
-    g = load_golden("textures/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
-    ds = pkg.DeviceScene(ps)
-    monkeypatch.setenv("PBRT_HIP_PIPELINE", "0")
-    ds.render()
-    ref = ds.film_accum()
-    cnt_ref = ds.counters()
-    for occ in ("0", "1"):
-        monkeypatch.setenv("PBRT_HIP_HIGH_OCC", occ)
-        ds.set_counting(False); ds.clear_film(); ds.render()
-        got = ds.film_accum()
-        assert np.array_equal(got, ref), (name, occ, float(np.abs(got - ref).max()))
-    monkeypatch.delenv("PBRT_HIP_HIGH_OCC")
-    for env in (dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="0"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_VERTEX="1"), dict(PBRT_HIP_PIPELINE="1", PBRT_HIP_PIPE_SLOTS="512")):
-        with pytest.MonkeyPatch.context() as mp:
-            for k, v in env.items():
-                mp.setenv(k, v)
-            for counting in (False, True):
-                ds.set_counting(counting); ds.reset_counters(); ds.clear_film(); ds.render()
-                assert ds.last_stats()["pipeline"] == 1
-                got = ds.film_accum()
-                assert np.array_equal(got, ref), (name, env, counting, float(np.abs(got - ref).max()))
-                if counting:
-                    c = ds.counters()
-                    for k in ("camera_rays", "closest_rays", "any_rays", "nodes_visited", "leaf_refs", "tri_tests", "bad_samples"):
-                        assert c[k] == cnt_ref[k], (name, env, k, c[k], cnt_ref[k])
+    ds = pkg.DeviceScene(pkg.ParsedScene(text=load_golden("textures/" + name)["scene"]))
+    assert_flavours_agree(ds, name, PIPELINE_ENVS)
     ds.close()
 
 
@@ -182,19 +116,12 @@ def test_texture_kernel_flavours_give_the_same_film(pkg, name, monkeypatch):
 def test_prebuilt_scene_renders_the_textures(pkg, name):
     """rt_scene_create_prebuilt (the multi-rank path) gives the film of rt_scene_create."""
     need_gpu(pkg)
-    g = load_golden("textures/" + name)
-    ps = pkg.ParsedScene(text=g["scene"])
+    ps = pkg.ParsedScene(text=load_golden("textures/" + name)["scene"])
     a = pkg.DeviceScene(ps)
     a.render()
     ref = a.film_accum()
-    nodes, refs = a.accel_arrays()
-    info = a.accel_info()
     a.close()
-    b = pkg.DeviceScene(ps, prebuilt=(nodes, refs, info))
-    b.render()
-    got = b.film_accum()
-    b.close()
-    assert np.array_equal(got, ref), float(np.abs(got - ref).max())
+    assert_prebuilt_agrees(pkg, ps, ref).close()
 
 
 # ---- rt_scene_set_textures refuses bad input ------------------------------------------------------------------------------------------------

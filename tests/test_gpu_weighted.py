@@ -7,7 +7,8 @@ larger seeded frames against the oracle (whose "weighted" is pinned by those fiv
 their counting twins, both forms of the recurrence kernel (40 lights in lanes, 70 in LDS tables), a medium, the grid, the frames the device refuses."""
 import numpy as np
 import pytest
-from test_gpu_parity import need_gpu, check_film
+from gpu_checks import need_gpu
+from test_gpu_parity import check_film
 
 pytestmark = pytest.mark.gpu
 
