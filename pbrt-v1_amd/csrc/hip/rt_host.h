@@ -1,7 +1,8 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
-// the owners of its device memory, events and stream.  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
+// the owners of its device memory, events and stream, the kernel tables and their resident grids (rt_flavour.h).  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
 // rt_kernels.hip renders (make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
+#include "rt_flavour.h"
 #include "rt_render_kernel.h"
 #include "rt_pipeline.h"
 #include "rt_pipe_vertex.h"
@@ -39,19 +40,28 @@ using namespace rt;
     } while (0)
 #define HIPWARN(expr) rt::hip_warn((expr), #expr)
 
-// render_kernel instantiations live in rt_mega_{w,d,p}.hip, 16 per integrator: k = (VOL*2 + ACCEL)*2 + COUNT for the natural-allocation
-// kernels (0..7; the counting twins always carry the glossy / quadric code, they are not timed), 8 + VOL*2 + ACCEL for the
-// high-occupancy flavour, 12 + VOL*2 + ACCEL for the timed kernels with the glossy (plastic) lobes and quadric slots compiled in
-// (EXT: powf and the second lobe cost ~17 VGPRs, one wave per SIMD less for DirectLighting).  `variant` keeps round 1's numbering:
-// ((VOL*2 + ACCEL)*2 + COUNT)*3 + INTEG | 24 + (VOL*2 + ACCEL)*3 + INTEG | 36 + (VOL*2 + ACCEL)*3 + INTEG.
-namespace rt { extern const RenderKernelFn g_render_kernels_whitted[16], g_render_kernels_direct[16], g_render_kernels_path[16], g_render_kernels_weighted[8]; }
-namespace rt { extern const RenderKernelFn g_render_kernels_bidir[4]; }      // rt_mega_b.hip: k = ACCEL*2 + COUNT
-namespace rt { extern const PipeShadeFn g_pipe_shade_whitted[6], g_pipe_shade_direct[6], g_pipe_shade_path[6]; extern const PipeTraceFn g_pipe_trace[8]; extern const PipeShadeFn g_pipe_vertex[3];
-               extern const PipeMarchFn g_pipe_march[6]; }
-static inline RenderKernelFn render_kernel_of(int variant) {
-    const RenderKernelFn *t = (variant % 3 == 0) ? g_render_kernels_whitted : (variant % 3 == 1) ? g_render_kernels_direct : g_render_kernels_path;
-    return t[variant < 24 ? variant / 3 : variant < 36 ? 8 + (variant - 24) / 3 : 12 + (variant - 36) / 3];
-}
+// The kernel tables of the seven families, one per translation unit that instantiates kernels; rt_flavour.h has their sizes, the order of their
+// entries and index(), the entry a frame takes.  The megakernel and the pipeline's shade kernel have a table per integrator (Whitted, DirectLighting, Path).
+namespace rt {
+extern const flavour::Table<RenderKernelFn, flavour::Mega> g_render_kernels_whitted, g_render_kernels_direct, g_render_kernels_path;
+extern const flavour::Table<RenderKernelFn, flavour::Weighted> g_render_kernels_weighted;
+extern const flavour::Table<RenderKernelFn, flavour::Bidir> g_render_kernels_bidir;
+extern const flavour::Table<PipeShadeFn, flavour::Shade> g_pipe_shade_whitted, g_pipe_shade_direct, g_pipe_shade_path;
+extern const flavour::Table<PipeShadeFn, flavour::Vertex> g_pipe_vertex;
+extern const flavour::Table<PipeTraceFn, flavour::Trace> g_pipe_trace;
+extern const flavour::Table<PipeMarchFn, flavour::March> g_pipe_march;
+}  // namespace rt
+// ... by RtRenderDesc::integrator
+static const flavour::Table<RenderKernelFn, flavour::Mega> *const g_render_kernels[RT_INTEGRATOR_PATH + 1] = {&g_render_kernels_whitted, &g_render_kernels_direct, &g_render_kernels_path};
+static const flavour::Table<PipeShadeFn, flavour::Shade> *const g_pipe_shade[RT_INTEGRATOR_PATH + 1] = {&g_pipe_shade_whitted, &g_pipe_shade_direct, &g_pipe_shade_path};
+// The persistent families are launched with as many blocks as stay resident (scene_create): a grid per table entry
+struct ResidentGrids {
+    flavour::Table<unsigned, flavour::Mega> mega[RT_INTEGRATOR_PATH + 1];
+    flavour::Table<unsigned, flavour::Weighted> weighted;
+    flavour::Table<unsigned, flavour::Bidir> bidir;
+    flavour::Table<unsigned, flavour::Trace> trace;
+    flavour::Table<unsigned, flavour::March> march;
+};
 
 // ---- owners (rt_devbuf.h).  A device block is a DevBuf<T>; the same template with another release function owns page-locked memory, an event and the
 // stream a scene created itself.  rt_kernels.hip defines the release functions, next to rt::dev_alloc / rt::dev_free.
@@ -91,9 +101,7 @@ struct RtScene {
     DevBuf<uint2> spill;
     DevBuf<float> frames;
     unsigned grid = 0, n_threads = 0;
-    unsigned grids[48] = {0};          // resident grid per render_kernel<COUNT, INTEG> instantiation
-    unsigned wgrids[8] = {0};          // ... of the DirectLighting "weighted" family (rt_mega_dw.hip)
-    unsigned bgrids[4] = {0};          // ... of the bidirectional integrator's (rt_mega_b.hip)
+    ResidentGrids grids{};             // grid: the largest of the megakernel families, n_threads: of all
     DevBuf<DimReq> light_dims;         // DirectLighting "all": the per-light sample requests (make_frame); the bidirectional integrator: its BidirTable
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
@@ -127,7 +135,6 @@ struct RtScene {
     // queue pipeline (rt_pipeline.h)
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
     Pinned<unsigned> h_qcount;                          // page-locked mirror of q_count (termination test)
-    unsigned trace_grids[8] = {0}, march_grids[6] = {0};
     bool last_pipeline = false, last_marches = false; int pipe_iters = 0, pipe_timed = 0; unsigned pipe_slots = 0;
     DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;

@@ -1,5 +1,5 @@
 // rt_kernels.hip -- the render path of libpbrt_hip.so's C ABI (include/pbrt_hip.h): make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*.
-// (Scene create: rt_scene.hip.  Film kernels and rt_film_*: rt_film.hip.  Shared host declarations: rt_host.h.)
+// (Scene create: rt_scene.hip.  Film kernels and rt_film_*: rt_film.hip.  Shared host declarations: rt_host.h.  Which kernel instantiation: rt_flavour.h.)
 //
 // Kernels
 //   render_kernel   persistent-thread wavefront renderer: Scene::Render's sample loop (scene.cpp:42-84).
@@ -84,6 +84,11 @@ static int bind_scratch(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, size_t
     return ensure_material_pool(s, fr, w.mat_levels, n);
 }
 
+// What a frame asks of the kernel tables (rt_flavour.h: each family's index() turns it into the entry to launch); rt_trace_* have no frame
+static flavour::Request request_of(const RtScene *s, const RtRenderDesc *rd = nullptr, const DevFrame *fr = nullptr) {
+    return flavour::Request{rd ? rd->integrator : 0, s->accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->counting, s->has_ext, fr && fr->high_occupancy};
+}
+
 // The queue pipeline: alternate a shade kernel (pipe_shade_kernel, or pipe_vertex_kernel for a path without a medium) and pipe_trace_kernel
 // until a shade pass enqueues no ray.  The host learns the queue sizes RT_PIPE_BATCH iterations late (page-locked copy + fence event per
 // batch), so the GPU never waits for it; the iterations launched after the last productive one find every slot in ST_EXIT and return at once.
@@ -128,16 +133,15 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
         for (auto &e : s->pipe_ev) HIPCHK(hipEventCreate(&e.p));
         for (auto &e : s->pipe_fence) HIPCHK(hipEventCreateWithFlags(&e.p, hipEventDisableTiming));
     }
-    const int f = s->counting ? 1 : (s->has_ext ? 2 : 0);
-    const PipeShadeFn *st = integ == RT_INTEGRATOR_WHITTED ? g_pipe_shade_whitted : integ == RT_INTEGRATOR_DIRECT ? g_pipe_shade_direct : g_pipe_shade_path;
-    const PipeShadeFn shade = by_vertex ? g_pipe_vertex[f] : st[(s->volume.present ? 3 : 0) + f];
-    const int tk = (s->accel_kind == RT_ACCEL_GRID ? 4 : 0) + (s->counting ? (s->has_ext ? 1 : 3) : (s->has_ext ? 2 : 0));
+    const flavour::Request rq = request_of(s, rd, &fr);
+    const PipeShadeFn shade = by_vertex ? g_pipe_vertex[flavour::Vertex::index(rq)] : (*g_pipe_shade[integ])[flavour::Shade::index(rq)];
+    const int tk = flavour::Trace::index(rq);
     const PipeTraceFn trace = g_pipe_trace[tk];
-    const unsigned trace_grid = s->trace_grids[tk];
+    const unsigned trace_grid = s->grids.trace[tk];
     // frames with a medium: the march kernel (rt_pipe_march.h) runs the ray marches the shade pass parked
     const bool marches = s->volume.present;
-    const int mk = (s->accel_kind == RT_ACCEL_GRID ? 3 : 0) + f;
-    const unsigned march_grid = s->march_grids[mk];
+    const int mk = flavour::March::index(rq);
+    const unsigned march_grid = s->grids.march[mk];
     HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemcpyAsync(s->dev_pool, &pl, sizeof(PipePool), hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemsetAsync(s->work_counter, 0, sizeof(unsigned long long), s->stream));
@@ -189,22 +193,160 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     s->last_marches = marches;
     s->pipe_slots = n_slots; s->pipe_iters = checked + 1; s->pipe_timed = std::min(s->pipe_iters, RT_PIPE_TIMED);
     HIPCHK(hipEventRecord(s->ev1, s->stream));
-    s->last_pipeline = true;
     return RT_OK;
 }
 
-// The bidirectional integrator: rt::bidir_kernel (rt_bidir.h), k = ACCEL*2 + COUNT, with the eight path vertices of every thread in s->frames
+// The bidirectional integrator: rt::bidir_kernel (rt_bidir.h), with the eight path vertices of every thread in s->frames
 static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-    const int bk = (s->accel_kind == RT_ACCEL_GRID ? 2 : 0) + (s->counting ? 1 : 0);
-    if (s->bgrids[bk] == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    const int k = flavour::Bidir::index(request_of(s, rd, &fr));
+    const unsigned grid = s->grids.bidir[k];
+    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
     HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
     HIPCHK(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(g_render_kernels_bidir[bk], dim3(s->bgrids[bk]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
+    hipLaunchKernelGGL(g_render_kernels_bidir[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev1, s->stream));
-    s->last_pipeline = false; s->last_weighted = false;
+    return RT_OK;
+}
+
+// The megakernel of Whitted, DirectLighting "all" / "one" and Path: one launch of rt::render_kernel
+static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+    int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
+    const int k = flavour::Mega::index(request_of(s, rd, &fr));
+    const unsigned grid = s->grids.mega[rd->integrator][k];
+    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+#ifdef RT_TAIL_PROBE
+    static unsigned long long *probe = nullptr;
+    const size_t n_waves = size_t(grid) * (RT_BLOCK / 64);
+    if (!probe) HIPCHK(hipMalloc((void **)&probe, size_t(s->n_threads / 64 + 64) * 4 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(probe, 0, n_waves * 4 * sizeof(unsigned long long), s->stream));
+    fr.probe = probe;
+#endif
+    HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
+    HIPCHK(hipEventRecord(s->ev0, s->stream));
+    hipLaunchKernelGGL((*g_render_kernels[rd->integrator])[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev1, s->stream));
+#ifdef RT_TAIL_PROBE
+    {   // the launch's timeline: when the waves started, when each found the work list empty, when each ended (10 ns ticks of s_memrealtime)
+        std::vector<unsigned long long> h(n_waves * 4);
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipMemcpy(h.data(), probe, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, t0max = 0, e0 = ~0ull, e1 = 0, x1 = 0, smin = ~0ull, smax = 0, stot = 0;
+        std::vector<double> ends, drain;
+        for (size_t w = 0; w < n_waves; ++w) {
+            const unsigned long long *r = &h[4 * w];
+            if (!r[2]) continue;
+            t0 = std::min(t0, r[0]); t0max = std::max(t0max, r[0]); x1 = std::max(x1, r[2]);
+            if (r[1]) { e0 = std::min(e0, r[1]); e1 = std::max(e1, r[1]); drain.push_back(double(r[2] - r[1]) * 1e-2); }
+            smin = std::min(smin, r[3]); smax = std::max(smax, r[3]); stot += r[3];
+            ends.push_back(double(r[2]));
+        }
+        std::sort(ends.begin(), ends.end()); std::sort(drain.begin(), drain.end());
+        auto q = [&](const std::vector<double> &v, double f) { return v.empty() ? 0.0 : v[size_t(f * (v.size() - 1))]; };
+        std::fprintf(stderr, "RT_TAIL_PROBE waves=%zu span=%.1f us | starts spread %.1f us | list first seen empty at %.1f us, last at %.1f us | wave ends (us after start): p1 %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f | "
+                             "drain per wave (end - empty, us): p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f | samples per wave min %llu mean %.1f max %llu\n",
+                     ends.size(), double(x1 - t0) * 1e-2, double(t0max - t0) * 1e-2, double(e0 - t0) * 1e-2, double(e1 - t0) * 1e-2,
+                     (q(ends, .01) - double(t0)) * 1e-2, (q(ends, .1) - double(t0)) * 1e-2, (q(ends, .5) - double(t0)) * 1e-2, (q(ends, .9) - double(t0)) * 1e-2, (q(ends, .99) - double(t0)) * 1e-2, (q(ends, 1.) - double(t0)) * 1e-2,
+                     q(drain, .1), q(drain, .5), q(drain, .9), q(drain, .99), q(drain, 1.), smin, double(stot) / double(std::max<size_t>(ends.size(), 1)), smax);
+    }
+#endif
+    return RT_OK;
+}
+
+// DirectLighting "weighted" (rt_weighted.h): count -> scan -> survey -> recurrence -> the frame.  ev0 .. ev1 bracket all of it (kernel_ms of a weighted frame
+// is the five together)
+static int render_weighted(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+    int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
+    const int k = flavour::Weighted::index(request_of(s, rd, &fr));
+    const unsigned grid = s->grids.weighted[k];
+    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    const int nL = int(s->dev.n_lights), R = 1 + 2 * nL;
+    if (!s->wt_total) HIPCHK(hipHostMalloc((void **)&s->wt_total.p, sizeof(unsigned long long), hipHostMallocDefault));
+    if ((rc = s->wt_sums.grow(RT_WSCAN_BLOCKS))) return rc;
+    for (Event &e : s->wt_ev) if (!e) HIPCHK(hipEventCreate(&e.p));
+    rc = ensure(s, s->wt_base, size_t(fr.total_work) + 1); if (rc) return rc;
+    fr.wt_base = s->wt_base;
+    auto pass = [&](int phase) -> int {
+        fr.weighted_phase = phase;
+        HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
+        hipLaunchKernelGGL(g_render_kernels_weighted[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
+        HIPCHK(hipGetLastError());
+        return RT_OK;
+    };
+    HIPCHK(hipEventRecord(s->ev0, s->stream));
+    if ((rc = pass(1))) return rc;
+    HIPCHK(hipEventRecord(s->wt_ev[0], s->stream));
+    hipLaunchKernelGGL(weighted_scan_sums_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, (const unsigned *)s->wt_base, (unsigned long long)fr.total_work, s->wt_sums);
+    hipLaunchKernelGGL(weighted_scan_top_kernel, dim3(1), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_base, (unsigned long long)fr.total_work, s->wt_sums, s->wt_total);
+    hipLaunchKernelGGL(weighted_scan_apply_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_base, (unsigned long long)fr.total_work, (const unsigned long long *)s->wt_sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->wt_ev[1], s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const unsigned long long n_points = *s->wt_total;
+    // The one place where rt_render can fail AFTER it has launched work (the number of shading points is only known once the count pass has run;
+    // pbrt_hip.h says so): the film and the sample buffer are untouched (the count pass writes neither), the scene is left without a last frame.
+    auto late_fail = [&](int code, const char *msg) { s->last_weighted = false; s->last_pipeline = false; s->have_timing = false; s->wt_points = 0; return fail(code, msg); };
+    if (n_points >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 shading points in the frame");
+    s->wt_points = n_points;
+    const bool mixed = s->light_draws < 0;
+    const int nD = int(s->n_drawing_lights);
+    size_t rec_floats = size_t(n_points) * size_t(R);
+    fr.wt_mixed = mixed ? 1 : 0; fr.wt_nd = unsigned(nD); fr.wt_recbase = nullptr;
+    if (mixed) {
+        // A sample with P shading points keeps P * A + nD * P * (P + 1) floats: quadratic in P, and sum P (P + 1) >= W * Pavg * (Pavg + 1) for W samples of
+        // Pavg points on average (convexity) -- a frame that cannot fit even by that lower bound is refused here, before the size scan is launched
+        {
+            const double W = double(fr.total_work ? fr.total_work : 1), Pavg = double(n_points) / W;
+            const double at_least = double(n_points) * double(1 + 2 * (nL - nD)) + double(nD) * W * Pavg * (Pavg + 1.0);
+            if (at_least >= 4294967295.0) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\" with lights of mixed RNG use: the survey's records exceed 2^32 floats (quadratic in a sample's shading points)");
+        }
+        // where every sample's records start: per-sample sizes from the point counts (P * A + nD * P * (P + 1)), scanned like the counts were
+        rc = ensure(s, s->wt_recbase, size_t(fr.total_work) + 1); if (rc) return late_fail(rc, rt::last_error());
+        const unsigned long long nw = fr.total_work;
+        if (nw) hipLaunchKernelGGL(weighted_sizes_kernel, dim3(unsigned((nw + 255) / 256)), dim3(256), 0, s->stream, (const unsigned *)s->wt_base, nw, unsigned(1 + 2 * (nL - nD)), unsigned(nD), s->wt_recbase);
+        hipLaunchKernelGGL(weighted_scan_sums_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, (const unsigned *)s->wt_recbase, nw, s->wt_sums);
+        hipLaunchKernelGGL(weighted_scan_top_kernel, dim3(1), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_recbase, nw, s->wt_sums, s->wt_total);
+        hipLaunchKernelGGL(weighted_scan_apply_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_recbase, nw, (const unsigned long long *)s->wt_sums);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (*s->wt_total >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\" with lights of mixed RNG use: the survey's records exceed 2^32 floats");
+        rec_floats = size_t(*s->wt_total);
+        fr.wt_recbase = s->wt_recbase;
+    }
+    rc = ensure(s, s->wt_rec, rec_floats + 1); if (rc) return late_fail(rc, rt::last_error());
+    rc = ensure(s, s->wt_pick, size_t(n_points) + 1); if (rc) return late_fail(rc, rt::last_error());
+    fr.wt_rec = s->wt_rec; fr.wt_pick = s->wt_pick;
+    if (n_points > 0) {
+        if ((rc = pass(2))) return rc;
+        HIPCHK(hipEventRecord(s->wt_ev[2], s->stream));
+        // LDS of the recurrence kernel: [state | chunk records | chunk picks] within 64 KB
+        const size_t state_f = nL <= 64 ? 0 : size_t((3 * nL + 2) & ~1);
+        int chunk = int((size_t(64) * 1024 / 4 - state_f - 2) / size_t(R + 2));
+        chunk = chunk > 1024 ? 1024 : chunk < 1 ? 1 : chunk;
+        const size_t lds = (state_f + size_t((chunk * R + 1) & ~1) + size_t(chunk) * 2) * sizeof(float);
+        if (mixed) {
+            // LDS of the general form: [5 nL + 1 state | 2 x (group + 1) sample offsets | staged records | staged picks] within 64 KB
+            const int group = 256;
+            const size_t fixed = size_t(5 * nL + 2) + 2 * size_t(group + 1);
+            const size_t room = size_t(64) * 1024 / 4 - fixed - 4;
+            const int cap_points = int(room / 4 / 2), cap_floats = int(room - size_t(cap_points) * 2) & ~1;     // a quarter of the room for the picks (2 floats each)
+            const size_t mlds = (fixed + size_t(cap_floats) + 2 + size_t(cap_points) * 2) * sizeof(float);
+            hipLaunchKernelGGL(weighted_recurrence_mixed_kernel, dim3(1), dim3(64), mlds, s->stream, (const float *)s->wt_rec, s->wt_pick, (const unsigned *)s->wt_base,
+                               (const unsigned *)s->wt_recbase, (unsigned long long)fr.total_work, nL, nD, s->light_draw_flags, group, cap_floats, cap_points);
+        } else {
+            auto rk = nL <= 64 ? weighted_recurrence_lanes_kernel : weighted_recurrence_lds_kernel;      // light i in lane i | tables in LDS, one lane
+            hipLaunchKernelGGL(rk, dim3(1), dim3(64), lds, s->stream, (const float *)s->wt_rec, s->wt_pick, n_points, nL, chunk);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(s->wt_ev[3], s->stream));
+    } else { HIPCHK(hipEventRecord(s->wt_ev[2], s->stream)); HIPCHK(hipEventRecord(s->wt_ev[3], s->stream)); }
+    if ((rc = pass(3))) return rc;
+    HIPCHK(hipEventRecord(s->ev1, s->stream));
     return RT_OK;
 }
 
@@ -448,9 +590,11 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
     TraceJob job{};
     job.q_o = s->trace_buf; job.q_d = s->trace_buf + n; job.q_slot = nullptr; job.q_count = s->trace_qc; job.hit = s->trace_buf + 2 * size_t(n);
     job.n_slots = 0; job.spill = s->spill; job.n_threads = s->n_threads; job.counters = s->counters;
-    const int k = (s->accel_kind == RT_ACCEL_GRID ? 4 : 0) + (s->has_ext ? 1 : 3);
+    flavour::Request rq = request_of(s);
+    rq.count = true;                                            // whatever rt_set_counting says
+    const int k = flavour::Trace::index(rq);
     HIPWARN(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->trace_grids[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
+    hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
     HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream)); s->have_timing = true; s->last_pipeline = false;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host.data(), s->trace_buf + 2 * size_t(n), size_t(n) * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
@@ -464,6 +608,8 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
 }
 int rt_trace_closest(RtScene *s, const RtRay *rays, uint32_t n, RtHit *hits_out) { return trace_common(s, rays, n, 0, hits_out, nullptr); }
 int rt_trace_any(RtScene *s, const RtRay *rays, uint32_t n, uint8_t *occluded_out) { return trace_common(s, rays, n, 1, nullptr, occluded_out); }
+// Validate, bound the medium's marches, size the sample buffer, hand the frame to one of render_pipeline / render_bidir / render_weighted / render_mega,
+// then the film gather.  Which instantiation each of the four launches is rt_flavour.h's index() of request_of(s, rd, &fr).
 int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (!s || !rd) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
@@ -554,147 +700,11 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
     s->rendered = true;
-    if (fr.pipeline) {
-        rc = render_pipeline(s, rd, fr); if (rc) return rc;
-        s->last_weighted = false;
-    } else if (bidir) {                                       // a kernel family of its own, ahead of the variant arithmetic of the three megakernel integrators
-        rc = render_bidir(s, rd, fr); if (rc) return rc;
-    } else {
-        rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-        int variant = (((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 2 + (s->counting ? 1 : 0)) * 3 + rd->integrator;
-        if (fr.high_occupancy && !s->counting) variant = 24 + ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 3 + rd->integrator;
-        if (s->has_ext && !s->counting) variant = 36 + ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 3 + rd->integrator;
-        if (s->grids[variant] == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
-        fr.weighted_phase = 0; fr.wt_base = nullptr; fr.wt_rec = nullptr; fr.wt_pick = nullptr; fr.wt_mixed = 0; fr.wt_nd = 0; fr.wt_recbase = nullptr;
-        if (weighted) {
-            // rt_weighted.h: count -> scan -> survey -> recurrence -> the frame.  ev0 .. ev1 bracket all of it (kernel_ms of a weighted frame is the five together)
-            const int wk = ((s->volume.present ? 1 : 0) * 2 + (s->accel_kind == RT_ACCEL_GRID ? 1 : 0)) * 2 + (s->counting ? 1 : 0);
-            const int nL = int(s->dev.n_lights), R = 1 + 2 * nL;
-            if (!s->wt_total) HIPCHK(hipHostMalloc((void **)&s->wt_total.p, sizeof(unsigned long long), hipHostMallocDefault));
-            if ((rc = s->wt_sums.grow(RT_WSCAN_BLOCKS))) return rc;
-            for (Event &e : s->wt_ev) if (!e) HIPCHK(hipEventCreate(&e.p));
-            rc = ensure(s, s->wt_base, size_t(fr.total_work) + 1); if (rc) return rc;
-            fr.wt_base = s->wt_base;
-            auto pass = [&](int phase) -> int {
-                fr.weighted_phase = phase;
-                HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-                HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-                hipLaunchKernelGGL(g_render_kernels_weighted[wk], dim3(s->wgrids[wk]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
-                HIPCHK(hipGetLastError());
-                return RT_OK;
-            };
-            HIPCHK(hipEventRecord(s->ev0, s->stream));
-            if ((rc = pass(1))) return rc;
-            HIPCHK(hipEventRecord(s->wt_ev[0], s->stream));
-            hipLaunchKernelGGL(weighted_scan_sums_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, (const unsigned *)s->wt_base, (unsigned long long)fr.total_work, s->wt_sums);
-            hipLaunchKernelGGL(weighted_scan_top_kernel, dim3(1), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_base, (unsigned long long)fr.total_work, s->wt_sums, s->wt_total);
-            hipLaunchKernelGGL(weighted_scan_apply_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_base, (unsigned long long)fr.total_work, (const unsigned long long *)s->wt_sums);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(s->wt_ev[1], s->stream));
-            HIPCHK(hipStreamSynchronize(s->stream));
-            const unsigned long long n_points = *s->wt_total;
-            // The one place where rt_render can fail AFTER it has launched work (the number of shading points is only known once the count pass has run;
-            // pbrt_hip.h says so): the film and the sample buffer are untouched (the count pass writes neither), the scene is left without a last frame.
-            auto late_fail = [&](int code, const char *msg) { s->last_weighted = false; s->last_pipeline = false; s->have_timing = false; s->wt_points = 0; return fail(code, msg); };
-            if (n_points >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 shading points in the frame");
-            s->wt_points = n_points;
-            const bool mixed = s->light_draws < 0;
-            const int nD = int(s->n_drawing_lights);
-            size_t rec_floats = size_t(n_points) * size_t(R);
-            fr.wt_mixed = mixed ? 1 : 0; fr.wt_nd = unsigned(nD); fr.wt_recbase = nullptr;
-            if (mixed) {
-                // A sample with P shading points keeps P * A + nD * P * (P + 1) floats: quadratic in P, and sum P (P + 1) >= W * Pavg * (Pavg + 1) for W samples of
-                // Pavg points on average (convexity) -- a frame that cannot fit even by that lower bound is refused here, before the size scan is launched
-                {
-                    const double W = double(fr.total_work ? fr.total_work : 1), Pavg = double(n_points) / W;
-                    const double at_least = double(n_points) * double(1 + 2 * (nL - nD)) + double(nD) * W * Pavg * (Pavg + 1.0);
-                    if (at_least >= 4294967295.0) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\" with lights of mixed RNG use: the survey's records exceed 2^32 floats (quadratic in a sample's shading points)");
-                }
-                // where every sample's records start: per-sample sizes from the point counts (P * A + nD * P * (P + 1)), scanned like the counts were
-                rc = ensure(s, s->wt_recbase, size_t(fr.total_work) + 1); if (rc) return late_fail(rc, rt_last_error());
-                const unsigned long long nw = fr.total_work;
-                if (nw) hipLaunchKernelGGL(weighted_sizes_kernel, dim3(unsigned((nw + 255) / 256)), dim3(256), 0, s->stream, (const unsigned *)s->wt_base, nw, unsigned(1 + 2 * (nL - nD)), unsigned(nD), s->wt_recbase);
-                hipLaunchKernelGGL(weighted_scan_sums_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, (const unsigned *)s->wt_recbase, nw, s->wt_sums);
-                hipLaunchKernelGGL(weighted_scan_top_kernel, dim3(1), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_recbase, nw, s->wt_sums, s->wt_total);
-                hipLaunchKernelGGL(weighted_scan_apply_kernel, dim3(RT_WSCAN_BLOCKS), dim3(RT_WSCAN_THREADS), 0, s->stream, s->wt_recbase, nw, (const unsigned long long *)s->wt_sums);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(s->stream));
-                if (*s->wt_total >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\" with lights of mixed RNG use: the survey's records exceed 2^32 floats");
-                rec_floats = size_t(*s->wt_total);
-                fr.wt_recbase = s->wt_recbase;
-            }
-            rc = ensure(s, s->wt_rec, rec_floats + 1); if (rc) return late_fail(rc, rt_last_error());
-            rc = ensure(s, s->wt_pick, size_t(n_points) + 1); if (rc) return late_fail(rc, rt_last_error());
-            fr.wt_rec = s->wt_rec; fr.wt_pick = s->wt_pick;
-            if (n_points > 0) {
-                if ((rc = pass(2))) return rc;
-                HIPCHK(hipEventRecord(s->wt_ev[2], s->stream));
-                // LDS of the recurrence kernel: [state | chunk records | chunk picks] within 64 KB
-                const size_t state_f = nL <= 64 ? 0 : size_t((3 * nL + 2) & ~1);
-                int chunk = int((size_t(64) * 1024 / 4 - state_f - 2) / size_t(R + 2));
-                chunk = chunk > 1024 ? 1024 : chunk < 1 ? 1 : chunk;
-                const size_t lds = (state_f + size_t((chunk * R + 1) & ~1) + size_t(chunk) * 2) * sizeof(float);
-                if (mixed) {
-                    // LDS of the general form: [5 nL + 1 state | 2 x (group + 1) sample offsets | staged records | staged picks] within 64 KB
-                    const int group = 256;
-                    const size_t fixed = size_t(5 * nL + 2) + 2 * size_t(group + 1);
-                    const size_t room = size_t(64) * 1024 / 4 - fixed - 4;
-                    const int cap_points = int(room / 4 / 2), cap_floats = int(room - size_t(cap_points) * 2) & ~1;     // a quarter of the room for the picks (2 floats each)
-                    const size_t mlds = (fixed + size_t(cap_floats) + 2 + size_t(cap_points) * 2) * sizeof(float);
-                    hipLaunchKernelGGL(weighted_recurrence_mixed_kernel, dim3(1), dim3(64), mlds, s->stream, (const float *)s->wt_rec, s->wt_pick, (const unsigned *)s->wt_base,
-                                       (const unsigned *)s->wt_recbase, (unsigned long long)fr.total_work, nL, nD, s->light_draw_flags, group, cap_floats, cap_points);
-                } else {
-                auto rk = nL <= 64 ? weighted_recurrence_lanes_kernel : weighted_recurrence_lds_kernel;      // light i in lane i | tables in LDS, one lane
-                hipLaunchKernelGGL(rk, dim3(1), dim3(64), lds, s->stream, (const float *)s->wt_rec, s->wt_pick, n_points, nL, chunk);
-                }
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(s->wt_ev[3], s->stream));
-            } else { HIPCHK(hipEventRecord(s->wt_ev[2], s->stream)); HIPCHK(hipEventRecord(s->wt_ev[3], s->stream)); }
-            if ((rc = pass(3))) return rc;
-            HIPCHK(hipEventRecord(s->ev1, s->stream));
-            s->last_pipeline = false; s->last_weighted = true;
-        } else {
-#ifdef RT_TAIL_PROBE
-        static unsigned long long *probe = nullptr;
-        const size_t n_waves = size_t(s->grids[variant]) * (RT_BLOCK / 64);
-        if (!probe) HIPCHK(hipMalloc((void **)&probe, size_t(s->n_threads / 64 + 64) * 4 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(probe, 0, n_waves * 4 * sizeof(unsigned long long), s->stream));
-        fr.probe = probe;
-#endif
-        HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-        HIPCHK(hipEventRecord(s->ev0, s->stream));
-        hipLaunchKernelGGL(render_kernel_of(variant), dim3(s->grids[variant]), dim3(RT_BLOCK), 0, s->stream,
-                           (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(s->ev1, s->stream));
-#ifdef RT_TAIL_PROBE
-        {   // the launch's timeline: when the waves started, when each found the work list empty, when each ended (10 ns ticks of s_memrealtime)
-            std::vector<unsigned long long> h(n_waves * 4);
-            HIPCHK(hipStreamSynchronize(s->stream));
-            HIPCHK(hipMemcpy(h.data(), probe, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            unsigned long long t0 = ~0ull, t0max = 0, e0 = ~0ull, e1 = 0, x1 = 0, smin = ~0ull, smax = 0, stot = 0;
-            std::vector<double> ends, drain;
-            for (size_t w = 0; w < n_waves; ++w) {
-                const unsigned long long *r = &h[4 * w];
-                if (!r[2]) continue;
-                t0 = std::min(t0, r[0]); t0max = std::max(t0max, r[0]); x1 = std::max(x1, r[2]);
-                if (r[1]) { e0 = std::min(e0, r[1]); e1 = std::max(e1, r[1]); drain.push_back(double(r[2] - r[1]) * 1e-2); }
-                smin = std::min(smin, r[3]); smax = std::max(smax, r[3]); stot += r[3];
-                ends.push_back(double(r[2]));
-            }
-            std::sort(ends.begin(), ends.end()); std::sort(drain.begin(), drain.end());
-            auto q = [&](const std::vector<double> &v, double f) { return v.empty() ? 0.0 : v[size_t(f * (v.size() - 1))]; };
-            std::fprintf(stderr, "RT_TAIL_PROBE waves=%zu span=%.1f us | starts spread %.1f us | list first seen empty at %.1f us, last at %.1f us | wave ends (us after start): p1 %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f | "
-                                 "drain per wave (end - empty, us): p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f | samples per wave min %llu mean %.1f max %llu\n",
-                         ends.size(), double(x1 - t0) * 1e-2, double(t0max - t0) * 1e-2, double(e0 - t0) * 1e-2, double(e1 - t0) * 1e-2,
-                         (q(ends, .01) - double(t0)) * 1e-2, (q(ends, .1) - double(t0)) * 1e-2, (q(ends, .5) - double(t0)) * 1e-2, (q(ends, .9) - double(t0)) * 1e-2, (q(ends, .99) - double(t0)) * 1e-2, (q(ends, 1.) - double(t0)) * 1e-2,
-                         q(drain, .1), q(drain, .5), q(drain, .9), q(drain, .99), q(drain, 1.), smin, double(stot) / double(std::max<size_t>(ends.size(), 1)), smax);
-        }
-#endif
-        s->last_pipeline = false; s->last_weighted = false;
-        }
-    }
+    // ---- the frame, by one of the four launch functions
+    rc = fr.pipeline ? render_pipeline(s, rd, fr) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr);
+    if (rc) return rc;
+    s->last_pipeline = fr.pipeline != 0; s->last_weighted = weighted;
+    // ---- film gather and events
     if (!skip_film) { rc = film_gather_launch(s, fr, fg, (const DevFrame *)s->dev_frame, 0, fr.y_pixel_count); if (rc) return rc; }
     HIPCHK(hipEventRecord(s->ev2, s->stream));
     s->have_timing = true;

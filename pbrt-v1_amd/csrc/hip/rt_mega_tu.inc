@@ -1,17 +1,6 @@
-// rt_mega_tu.inc -- one integrator's 16 instantiations of rt::render_kernel (see render_kernel_of in rt_kernels.hip)
+// rt_mega_tu.inc -- one integrator's instantiations of rt::render_kernel, in the order of flavour::Mega (rt_flavour.h)
 #include "rt_render_kernel.h"
+#include "rt_flavour.h"
 namespace rt {
-#define RT_K(C, A, V, W, G) render_kernel<C, RT_TU_INTEG, A, V, W, G>
-// waves per SIMD the timed natural-allocation kernels (no medium, no EXT) are held to: DirectLighting's kd-tree kernel allocates 170 VGPRs on
-// its own, 2 above the 3-wave step of gfx950 (168); asking for 3 waves costs two spilled registers and buys the third wave
-#ifndef RT_TU_NAT_WAVES
-#define RT_TU_NAT_WAVES RT_MIN_WAVES
-#endif
-extern const RenderKernelFn RT_TU_TABLE[16];
-const RenderKernelFn RT_TU_TABLE[16] = {
-    RT_K(false, 0, false, RT_TU_NAT_WAVES, false), RT_K(true, 0, false, RT_MIN_WAVES, true), RT_K(false, 1, false, RT_TU_NAT_WAVES, false), RT_K(true, 1, false, RT_MIN_WAVES, true),
-    RT_K(false, 0, true, RT_MIN_WAVES, false),  RT_K(true, 0, true, RT_MIN_WAVES, true),  RT_K(false, 1, true, RT_MIN_WAVES, false),  RT_K(true, 1, true, RT_MIN_WAVES, true),
-    RT_K(false, 0, false, RT_HIGH_OCC_WAVES, false), RT_K(false, 1, false, RT_HIGH_OCC_WAVES, false), RT_K(false, 0, true, RT_HIGH_OCC_WAVES, false), RT_K(false, 1, true, RT_HIGH_OCC_WAVES, false),
-    RT_K(false, 0, false, RT_MIN_WAVES, true), RT_K(false, 1, false, RT_MIN_WAVES, true), RT_K(false, 0, true, RT_MIN_WAVES, true), RT_K(false, 1, true, RT_MIN_WAVES, true)};
-#undef RT_K
+RT_FLAVOUR_TABLE(RT_TU_TABLE, RenderKernelFn, Mega, Mega::flavour(K, RT_TU_INTEG), render_kernel<f.count, RT_TU_INTEG, f.accel, f.vol, f.waves, f.ext>)
 }  // namespace rt

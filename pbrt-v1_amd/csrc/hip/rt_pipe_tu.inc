@@ -1,10 +1,6 @@
-// rt_pipe_tu.inc -- one integrator's 6 instantiations of rt::pipe_shade_kernel: k = VOL*3 + f, f = 0: timed, 1: counting twin
-// (carries the glossy / quadric code), 2: timed with the glossy / quadric code (EXT)
+// rt_pipe_tu.inc -- one integrator's instantiations of rt::pipe_shade_kernel, in the order of flavour::Shade (rt_flavour.h)
 #include "rt_pipeline.h"
+#include "rt_flavour.h"
 namespace rt {
-#define RT_K(C, V, G) pipe_shade_kernel<C, RT_TU_INTEG, V, G>
-extern const PipeShadeFn RT_TU_TABLE[6];
-const PipeShadeFn RT_TU_TABLE[6] = {RT_K(false, false, false), RT_K(true, false, true), RT_K(false, false, true),
-                                    RT_K(false, true, false),  RT_K(true, true, true),  RT_K(false, true, true)};
-#undef RT_K
+RT_FLAVOUR_TABLE(RT_TU_TABLE, PipeShadeFn, Shade, Shade::flavour(K), pipe_shade_kernel<f.count, RT_TU_INTEG, f.vol, f.ext>)
 }  // namespace rt

@@ -1,6 +1,6 @@
-// rt_pipe_v.hip -- rt::pipe_vertex_kernel (rt_pipe_vertex.h): f = 0: timed, 1: counting twin (carries the glossy / quadric code), 2: timed with that code (EXT)
+// rt_pipe_v.hip -- rt::pipe_vertex_kernel (rt_pipe_vertex.h), in the order of flavour::Vertex (rt_flavour.h)
 #include "rt_pipe_vertex.h"
+#include "rt_flavour.h"
 namespace rt {
-extern const PipeShadeFn g_pipe_vertex[3];
-const PipeShadeFn g_pipe_vertex[3] = {pipe_vertex_kernel<false, false>, pipe_vertex_kernel<true, true>, pipe_vertex_kernel<false, true>};
+RT_FLAVOUR_TABLE(g_pipe_vertex, PipeShadeFn, Vertex, Vertex::flavour(K), pipe_vertex_kernel<f.count, f.ext>)
 }  // namespace rt

@@ -527,19 +527,21 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     unsigned trace_per_cu = ~0u;
     if (const char *e = knob("PBRT_HIP_TRACE_BLOCKS_PER_CU")) trace_per_cu = unsigned(std::max(1, std::atoi(e)));   // occupancy experiments
     unsigned mx = 0;                                            // the largest grid of a family
-    auto resident = [&](const void *kernel, unsigned &grid, unsigned at_most = ~0u) -> int {      // kernel -> resident blocks x CUs
-        int per_cu = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RT_BLOCK, 0));
-        grid = unsigned(prop.multiProcessorCount) * std::max(1u, std::min(unsigned(std::max(per_cu, 0)), at_most));
-        mx = std::max(mx, grid);
+    auto resident = [&](const auto &kernels, auto &grids, unsigned at_most = ~0u) -> int {      // a family's kernels -> resident blocks x CUs
+        static_assert(sizeof kernels / sizeof kernels[0] == sizeof grids / sizeof grids[0], "a grid per table entry");
+        for (size_t k = 0; k < kernels.size(); ++k) {
+            int per_cu = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernels[k], RT_BLOCK, 0));
+            grids[k] = unsigned(prop.multiProcessorCount) * std::max(1u, std::min(unsigned(std::max(per_cu, 0)), at_most));
+            mx = std::max(mx, grids[k]);
+        }
         return RT_OK;
     };
-    for (int k = 0; k < 48; ++k) if ((rc = resident((const void *)render_kernel_of(k), s->grids[k]))) return rc;
-    for (int k = 0; k < 8; ++k) if ((rc = resident((const void *)g_render_kernels_weighted[k], s->wgrids[k]))) return rc;
-    for (int k = 0; k < 4; ++k) if ((rc = resident((const void *)g_render_kernels_bidir[k], s->bgrids[k]))) return rc;
+    ResidentGrids &g = s->grids;
+    for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) if ((rc = resident(*g_render_kernels[i], g.mega[i]))) return rc;
+    if ((rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir))) return rc;
     s->grid = mx;                                               // ... of the megakernels
-    for (int k = 0; k < 8; ++k) if ((rc = resident((const void *)g_pipe_trace[k], s->trace_grids[k], trace_per_cu))) return rc;
-    for (int k = 0; k < 6; ++k) if ((rc = resident((const void *)g_pipe_march[k], s->march_grids[k]))) return rc;
+    if ((rc = resident(g_pipe_trace, g.trace, trace_per_cu)) || (rc = resident(g_pipe_march, g.march))) return rc;
     s->n_threads = mx * RT_BLOCK;                               // ... of all: the spill area is shared
     s->spill_depth = s->tree.max_depth > RT_TRACE_STACK ? s->tree.max_depth - RT_TRACE_STACK + 1 : 1;     // RT_TRACE_STACK <= RT_STACK_LDS
     if ((rc = s->work_counter.grow(64))) return rc;             // 8 band counters, one 64-byte line each (the pipeline uses the first)
