@@ -183,6 +183,16 @@ typedef struct RtSceneDesc {
 enum { RT_INTEGRATOR_WHITTED = 0, RT_INTEGRATOR_DIRECT = 1, RT_INTEGRATOR_PATH = 2, RT_INTEGRATOR_BIDIRECTIONAL = 3 };
 /* RT_INTEGRATOR_BIDIRECTIONAL: BidirIntegrator (integrators/bidirectional.cpp:80-131), eye and light sub-paths of at most 4 vertices each.  Its factory
  * reads no parameter (:211-213): max_depth and strategy are ignored.  rt_render refuses it in a participating medium and in a scene without lights. */
+/* Values from 0x100 on are integrators that estimate no radiance (value 4 stays an unknown integrator).
+ * RT_INTEGRATOR_DEBUG: DebugIntegrator (integrators/debug.cpp:61-133): the film's three channels are hit data of the camera ray, one RT_DEBUG_* code
+ * per channel, carried in `strategy` as red | green << 8 | blue << 16; max_depth is ignored.  A code above RT_DEBUG_HIT is refused (RT_EINVAL).  alpha is 1
+ * for every sample, misses included (:69).  It takes no integrator samples, renders a scene without lights, and in a medium Scene::Li's T * Lo + Lv
+ * applies to it as to the others (scene.cpp:120-126). */
+enum { RT_INTEGRATOR_DEBUG = 0x100 };
+/* ... in the order of the reference's DebugVariable (debug.cpp:33-44): dg.u, dg.v, |x|, |y|, |z| of the geometric normal isect.dg.nn and of the shading
+ * normal bsdf->dgShading.nn, the constants, and 1 where the camera ray hit something.  A miss leaves every hit-dependent channel 0. */
+enum { RT_DEBUG_U = 0, RT_DEBUG_V = 1, RT_DEBUG_NX = 2, RT_DEBUG_NY = 3, RT_DEBUG_NZ = 4, RT_DEBUG_SNX = 5, RT_DEBUG_SNY = 6, RT_DEBUG_SNZ = 7,
+       RT_DEBUG_ONE = 8, RT_DEBUG_ZERO = 9, RT_DEBUG_HIT = 10 };
 enum { RT_STRATEGY_ALL = 0, RT_STRATEGY_ONE = 1, RT_STRATEGY_WEIGHTED = 2 };
 /* RT_STRATEGY_WEIGHTED: WeightedSampleOneLight (transport.cpp:71-122), a recurrence over every shading point of the frame in program order.
  * rt_render accepts it on one shard (shard_count == 1) with at most 2048 lights of any mix (round 5: emitters of several triangles, which draw one
@@ -203,7 +213,7 @@ enum { RT_VOLUME_NONE = 0, RT_VOLUME_EMISSION = 1, RT_VOLUME_SINGLE = 2 };
 enum { RT_SAMPLER_STRATIFIED = 0, RT_SAMPLER_LOWDISCREPANCY = 1, RT_SAMPLER_RANDOM = 2 };
 
 typedef struct RtRenderDesc {
-    /* SurfaceIntegrator: integrators/{whitted,directlighting,path,bidirectional}.cpp factories */
+    /* SurfaceIntegrator: integrators/{whitted,directlighting,path,bidirectional,debug}.cpp factories (debug: strategy = the three channel codes) */
     int32_t integrator, max_depth, strategy;
     /* VolumeIntegrator: integrators/{emission,single}.cpp */
     int32_t volume_integrator;

@@ -33,7 +33,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 
 
-HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
+HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
              "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
@@ -194,11 +194,25 @@ RT_DENSITY_NAMES = {1: "exponential", 2: "volumegrid"}
 
 RT_LIGHT_NAMES = ("point", "area", "spot", "distant", "infinite")
 
+# SurfaceIntegrator "debug" (include/pbrt_hip.h): the integrator's value and its channel codes, in the order of the reference's DebugVariable
+RT_INTEGRATOR_DEBUG = 0x100
+RT_DEBUG_NAMES = ("u", "v", "nx", "ny", "nz", "snx", "sny", "snz", "one", "zero", "hit")
+(RT_DEBUG_U, RT_DEBUG_V, RT_DEBUG_NX, RT_DEBUG_NY, RT_DEBUG_NZ, RT_DEBUG_SNX, RT_DEBUG_SNY, RT_DEBUG_SNZ,
+ RT_DEBUG_ONE, RT_DEBUG_ZERO, RT_DEBUG_HIT) = range(11)
+
 
 class RtLight(C.Structure):                        # include/pbrt_hip.h (108 bytes)
     _fields_ = [("type", C.c_int32), ("color", C.c_float * 3), ("pos", C.c_float * 3), ("n_samples", C.c_int32), ("first_tri", C.c_uint32),
                 ("n_tris", C.c_uint32), ("reverse_orientation", C.c_int32), ("flip_normal", C.c_int32), ("dir", C.c_float * 3),
                 ("world_to_light", C.c_float * 9), ("cos_total_width", C.c_float), ("cos_falloff_start", C.c_float), ("quadric_plus1", C.c_int32)]
+
+class RtRenderDesc(C.Structure):                   # include/pbrt_hip.h (1128 bytes): the frame a ParsedScene hands to rt_render, ParsedScene.render_struct()
+    _fields_ = [(n, C.c_int32) for n in ("integrator", "max_depth", "strategy", "volume_integrator")] + [("step_size", C.c_float)] + \
+               [(n, C.c_int32) for n in ("sampler", "x_samples", "y_samples", "jitter", "pixel_samples")] + [("seed", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("x_res", "y_res", "x_pixel_start", "y_pixel_start", "x_pixel_count", "y_pixel_count", "x_start", "x_end", "y_start", "y_end")] + \
+               [("filter_x_width", C.c_float), ("filter_y_width", C.c_float), ("filter_table", C.c_float * 256)] + \
+               [(n, C.c_int32) for n in ("shard_index", "shard_count", "tile_pixels")]
+
 
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
@@ -542,6 +556,19 @@ class ParsedScene:
     def n_camera_samples(self) -> int:
         x0, x1, y0, y1 = self.sample_extent
         return (x1 - x0) * (y1 - y0) * self.spp
+
+    def render_struct(self) -> RtRenderDesc:
+        """This frame's RtRenderDesc in place (not a copy): a field written here is what the next rt_render is given."""
+        return C.cast(self.render_desc, C.POINTER(RtRenderDesc)).contents
+
+    @property
+    def debug_channels(self):
+        """("red", "green", "blue") names of a SurfaceIntegrator "debug" frame (RtRenderDesc.strategy = red | green << 8 | blue << 16, read from
+        the descriptor as it stands), None for every other integrator."""
+        v = self.render_view()
+        if v["integrator"] != RT_INTEGRATOR_DEBUG:
+            return None
+        return tuple(RT_DEBUG_NAMES[c] if c < len(RT_DEBUG_NAMES) else "?" for c in ((v["strategy"] >> (8 * i)) & 0xff for i in range(3)))
 
     def set_shard(self, index: int, count: int, tile_pixels=64, fit: bool = False):
         """tile_pixels: an int = tiles of that many consecutive pixels of the sample extent (scanline order); a pair (w, h) = 2-D tiles of

@@ -1,4 +1,4 @@
-// rt_flavour.h -- which kernel instantiation a frame runs.  A frame asks with a Request; each of the seven kernel families has index(request), the
+// rt_flavour.h -- which kernel instantiation a frame runs.  A frame asks with a Request; each of the eight kernel families has index(request), the
 // entry of its table that serves the request, flavour(k), the template arguments of entry k, and N, the table's size.  The translation units build
 // their tables from flavour(k) (RT_FLAVOUR_TABLE below), rt_host.h sizes the resident grids by N and rt_kernels.hip picks entries with index():
 // a table's order, its size and the host's choice cannot disagree.  No HIP header: tests/flavour_host_test.cpp checks the rules with a host compiler.
@@ -67,6 +67,15 @@ struct Bidir {
     static constexpr int index(const Request &r) { return (r.grid ? 2 : 0) + (r.count ? 1 : 0); }
     static constexpr Flavour flavour(int k) { return Flavour{(k & 1) != 0, k >> 1, false, true, RT_MIN_WAVES, false}; }
 };
+// rt::render_kernel for the debug integrator (RT_INTEGRATOR_DEBUG, rt_mega_g.hip): the timed kernel and its counting twin per (VOL, ACCEL), all with the
+// hit-frame code of the EXT set (quadric u / v, per-vertex N / S, mesh uvs); no second flavour -- a debug frame always runs these.  All allocate what the
+// compiler asks for.  Without a medium that is 95 - 107 VGPRs, below the 4-wave step (128), so those four are launched with that bound: it caps nothing and
+// leaves out the pooled-leaf LDS (rt_render_kernel.h POOL), which held the kd-tree kernels to 3 waves per SIMD (1 M-triangle frame 2.31 -> 1.92 ms)
+struct Debug {
+    static constexpr int N = 8;
+    static constexpr int index(const Request &r) { return ((r.vol ? 2 : 0) + (r.grid ? 1 : 0)) * 2 + (r.count ? 1 : 0); }
+    static constexpr Flavour flavour(int k) { return Flavour{(k & 1) != 0, (k >> 1) & 1, (k & 4) != 0, true, (k & 4) != 0 ? RT_MIN_WAVES : RT_HIGH_OCC_WAVES, false}; }
+};
 // rt::pipe_shade_kernel per integrator (rt_pipe_{w,d,p}.hip): the triple per VOL
 struct Shade {
     static constexpr int N = 6;
@@ -99,6 +108,7 @@ template <class Family, class... Integ> constexpr bool round_trips(Integ... inte
 }
 static_assert(round_trips<Mega>(RT_INTEGRATOR_WHITTED) && round_trips<Mega>(RT_INTEGRATOR_DIRECT) && round_trips<Mega>(RT_INTEGRATOR_PATH), "Mega: index(flavour(k)) != k");
 static_assert(round_trips<Weighted>() && round_trips<Bidir>(), "Weighted / Bidir: index(flavour(k)) != k");
+static_assert(round_trips<Debug>(), "Debug: index(flavour(k)) != k");
 static_assert(round_trips<Shade>() && round_trips<Vertex>() && round_trips<March>() && round_trips<Trace>(), "pipeline: index(flavour(k)) != k");
 
 // A family's table: one value per entry, in the order of flavour(k) -- the kernels of a translation unit, the resident grids of a scene (rt_host.h)

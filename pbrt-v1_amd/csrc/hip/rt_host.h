@@ -40,12 +40,13 @@ using namespace rt;
     } while (0)
 #define HIPWARN(expr) rt::hip_warn((expr), #expr)
 
-// The kernel tables of the seven families, one per translation unit that instantiates kernels; rt_flavour.h has their sizes, the order of their
+// The kernel tables of the eight families, one per translation unit that instantiates kernels; rt_flavour.h has their sizes, the order of their
 // entries and index(), the entry a frame takes.  The megakernel and the pipeline's shade kernel have a table per integrator (Whitted, DirectLighting, Path).
 namespace rt {
 extern const flavour::Table<RenderKernelFn, flavour::Mega> g_render_kernels_whitted, g_render_kernels_direct, g_render_kernels_path;
 extern const flavour::Table<RenderKernelFn, flavour::Weighted> g_render_kernels_weighted;
 extern const flavour::Table<RenderKernelFn, flavour::Bidir> g_render_kernels_bidir;
+extern const flavour::Table<RenderKernelFn, flavour::Debug> g_render_kernels_debug;
 extern const flavour::Table<PipeShadeFn, flavour::Shade> g_pipe_shade_whitted, g_pipe_shade_direct, g_pipe_shade_path;
 extern const flavour::Table<PipeShadeFn, flavour::Vertex> g_pipe_vertex;
 extern const flavour::Table<PipeTraceFn, flavour::Trace> g_pipe_trace;
@@ -59,6 +60,7 @@ struct ResidentGrids {
     flavour::Table<unsigned, flavour::Mega> mega[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Weighted> weighted;
     flavour::Table<unsigned, flavour::Bidir> bidir;
+    flavour::Table<unsigned, flavour::Debug> debug;
     flavour::Table<unsigned, flavour::Trace> trace;
     flavour::Table<unsigned, flavour::March> march;
 };
@@ -125,7 +127,7 @@ struct RtScene {
     // textured materials (rt_scene_set_textures): the scene's own resolved records (host copy) and the device array that holds them followed by
     // the records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
     std::vector<DevMaterial> materials_host;
-    std::vector<int> tex_uv_idx_host; std::vector<float> tex_uv_host;   // uvs of the triangles whose mesh has "uv" ([n_tris] index or -1, 6 floats each): host only until rt_scene_set_textures
+    std::vector<int> tex_uv_idx_host; std::vector<float> tex_uv_host;   // uvs of the triangles whose mesh has "uv" ([n_tris] index or -1, 6 floats each): host only until upload_tex_uv
     bool has_textures = false;
     DevBuf<DevMaterial> mat_buf;
     int spill_depth = 0;
@@ -160,6 +162,8 @@ static inline int upload(RtScene *s, const T *host, size_t n, const T **dev) {
     return RT_OK;
 }
 
+// the uvs of the meshes that have them, to the device (hit_point_uv reads them): once, for a scene that gets textures or renders a debug frame; rt_scene.hip
+int upload_tex_uv(RtScene *s);
 // scenes with textures: room for `levels` resolved materials per thread / slot behind the scene's own (fr.mat_pool_base); rt_scene.hip
 int ensure_material_pool(RtScene *s, rt::DevFrame &fr, size_t levels, size_t n_slots);
 

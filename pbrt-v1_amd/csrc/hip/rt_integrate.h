@@ -679,6 +679,47 @@ RT_DEV bool march_steps(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
     return false;
 }
 
+// ---- DebugIntegrator::Li (integrators/debug.cpp:61-133): the camera ray's hit data as the sample's three channels, one RT_DEBUG_* code each in
+// DevFrame::strategy (red | green << 8 | blue << 16).  isect.dg.u / dg.v are hit_point_uv's (rt_texture.h), isect.dg.nn is make_vertex's geometric normal
+// and bsdf->dgShading.nn the normal of its BSDF frame (after GetShadingGeometry and Material::Bump's constant-0 displacement).  alpha is 1 whether the ray
+// hit or not (:69); a miss leaves u, v and the normals 0 (:76, :93).  The codes are the frame's, so which of the two hit records is read is wave-uniform.
+RT_DEV float debug_value(int code, bool hit, float u, float v, V3 ng, V3 ns) {
+    switch (code) {
+        case RT_DEBUG_U: return u;
+        case RT_DEBUG_V: return v;
+        case RT_DEBUG_NX: return fabsf(ng.x);
+        case RT_DEBUG_NY: return fabsf(ng.y);
+        case RT_DEBUG_NZ: return fabsf(ng.z);
+        case RT_DEBUG_SNX: return fabsf(ns.x);
+        case RT_DEBUG_SNY: return fabsf(ns.y);
+        case RT_DEBUG_SNZ: return fabsf(ns.z);
+        case RT_DEBUG_ONE: return 1.f;
+        case RT_DEBUG_HIT: return hit ? 1.f : 0.f;
+        default: return 0.f;                                                    // RT_DEBUG_ZERO (rt_render refuses every other code)
+    }
+}
+template <bool COUNT, bool VOL>
+RT_DEV void debug_vertex(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid, unsigned *c_closest) {
+    if (COUNT) ++*c_closest;
+    const bool hit = ln.tv.hit_prim >= 0;
+    const int cr = fr.strategy & 0xff, cg = (fr.strategy >> 8) & 0xff, cb = (fr.strategy >> 16) & 0xff;
+    const bool want_uv = cr <= RT_DEBUG_V || cg <= RT_DEBUG_V || cb <= RT_DEBUG_V;
+    const bool want_n = (cr >= RT_DEBUG_NX && cr <= RT_DEBUG_SNZ) || (cg >= RT_DEBUG_NX && cg <= RT_DEBUG_SNZ) || (cb >= RT_DEBUG_NX && cb <= RT_DEBUG_SNZ);
+    float u = 0.f, v = 0.f; V3 ng = mk3(0.f), ns = mk3(0.f);
+    if (hit) {
+        if (want_uv) {
+            RtTexHit h;
+            hit_point_uv(sc, ln.tv, __float_as_uint(RT_GPTR(const float4, sc.tri_shade)[size_t(2) * unsigned(ln.tv.hit_prim)].w), h);
+            u = h.u; v = h.v;
+        }
+        if (want_n) { make_vertex<true>(sc, ln.tv, ln.v); ng = ln.v.ng; ns = ln.v.nn; }
+        if (VOL) vol_ray_ptr(fr, 0, gtid)[7 * size_t(fr.n_threads)] = ln.tv.maxt;   // Intersect shortened the ray Scene::Li hands to the volume integrator
+    }
+    ln.L = mk3(debug_value(cr, hit, u, v, ng, ns), debug_value(cg, hit, u, v, ng, ns), debug_value(cb, hit, u, v, ng, ns));
+    ln.alpha = 1.f;
+    ln.stage = ST_RETURN;
+}
+
 // The body of ONE stage.  Returns when the lane has a ray in flight or has changed stage.
 template <bool COUNT, int INTEG_, bool VOL, bool EXT, int STAGE, bool DEFER = false, bool PARK = false>
 RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid,
@@ -686,7 +727,10 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
     // RT_INTEG_DIRECT_WEIGHTED: DirectLighting with strategy "weighted", a kernel family of its own so that the all / one kernels keep their code
     constexpr bool WEIGHTED = INTEG_ == RT_INTEG_DIRECT_WEIGHTED;
     constexpr int INTEG = WEIGHTED ? int(RT_INTEGRATOR_DIRECT) : INTEG_;
-    if constexpr (STAGE == ST_VERTEX) {
+    if constexpr (STAGE == ST_VERTEX && INTEG_ == RT_INTEGRATOR_DEBUG) {          // (a kernel family of its own, rt_mega_g.hip: no other kernel carries this)
+        debug_vertex<COUNT, VOL>(sc, fr, ln, gtid, c_closest);
+        return;
+    } else if constexpr (STAGE == ST_VERTEX) {
         if (COUNT) ++*c_closest;
         const bool hit = ln.tv.hit_prim >= 0;
         if (INTEG == RT_INTEGRATOR_PATH) {
@@ -1137,6 +1181,13 @@ RT_DEV void advance_pass(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
 #else
 #define RT_RUN(S) if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
 #endif
+    if constexpr (INTEG_ == RT_INTEGRATOR_DEBUG) {            // one camera ray per sample: its hit data, then Scene::Li's medium and the sample record
+        RT_RUN(ST_VERTEX);
+        RT_RUN(ST_RETURN);
+        if (VOL) { RT_RUN(ST_VOL_STEP); RT_RUN(ST_VOL_BEGIN); }
+        RT_RUN(ST_POP);
+        RT_RUN(ST_FINISH);
+    } else {
     if (phase != 0) {
         RT_RUN(ST_MIS_DONE);
         RT_RUN(ST_SHADOW_DONE);
@@ -1153,6 +1204,7 @@ RT_DEV void advance_pass(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
         if (VOL) { if (!PARK) RT_RUN(ST_VOL_STEP); RT_RUN(ST_VOL_BEGIN); }
         RT_RUN(ST_POP);
         RT_RUN(ST_FINISH);
+    }
     }
 #undef RT_RUN
 }

@@ -63,7 +63,8 @@ void stream_free(void *st) { HIPWARN(hipStreamDestroy(static_cast<hipStream_t>(s
 // resolved per hit (rt_texture.h).  fr.vol_nmax is what rt_render's validation found.
 struct ScratchWords { size_t frame = 0, vol_levels = 0, vol = 0, mat_levels = 0; };
 static ScratchWords scratch_words(const RtScene *s, const RtRenderDesc *rd, const DevFrame &fr) {
-    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL, path = rd->integrator == RT_INTEGRATOR_PATH;
+    // (the debug integrator recurses no more than the path integrator does: no frames, one level of the medium's rays)
+    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL, path = rd->integrator == RT_INTEGRATOR_PATH || rd->integrator == RT_INTEGRATOR_DEBUG;
     ScratchWords w;
     w.frame = bidir ? size_t(RT_BD_FRAME_WORDS) : path ? 0 : size_t(rd->max_depth + 2) * RT_FRAME_WORDS;
     w.mat_levels = bidir ? size_t(2 * RT_BD_MAX_VERTS) : path ? 1 : size_t(rd->max_depth + 2);
@@ -211,11 +212,13 @@ static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     return RT_OK;
 }
 
-// The megakernel of Whitted, DirectLighting "all" / "one" and Path: one launch of rt::render_kernel
+// The megakernel of Whitted, DirectLighting "all" / "one", Path and the debug integrator (a table of its own, flavour::Debug): one launch of rt::render_kernel
 static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-    const int k = flavour::Mega::index(request_of(s, rd, &fr));
-    const unsigned grid = s->grids.mega[rd->integrator][k];
+    const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
+    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
+    const unsigned grid = debug ? s->grids.debug[k] : s->grids.mega[rd->integrator][k];
+    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : (*g_render_kernels[rd->integrator])[k];
     if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
 #ifdef RT_TAIL_PROBE
     static unsigned long long *probe = nullptr;
@@ -227,7 +230,7 @@ static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
     HIPCHK(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL((*g_render_kernels[rd->integrator])[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev1, s->stream));
 #ifdef RT_TAIL_PROBE
@@ -413,7 +416,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
     } else if (rd->integrator == RT_INTEGRATOR_DIRECT) { n2 = {1, 1}; n1 = {1, 1}; }
     else if (rd->integrator == RT_INTEGRATOR_PATH) { n1.assign(9, 1); n2.assign(9, 1); }
     else if (rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL) { n1.assign(4 * RT_BD_MAX_VERTS + 1, 1); n2.assign(4 * RT_BD_MAX_VERTS + 2, 1); }     // bidirectional.cpp:65-79
-    else if (rd->integrator != RT_INTEGRATOR_WHITTED) return fail(RT_EINVAL, "unknown integrator");
+    else if (rd->integrator != RT_INTEGRATOR_WHITTED && rd->integrator != RT_INTEGRATOR_DEBUG) return fail(RT_EINVAL, "unknown integrator");     // (neither requests samples)
     n1.push_back(1); n1.push_back(1);                   // the volume integrator's tau / scatter samples
     // The requests in the reference's order (every 1-D request, then every 2-D one: Sample::Sample sampling.cpp:41-70).  DirectLighting "all" asks for
     // 2 x 2-D and 1 x 1-D per light WITHOUT bound (directlighting.cpp:39-66): its per-light requests go to a table in HBM (DevFrame::light_dims, three
@@ -534,6 +537,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
         if (s->dev.n_lights >= 65535u) fr.pipeline = 0;
         if (rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED) fr.pipeline = 0;    // three megakernel passes (rt_weighted.h)
         if (bidir) { fr.pipeline = 0; fr.xcd_bands = 0; }   // rt::bidir_kernel (rt_bidir.h): a persistent kernel of its own, one work counter
+        if (rd->integrator == RT_INTEGRATOR_DEBUG) { fr.pipeline = 0; fr.high_occupancy = 0; }     // flavour::Debug: the megakernel, one kernel per (medium, accelerator, counting), whatever the knobs say
         if (fr.shard_count == 1 && !fr.pipeline) {
             // One shard: the tiles partition nothing, and the megakernel then renders the sample extent in scanline order.  2-D tiles pad the extent to
             // whole tiles and every dropped padding item idles a lane for about a ray's time: 64 x 64 tiles cost C3 5 % of its frame
@@ -614,9 +618,15 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (!s || !rd) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
     // ---- validation first: a failing call launches nothing and leaves the film and the sample buffer untouched
-    if (rd->integrator < RT_INTEGRATOR_WHITTED || rd->integrator > RT_INTEGRATOR_BIDIRECTIONAL) return fail(RT_EINVAL, "unknown integrator");
+    const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
+    if ((rd->integrator < RT_INTEGRATOR_WHITTED || rd->integrator > RT_INTEGRATOR_BIDIRECTIONAL) && !debug) return fail(RT_EINVAL, "unknown integrator");
     const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL;
-    if (rd->max_depth < 0 && !bidir) return fail(RT_EINVAL, "rt_render: negative maxdepth");
+    if (rd->max_depth < 0 && !bidir && !debug) return fail(RT_EINVAL, "rt_render: negative maxdepth");
+    if (debug) {                                              // DebugIntegrator (debug.cpp): strategy = red | green << 8 | blue << 16 (include/pbrt_hip.h)
+        const unsigned codes = unsigned(rd->strategy);
+        if ((codes >> 24) != 0u || (codes & 0xffu) > unsigned(RT_DEBUG_HIT) || ((codes >> 8) & 0xffu) > unsigned(RT_DEBUG_HIT) || ((codes >> 16) & 0xffu) > unsigned(RT_DEBUG_HIT))
+            return fail(RT_EINVAL, "rt_render: unknown debug channel code (the debug integrator's strategy holds three RT_DEBUG_* codes, red | green << 8 | blue << 16)");
+    }
     if (bidir) {                                              // BidirIntegrator (bidirectional.cpp): rt_bidir.h
         // the reference's connections ignore the medium's transmittance while EstimateDirect applies it: left for a later change
         if (s->volume.present) return fail(RT_EINVAL, "rt_render: the bidirectional integrator in a participating medium is not supported");
@@ -698,6 +708,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     }
     fr.samples = s->samples; s->samples_last = fr.total_work; s->samples_spp = fr.spp;
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (debug) { rc = upload_tex_uv(s); if (rc) return rc; }    // dg.u / dg.v of a mesh with "uv": on the device from the first debug frame on
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
     s->rendered = true;
     // ---- the frame, by one of the four launch functions

@@ -541,6 +541,13 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) if ((rc = resident(*g_render_kernels[i], g.mega[i]))) return rc;
     if ((rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir))) return rc;
     s->grid = mx;                                               // ... of the megakernels
+    {   // the debug integrator's kernels need fewer registers than any of those: their grids stop at the largest of the others, so that the scratch
+        // every frame shares (n_threads) is sized as it was
+        const unsigned others = mx;
+        if ((rc = resident(g_render_kernels_debug, g.debug))) return rc;
+        for (unsigned &n : g.debug) n = std::min(n, others);
+        mx = others;
+    }
     if ((rc = resident(g_pipe_trace, g.trace, trace_per_cu)) || (rc = resident(g_pipe_march, g.march))) return rc;
     s->n_threads = mx * RT_BLOCK;                               // ... of all: the spill area is shared
     s->spill_depth = s->tree.max_depth > RT_TRACE_STACK ? s->tree.max_depth - RT_TRACE_STACK + 1 : 1;     // RT_TRACE_STACK <= RT_STACK_LDS
@@ -698,14 +705,9 @@ int rt_scene_set_textures(RtScene *s, const RtTexture *nodes, uint32_t n_nodes, 
             }
             HIPCHK(hipMemcpy(const_cast<float4 *>(s->dev.tri_shade), shade.data(), shade.size() * sizeof(float4), hipMemcpyHostToDevice));
         }
-        const int *duvi = nullptr; const float *duv = nullptr;                  // the per-vertex uvs of the meshes that have them (6 floats per triangle)
-        if (n_textured && !s->tex_uv_idx_host.empty()) {
-            if ((rc = upload(s, s->tex_uv_idx_host.data(), s->tex_uv_idx_host.size(), &duvi))) return rc;
-            if ((rc = upload(s, s->tex_uv_host.data(), s->tex_uv_host.size(), &duv))) return rc;
-        }
-        std::vector<int>().swap(s->tex_uv_idx_host); std::vector<float>().swap(s->tex_uv_host);   // (the call is made once)
         DevScene &d = s->dev;
-        d.n_textured = int(n_textured); d.tex_nodes = dnodes; d.tex_prog = dprog; d.mat_tex = dmt; d.tex_uv_idx = duvi; d.tex_uv = duv;
+        d.n_textured = int(n_textured); d.tex_nodes = dnodes; d.tex_prog = dprog; d.mat_tex = dmt;
+        if (n_textured) { if ((rc = upload_tex_uv(s))) return rc; }             // the per-vertex uvs of the meshes that have them (copies the scene record too)
         HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
         s->has_textures = true;
         s->has_ext = true;                                                      // the evaluator exists only in the EXT kernels
@@ -713,6 +715,20 @@ int rt_scene_set_textures(RtScene *s, const RtTexture *nodes, uint32_t n_nodes, 
     });
 }
 }  // extern "C"
+// The uvs rt_scene_create kept on the host (6 floats per triangle of a mesh with "uv"), uploaded once: by rt_scene_set_textures for a scene with a textured
+// material, by rt_render before the first debug frame (dg.u / dg.v, hit_point_uv).  Nothing to do when no mesh has "uv" or they are on the device already.
+int upload_tex_uv(RtScene *s) {
+    if (s->tex_uv_idx_host.empty() || s->dev.tex_uv_idx) return RT_OK;
+    const int *duvi = nullptr; const float *duv = nullptr;
+    int rc;
+    if ((rc = upload(s, s->tex_uv_idx_host.data(), s->tex_uv_idx_host.size(), &duvi))) return rc;
+    if ((rc = upload(s, s->tex_uv_host.data(), s->tex_uv_host.size(), &duv))) return rc;
+    std::vector<int>().swap(s->tex_uv_idx_host); std::vector<float>().swap(s->tex_uv_host);
+    HIPCHK(hipStreamSynchronize(s->stream));                                    // (a frame queued earlier reads the scene record)
+    s->dev.tex_uv_idx = duvi; s->dev.tex_uv = duv;
+    HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
+    return RT_OK;
+}
 // room for the per-hit records: [the scene's materials | levels * n_slots resolved ones].  Called by rt_render before its first launch.
 int ensure_material_pool(RtScene *s, DevFrame &fr, size_t levels, size_t n_slots) {
     fr.mat_pool_base = 0;

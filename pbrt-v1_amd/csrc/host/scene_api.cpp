@@ -237,6 +237,20 @@ SurfaceIntegrator MakeSurfaceIntegrator(const std::string &name, const ParamSet 
         ps.ReportUnused();
         return si;
     }
+    if (name == "debug") {                                   // debug.cpp:135-166: three channel names, in the order of its DebugVariable (include/pbrt_hip.h RT_DEBUG_*)
+        static const char *const kNames[RT_DEBUG_HIT + 1] = {"u", "v", "nx", "ny", "nz", "snx", "sny", "snz", "one", "zero", "hit"};
+        static const char *const kChannel[3][2] = {{"red", "u"}, {"green", "v"}, {"blue", "zero"}};
+        si.kind = RT_INTEGRATOR_DEBUG; si.maxDepth = 5; si.strategy = 0;
+        for (int i = 0; i < 3; ++i) {
+            const std::string str = ps.FindOneString(kChannel[i][0], kChannel[i][1]);
+            int code = -1;
+            for (int k = 0; k <= RT_DEBUG_HIT; ++k) if (str == kNames[k]) code = k;
+            if (code < 0) { Error("Unknown debug type \"%s\", defaulting to zero.", str.c_str()); code = RT_DEBUG_ZERO; }
+            si.strategy |= code << (8 * i);                  // RtRenderDesc::strategy = red | green << 8 | blue << 16
+        }
+        ps.ReportUnused();
+        return si;
+    }
     si.maxDepth = ps.FindOneInt("maxdepth", 5);              // whitted.cpp:143, directlighting.cpp:196, path.cpp:147
     if (name == "whitted") si.kind = RT_INTEGRATOR_WHITTED;
     else if (name == "path") si.kind = RT_INTEGRATOR_PATH;

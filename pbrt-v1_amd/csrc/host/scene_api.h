@@ -7,7 +7,7 @@
 //   * the Make* plugin factories of core/dynload.cpp:112-260 for the plugins on the hot path
 //     (SURVEY.md section 8a): filters box/gaussian/mitchell/sinc/triangle, film "image", camera
 //     "perspective", samplers stratified/lowdiscrepancy/random, surface integrators
-//     whitted/directlighting/path, volume integrators emission/single, accelerators kdtree/grid, shape
+//     whitted/directlighting/path/bidirectional/debug, volume integrators emission/single, accelerators kdtree/grid, shape
 //     "trianglemesh", materials matte/glass/mirror, lights point + area, volumes "homogeneous", "exponential", "volumegrid";
 //     each takes the same parameters with the same defaults as the reference factory it replaces.
 //   * RenderOptions::MakeScene (core/api.cpp:484-529): instead of building C++ objects it flattens.
