@@ -2,15 +2,35 @@
 stores tests/golden/analytic/<case>.npz), tests/test_analytic_host.py and tests/test_gpu_analytic.py.  Each case is a scene of one or two
 analytic surfaces under delta lights and SurfaceIntegrator "whitted", so that one camera sample is one evaluation of
 f(wo, wi) Li |cos| (times transmittances); scene_text() writes it as a scene file, form() builds the float64 side (tests/analytic_forms.py).
-Every case names the term it is there for and one wrong twin of its form that the fixture must reject."""
+Every case names the term it is there for and one wrong twin of its form that the fixture must reject (`also`: further twins, held to the same share).
+
+Two families read the hit itself: "geometry" cases run SurfaceIntegrator "debug" with one channel triple (u, v, the normals, the hit mask of
+the camera ray), "textures" cases light a surface whose material parameters come from Texture graphs, so that a sample is
+f(material resolved at the hit) I / d^2 |cos|."""
+import importlib.util
+import os
+import re
+
 import numpy as np
 
 import analytic_forms as F
 
+
+def _scenes():
+    """pbrt-v1_amd/scenes.py (numpy only) without the package around it"""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pbrt-v1_amd", "scenes.py")
+    spec = importlib.util.spec_from_file_location("analytic_scenes", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+SCENES = _scenes()
+
 RES = 64
 COLORS = {"Kd", "Ks", "Kr", "Kt", "reflect", "transmit", "opacity", "I", "L", "sigma_a", "sigma_s", "Le"}
 POINTS = {"from", "to", "p0", "p1", "p2"}
-FAMILIES = ("lights", "lobes", "quadrics", "specular", "medium")
+FAMILIES = ("lights", "lobes", "quadrics", "specular", "medium", "geometry", "textures")
 
 PLANE_CAM = dict(lookat=(0, 2, -6, 0, .6, 0, 0, 1, 0))
 QUADRIC_CAM = dict(lookat=(0, 0, -4, 0, 0, 0, 0, 1, 0))
@@ -109,6 +129,143 @@ CASES = {
 }
 
 
+# ------------------------------------------------------------------------------------------------ geometry: SurfaceIntegrator "debug"
+def tex(name):
+    """a material or texture parameter that names a texture"""
+    return ("tex", name)
+
+
+def mesh_arrays(text):
+    """the arrays of a `Shape "trianglemesh"` statement (scenes.smooth_mesh_text): what the form is built from IS what the scene file says"""
+    get = lambda key, typ: (np.array(re.search(r'"%s" \[([^\]]*)\]' % key, text).group(1).split(), typ) if ('"%s"' % key) in text else None)
+    return dict(indices=get("integer indices", np.int64), P=get("point P", np.float64), uv=get("float uv", np.float64), N=get("normal N", np.float64),
+                S=get("vector S", np.float64))
+
+
+def smooth_mesh(**kw):
+    return ("mesh", mesh_arrays(SCENES.smooth_mesh_text(**kw)))
+
+
+def quad_mesh(corners, uv=None):
+    return ("mesh", dict(indices=np.array([0, 1, 2, 0, 2, 3]), P=np.array(corners, np.float64), uv=None if uv is None else np.array(uv, np.float64), N=None, S=None))
+
+
+GREY = ("matte", dict(Kd=(.5, .5, .5)))
+SQUASHED = dict(radius=1.45, nu=10, nv=6, squash=(1.0, .75, 1.0))
+MESH_CTM = [("Rotate", -55, 1, 0, 0), ("Rotate", 25, 0, 0, 1), ("Scale", 1.3, .8, 1)]
+
+
+def geometry_case(term, twin, channels, surfaces, **kw):
+    """the lights are ignored by the integrator; without one the reference warns"""
+    return dict(family="geometry", term=term, twin=twin, camera=QUADRIC_CAM, lights=Q_LIGHTS, debug=channels, surfaces=surfaces, **kw)
+
+
+def quadric_geometry(term, twin, channels, like, **kw):
+    """the shape and CTM of an existing quadric case"""
+    src = CASES[like]["surfaces"][0]
+    return geometry_case(term, twin, channels, [dict(shape=src["shape"], ctm=src["ctm"], material=GREY)], **kw)
+
+
+UV = ("u", "v", "hit")
+CASES.update({
+    # a quad without uvs (prims 0, 1: GetUVs' defaults on each triangle, the inner diagonal a discontinuity) before one whose uvs reach 2 and 3
+    # (prims 2, 3: rows 0, 1 of the uv table), both tilted
+    "geom_mesh_uv": geometry_case("mesh (u, v): explicit uvs beyond 1 next to the per-triangle defaults", "u_v_swapped", UV,
+                                  [dict(shape=quad_mesh((.15, -1.1, .3, 1.75, -.9, 0, 1.6, 1.0, .2, .1, .8, .5)), ctm=[("Rotate", 7, 0, 0, 1)], material=GREY),
+                                   dict(shape=quad_mesh((-1.8, -1.0, 0, -.2, -1.2, .4, -.1, .9, .3, -1.7, 1.1, -.1), uv=(0, 0, 2, 0, 2, 3, 0, 3)), ctm=[("Rotate", -9, 0, 0, 1)],
+                                        material=GREY)], also=("default_uvs_always",)),
+    "geom_mesh_n_geometric": geometry_case("mesh with N: the geometric normal stays the triangle's, from world-space vertices", "shading_for_geometric_normal", ("nx", "ny", "nz"),
+                                           [dict(shape=smooth_mesh(**SQUASHED), ctm=MESH_CTM, material=GREY)]),
+    "geom_mesh_n_shading": geometry_case("mesh with N under a non-uniform scale: interpolated, inverse transpose, renormalised", "normal_transformed_as_vector", ("snx", "sny", "snz"),
+                                         [dict(shape=smooth_mesh(**SQUASHED), ctm=MESH_CTM, material=GREY)], also=("geometric_for_shading_normal",)),
+    "geom_mesh_ns_reversed": geometry_case("mesh with N and S, ReverseOrientation, Scale -1 1 1: the flips change no |component|", "normal_not_renormalised", ("snx", "sny", "snz"),
+                                           [dict(shape=smooth_mesh(with_s=True, **SQUASHED), ctm=[("Rotate", -50, 1, 0, 0), ("Rotate", 40, 0, 0, 1), ("Scale", -1, 1, 1)], reverse=True,
+                                                 material=GREY)], also=("geometric_for_shading_normal",)),
+    "geom_uv_sphere": quadric_geometry("sphere: u = phi / phimax, v by theta between the thetas of zmin and zmax", "sphere_v_linear_in_z", UV, "quadric_sphere", also=("phimax_ignored_in_u",)),
+    "geom_uv_disk": quadric_geometry("disk: v = 1 - (r - innerradius) / (radius - innerradius)", "inner_radius_ignored", UV, "quadric_disk_inner", also=("phimax_ignored_in_u",)),
+    "geom_uv_cylinder": quadric_geometry("cylinder: v = (z - zmin) / (zmax - zmin)", "phimax_ignored_in_u", UV, "quadric_cylinder"),
+    "geom_uv_cone": quadric_geometry("cone: v = z / height", "cone_v_by_zmax_of_another_kind", UV, "quadric_cone", also=("phimax_ignored_in_u",)),
+    "geom_uv_paraboloid": quadric_geometry("paraboloid: v = (z - zmin) / (zmax - zmin)", "phimax_ignored_in_u", UV, "quadric_paraboloid"),
+    "geom_uv_hyperboloid": quadric_geometry("hyperboloid: v along p1 p2, phi against the ruling", "phimax_ignored_in_u", UV, "quadric_hyperboloid"),
+    "geom_n_cylinder": quadric_geometry("cylinder normal under a non-uniform scale", "normal_not_renormalised", ("nx", "ny", "nz"), "quadric_cylinder"),
+    "geom_n_paraboloid": quadric_geometry("paraboloid normal under a non-uniform scale", "normal_not_renormalised", ("nx", "ny", "nz"), "quadric_paraboloid"),
+    "geom_uv_cylinder_grid": quadric_geometry("(u, v) through the grid accelerator", "phimax_ignored_in_u", UV, "quadric_cylinder_grid", accel="grid"),
+})
+
+
+# ------------------------------------------------------------------------------------------------ textures: Whitted, one point light
+# a finite parallelogram with explicit uvs (so (u, v) is affine across the inner diagonal), tilted so that no edge runs along a row of samples
+PANEL = quad_mesh((-1.7, -1.4, 0, 1.7, -1.4, 0, 1.7, 1.4, 0, -1.7, 1.4, 0), uv=(0, 0, 1, 0, 1, 1, 0, 1))
+PANEL_CTM = [("Rotate", -25, 1, 0, 0), ("Rotate", 20, 0, 0, 1)]
+T_LIGHT = dict(kind="point", I=(30, 25, 20), **{"from": (1, 2, -3.5)})
+NONE = dict(aamode="none")
+TEX_CTM = [("Translate", .3, -.2, -1.2), ("Rotate", -60, 0, 1, .3), ("Scale", 1, 1.3, .8)]
+
+
+def texture_case(term, twin, textures, material, shape=PANEL, ctm=PANEL_CTM, light=T_LIGHT, **kw):
+    return dict(family="textures", term=term, twin=twin, camera=QUADRIC_CAM, lights=[light], surfaces=[dict(shape=shape, ctm=ctm, textures=textures, material=material)], **kw)
+
+
+def T(name, typ, cls, **params):
+    return dict(name=name, type=typ, cls=cls, params=params)
+
+
+CHK = lambda name, **kw: T(name, "color", "checkerboard", tex1=(.8, .2, .2), tex2=(.2, .3, .8), **NONE, **kw)
+CASES.update({
+    "tex_checker_negative": texture_case("checkerboard on Kd, uv mapping, negative s and t in frame: Floor2Int", "cells_truncated_toward_zero",
+                                         [CHK("chk", uscale=5, vscale=4, udelta=-2.3, vdelta=-1.7)], ("matte", dict(Kd=tex("chk")))),
+    "tex_bilerp_clamp": texture_case("bilerp on Kd, one corner negative in a channel: Kd clamped at 0", "corners_transposed",
+                                     [T("bl", "color", "bilerp", v00=(.9, .2, .1), v01=(.1, .7, .2), v10=(-1.4, .2, .9), v11=(.8, .8, .1))], ("matte", dict(Kd=tex("bl"))), also=("kd_unclamped",)),
+    "tex_uv": texture_case("uv texture on Kd: (s - floor s, t - floor t, 0)", "fraction_not_taken",
+                           [T("uvt", "color", "uv", uscale=3, vscale=2, udelta=.2, vdelta=.35)], ("matte", dict(Kd=tex("uvt")))),
+    # (a colour `scale` takes two colour textures, textures/scale.cpp:53-58: the scalar factor is a bilerp of greys, a float travelling as (f, f, f))
+    "tex_scale": texture_case("scale: a colour checkerboard times a grey bilerp", "scale_adds",
+                              [CHK("chk", uscale=4, vscale=3, udelta=.15, vdelta=.3), T("fb", "color", "bilerp", v00=(.2, .2, .2), v01=(.9, .9, .9), v10=(.7, .7, .7), v11=(.35, .35, .35)),
+                               T("sc", "color", "scale", tex1=tex("chk"), tex2=tex("fb"))], ("matte", dict(Kd=tex("sc")))),
+    "tex_mix_depth4": texture_case("mix(checkerboard(bilerp, uv), scale(constant, bilerp), amount = float checkerboard): four values alive", "amount_complemented",
+                                   [T("bl", "color", "bilerp", v00=(.9, .2, .1), v01=(.1, .7, .2), v10=(.2, .2, .9), v11=(.8, .8, .1)),
+                                    T("uvt", "color", "uv", uscale=3, vscale=2),
+                                    T("chk", "color", "checkerboard", tex1=tex("bl"), tex2=tex("uvt"), uscale=4, vscale=3, udelta=.15, vdelta=.3, **NONE),
+                                    T("bl2", "color", "bilerp", v00=(.3, .9, .8), v01=(.9, .9, .2), v10=(.6, .1, .7), v11=(.2, .5, .9)),
+                                    T("sc", "color", "scale", tex1=(.9, .6, .8), tex2=tex("bl2")),
+                                    T("amt", "float", "checkerboard", tex1=.2, tex2=.75, uscale=2, vscale=5, udelta=.4, vdelta=.1, **NONE),
+                                    T("mx", "color", "mix", tex1=tex("chk"), tex2=tex("sc"), amount=tex("amt"))], ("matte", dict(Kd=tex("mx"))),
+                                   also=("tex1_tex2_swapped",)),
+    "tex_planar": texture_case("planar mapping: non-orthogonal v1, v2 and deltas on the world-space hit point", "deltas_dropped",
+                               [CHK("chk", mapping="planar", v1=(1.5, .5, .3), v2=(-.4, 1.6, .5), udelta=.37, vdelta=.21)], ("matte", dict(Kd=tex("chk")))),
+    "tex_spherical": texture_case("spherical mapping declared under Translate / Rotate / Scale, its seam in frame", "texture_ctm_ignored",
+                                  [dict(T("sph", "color", "bilerp", mapping="spherical", v00=(.9, .1, .1), v01=(.1, .8, .1), v10=(.1, .1, .9), v11=(.9, .9, .1)), ctm=TEX_CTM)],
+                                  ("matte", dict(Kd=tex("sph")))),
+    "tex_cylindrical": texture_case("cylindrical mapping declared under Translate / Rotate / Scale, its seam in frame", "texture_ctm_ignored",
+                                    [dict(T("cyl", "color", "bilerp", mapping="cylindrical", v00=(.9, .1, .1), v01=(.1, .8, .1), v10=(.1, .1, .9), v11=(.9, .9, .1)),
+                                          ctm=[("Translate", -.2, .3, -1.0), ("Rotate", 200, 1, .3, 0), ("Scale", 1.2, 1, .7)])],
+                                    ("matte", dict(Kd=tex("cyl")))),
+    "tex_sigma": texture_case("matte sigma from a float bilerp over 0 .. 120: Oren-Nayar's A, B per hit, the clamp at 90", "sigma_unclamped",
+                              [T("sg", "float", "bilerp", v00=0, v01=100, v10=70, v11=120)], ("matte", dict(Kd=(.7, .6, .5), sigma=tex("sg")))),
+    "tex_roughness": texture_case("plastic roughness from a float checkerboard of .2 / .0005: the exponent per hit, capped at 1000", "exponent_uncapped",
+                                  [T("rg", "float", "checkerboard", tex1=.2, tex2=.0005, uscale=2, vscale=2, udelta=.5, vdelta=-.5, **NONE)],
+                                  ("plastic", dict(Kd=(.05, .04, .03), Ks=(.02, .015, .01), roughness=tex("rg"))),
+                                  light=dict(kind="point", I=(3400, 3000, 2400), **{"from": (0, -46, -38.6)})),
+    "tex_opacity": texture_case("uber opacity from a colour checkerboard: the lobes scaled per hit", "opacity_ignored",
+                                [T("op", "color", "checkerboard", tex1=(1, 1, 1), tex2=(.3, .3, .3), uscale=5, vscale=4, udelta=.13, vdelta=.29, **NONE)],
+                                ("uber", dict(Kd=(.5, .4, .3), Ks=(.4, .4, .3), opacity=tex("op"), roughness=.15))),
+    "tex_sphere_uv": texture_case("a partial sphere textured through its own (u, v)", "phimax_ignored_in_u",
+                                  [CHK("chk", uscale=6, vscale=4, udelta=.1, vdelta=.2)], ("matte", dict(Kd=tex("chk"))),
+                                  shape=("sphere", dict(radius=1.5, zmin=-1.1, zmax=.9, phimax=250)), ctm=TILT),
+    # the mirror floor's Kr and the matte wall's Kd are both textured: the records of recursion levels 0 and 1 are alive in one sample
+    "tex_mirror_floor_wall": dict(family="textures", term="a textured mirror floor reflecting a textured matte wall: the material records of two levels", twin="wall_material_at_the_floor",
+                                  camera=QUADRIC_CAM, maxdepth=1, lights=[dict(kind="point", I=(30, 25, 20), **{"from": (.3, 1.5, -1)})],
+                                  surfaces=[dict(shape=quad_mesh((-2.2, -1.2, -1.5, 2.2, -1.2, -1.5, 2.2, -1.2, 2, -2.2, -1.2, 2), uv=(0, 0, 1, 0, 1, 1, 0, 1)),
+                                                 ctm=[("Rotate", 14, 0, 1, 0), ("Rotate", 6, 0, 0, 1)],
+                                                 textures=[T("krc", "color", "checkerboard", tex1=(.9, .8, .7), tex2=(.3, .5, .9), uscale=4, vscale=3, udelta=.2, vdelta=.1, **NONE)],
+                                                 material=("mirror", dict(Kr=tex("krc")))),
+                                            dict(shape=quad_mesh((-2.2, -1.2, 2, 2.2, -1.2, 2, 2.2, 2.2, 2, -2.2, 2.2, 2), uv=(0, 0, 1, 0, 1, 1, 0, 1)),
+                                                 ctm=[("Rotate", 14, 0, 1, 0), ("Rotate", 6, 0, 0, 1)],
+                                                 textures=[T("kdc", "color", "checkerboard", tex1=(.8, .7, .2), tex2=(.2, .6, .3), uscale=5, vscale=4, udelta=.3, vdelta=.15, **NONE)],
+                                                 material=("matte", dict(Kd=tex("kdc"))))]),
+})
+
+
 # ---- the three camera probes: an orthographic camera with a screen window, an environment camera and a thin-lens perspective camera (under
 # the unjittered 1 x 1 sampler its lens sample is (.5, .5), the lens centre, so the ray is closed form), 32 x 32, each looking at one of every
 # quadric (partial, rotated, two under a non-uniform scale); the reference's probe integrator records every camera ray and its closest hit
@@ -142,6 +299,9 @@ def _params(d, skip=("kind", "ctm")):
     for k, v in d.items():
         if k in skip:
             continue
+        if isinstance(v, tuple) and len(v) == 2 and v[0] == "tex":
+            out.append('"texture %s" "%s"' % (k, v[1]))
+            continue
         typ = "color" if k in COLORS else "point" if k in POINTS else "float"
         out.append('"%s %s" [%s]' % (typ, k, _fmt(v)))
     return " ".join(out)
@@ -149,6 +309,35 @@ def _params(d, skip=("kind", "ctm")):
 
 def _ctm_text(ctm):
     return "".join("%s %s\n" % (op[0], _fmt(op[1:])) for op in ctm)
+
+
+VECTORS = {"v1", "v2"}
+STRINGS = {"mapping", "aamode"}
+
+
+def _texture_text(t):
+    """one Texture statement; a declaration with a `ctm` stands between TransformBegin and TransformEnd, so that CTM is the texture's alone"""
+    out = []
+    for k, v in t["params"].items():
+        if isinstance(v, tuple) and len(v) == 2 and v[0] == "tex":
+            out.append('"texture %s" "%s"' % (k, v[1]))
+        elif k in STRINGS:
+            out.append('"string %s" ["%s"]' % (k, v))
+        elif k in VECTORS:
+            out.append('"vector %s" [%s]' % (k, _fmt(v)))
+        else:
+            colour = t["type"] == "color" and k in ("tex1", "tex2", "v00", "v01", "v10", "v11", "value")
+            out.append('"%s %s" [%s]' % ("color" if colour else "float", k, _fmt(v)))
+    line = 'Texture "%s" "%s" "%s" %s\n' % (t["name"], t["type"], t["cls"], " ".join(out))
+    return ("TransformBegin\n" + _ctm_text(t["ctm"]) + line + "TransformEnd\n") if t.get("ctm") else line
+
+
+def _mesh_text(m):
+    out = 'Shape "trianglemesh" "integer indices" [%s] "point P" [%s]' % (" ".join(str(int(i)) for i in m["indices"]), _fmt(m["P"]))
+    for key, typ in (("N", "normal"), ("uv", "float"), ("S", "vector")):
+        if m.get(key) is not None:
+            out += ' "%s %s" [%s]' % (typ, key, _fmt(m[key]))
+    return out + "\n"
 
 
 def _ctm(ctm):
@@ -179,6 +368,8 @@ def scene_text(name, jitter=False, seed=7, probe_dump=None):
     out.append('PixelFilter "box" "float xwidth" [.5] "float ywidth" [.5]\n')
     if name in PROBES:
         out.append('SurfaceIntegrator "probe" "string dump" ["%s"] "point target" [0 50 0]\n' % (probe_dump or "probe_rays.bin"))
+    elif c.get("debug"):
+        out.append('SurfaceIntegrator "debug" "string red" ["%s"] "string green" ["%s"] "string blue" ["%s"]\n' % tuple(c["debug"]))
     else:
         out.append('SurfaceIntegrator "whitted" "integer maxdepth" [%d]\n' % c.get("maxdepth", 0))
     if c.get("volume_integrator"):
@@ -188,9 +379,12 @@ def scene_text(name, jitter=False, seed=7, probe_dump=None):
         out.append("AttributeBegin\n%sLightSource \"%s\" %s\nAttributeEnd\n" % (_ctm_text(l.get("ctm", [])), l["kind"], _params(l)))
     for s in c["surfaces"]:
         kind, sp = s["shape"]
-        out.append("AttributeBegin\n" + _ctm_text(s.get("ctm", [])) + ("ReverseOrientation\n" if s.get("reverse") else ""))
+        out.append("AttributeBegin\n" + "".join(_texture_text(t) for t in s.get("textures", [])))
+        out.append(_ctm_text(s.get("ctm", [])) + ("ReverseOrientation\n" if s.get("reverse") else ""))
         out.append('Material "%s" %s\n' % (s["material"][0], _params(s["material"][1])))
-        if kind == "quad":
+        if kind == "mesh":
+            out.append(_mesh_text(sp))
+        elif kind == "quad":
             out.append('Shape "trianglemesh" "integer indices" [0 1 2 0 2 3] "point P" [%s]\n' % _fmt(sp))
         else:
             out.append('Shape "%s" %s\n' % (kind, _params(sp)))
@@ -209,14 +403,34 @@ def camera_form(cam):
 
 MATERIAL_TWINS = {"fresnel_one", "blinn_normalised_by_e_plus_1", "no_geometric_term", "sigma_unclamped", "oren_nayar_without_b", "opacity_ignored", "exponent_uncapped", "eta_unclamped",
                   "reflect_transmit_swapped", "normal_ignored"}
-SHAPE_TWINS = {"normal_not_renormalised", "inner_radius_ignored"}
+SHAPE_TWINS = {"normal_not_renormalised", "inner_radius_ignored", "u_v_swapped", "default_uvs_always", "shading_for_geometric_normal", "geometric_for_shading_normal",
+               "normal_transformed_as_vector", "sphere_v_linear_in_z", "cone_v_by_zmax_of_another_kind", "phimax_ignored_in_u"}
+TEXTURE_TWINS = {"cells_truncated_toward_zero", "corners_transposed", "fraction_not_taken", "scale_adds", "amount_complemented", "tex1_tex2_swapped", "deltas_dropped",
+                 "texture_ctm_ignored"}
+MATERIAL_TWINS |= {"kd_unclamped"}
+
+
+def _textures(decls, twin):
+    """the Texture objects of a surface's declarations, by name; a literal child is a constant node (TextureParams::Get*Texture makes one)"""
+    made = {}
+    for t in decls:
+        p = dict(t["params"])
+        mapping = F.Mapping(p.pop("mapping", "uv"), _ctm(t.get("ctm", [])), twin=twin, **{k: p.pop(k) for k in ("uscale", "vscale", "udelta", "vdelta", "v1", "v2") if k in p})
+        p.pop("aamode", None)
+        if t["cls"] in ("scale", "mix", "checkerboard"):
+            dflt = dict(tex1=1.0, tex2=0.0) if t["cls"] == "checkerboard" else dict(tex1=1.0, tex2=1.0) if t["cls"] == "scale" else dict(tex1=0.0, tex2=1.0, amount=.5)
+            for k, d in dflt.items():
+                v = p.get(k, d)
+                p[k] = made[v[1]] if isinstance(v, tuple) and len(v) == 2 and v[0] == "tex" else F.Texture("constant", value=v)
+        made[t["name"]] = F.Texture(t["cls"], mapping, twin=twin, **p)
+    return made
 LIGHT_TWINS = {"spot_axis_untransformed"}
 
 
 def form(name, wrong=False):
-    """the float64 side of a case (analytic_forms.Scene); wrong=True: its wrong twin"""
+    """the float64 side of a case (analytic_forms.Scene); wrong=True: its wrong twin; wrong="<name>": that twin (a case's `also` twins)"""
     c = CASES[name] if name in CASES else PROBES[name]
-    twin = c["twin"] if wrong else None
+    twin = wrong if isinstance(wrong, str) else c["twin"] if wrong else None
     camera = camera_form(c["camera"])
     lights = []
     for l in c["lights"]:
@@ -227,11 +441,22 @@ def form(name, wrong=False):
     for s in c["surfaces"]:
         kind, sp = s["shape"]
         m = _ctm(s.get("ctm", []))
-        shape = F.Quad(sp, m) if kind == "quad" else F.Quadric(kind, m, twin=twin if twin in SHAPE_TWINS else None, **sp)
-        surfaces.append((shape, F.Material(s["material"][0], twin=twin if twin in MATERIAL_TWINS else None, **s["material"][1])))
+        stwin = twin if twin in SHAPE_TWINS else None
+        if kind == "mesh":
+            shape = F.Mesh(sp["P"], sp["indices"], m, uv=sp.get("uv"), N=sp.get("N"), S=sp.get("S"), twin=stwin)
+        else:
+            shape = F.Quad(sp, m) if kind == "quad" else F.Quadric(kind, m, twin=stwin, **sp)
+        mtwin = twin if twin in MATERIAL_TWINS else None
+        if s.get("textures"):
+            made = _textures(s["textures"], twin if twin in TEXTURE_TWINS else None)
+            mp = {k: (made[v[1]] if isinstance(v, tuple) and len(v) == 2 and v[0] == "tex" else v) for k, v in s["material"][1].items()}
+            surfaces.append((shape, F.Textured(s["material"][0], twin=mtwin, **mp)))
+        else:
+            surfaces.append((shape, F.Material(s["material"][0], twin=mtwin, **s["material"][1])))
     med = c.get("medium")
     medium = F.Medium(med["p0"], med["p1"], med["sigma_a"], med["sigma_s"]) if med else None
-    return F.Scene(camera, surfaces, lights, medium, c.get("maxdepth", 0), twin=twin if twin not in MATERIAL_TWINS | SHAPE_TWINS | LIGHT_TWINS else None)
+    return F.Scene(camera, surfaces, lights, medium, c.get("maxdepth", 0), twin=twin if twin not in MATERIAL_TWINS | SHAPE_TWINS | LIGHT_TWINS | TEXTURE_TWINS else None,
+                   debug=c.get("debug"))
 
 
 def pixel_centres(xres=RES, yres=RES):
@@ -252,19 +477,30 @@ def measure(name, rgb, alpha):
     ix, iy = pixel_centres()
     ix, iy = ix[:RES, :RES], iy[:RES, :RES]
     sc = form(name)
-    L, hit, _ = sc.samples(ix, iy)
+    L, _, _ = sc.samples(ix, iy)
     band = F.band(sc, ix, iy)
     inc = ~band
     e = F.sample_error(rgb, L, inc)
     o, d, mint, maxt = sc.camera.rays(ix, iy)
     t, n, idx, root = sc.closest(o, d, mint, maxt)
+    hit = (idx >= 0).astype(np.float64)
+    if sc.debug:
+        # a debug frame's alpha is 1 on EVERY pixel, band or not; coverage is its `hit` channel, which the film holds after an RGB -> XYZ -> RGB
+        # round trip in float32 (next to a v of 3 a 1 reads 1 +- 2e-6 there), so it is held to 0 or 1 within the strict film bar, 1e-5, and rounded before
+        # it is compared with the form's hit mask
+        alpha_ok = bool((alpha == 1).all())
+        if "hit" in sc.debug:
+            ch = rgb[..., list(sc.debug).index("hit")]
+            alpha_ok = alpha_ok and bool(np.array_equal(np.rint(ch)[inc], hit[inc])) and float(np.abs(ch - np.rint(ch)).max()) <= 1e-5
+    else:
+        alpha_ok = bool(np.array_equal(alpha[inc], hit[inc].astype(np.float32)))
     falloff = 0.0
     spots = [l for l in sc.lights if l.kind == "spot"]
     if spots and hit.any():
         p = o + np.where(np.isfinite(t), t, 0.0)[..., None] * d
         falloff = float((spots[0].sample(p)[3] == 1)[hit > 0].mean())
     return dict(band=band, band_share=float(band.mean()), ref_err=float(e[inc].max()), hit_share=float(hit.mean()), lcase=float(np.abs(L[inc]).max()),
-                alpha_equal=bool(np.array_equal(alpha[inc], hit[inc].astype(np.float32))), far_root_share=float(((root == 1) & (hit > 0)).mean()),
+                alpha_equal=alpha_ok, far_root_share=float(((root == 1) & (hit > 0)).mean()),
                 falloff_share=falloff, L=L, e=e)
 
 
@@ -274,10 +510,10 @@ def bar(name, ref_errs):
     return BAR_FACTOR * max(ref_errs[name], float(np.median(fam)))
 
 
-def twin_share(name, rgb, band, bar_value):
-    """the share of the included samples on which the reference's film lies beyond 10 x the bar from the case's wrong twin"""
+def twin_share(name, rgb, band, bar_value, twin=True):
+    """the share of the included samples on which the reference's film lies beyond 10 x the bar from the case's wrong twin (or the named one)"""
     ix, iy = pixel_centres()
-    L, _, _ = form(name, wrong=True).samples(ix[:RES, :RES], iy[:RES, :RES])
+    L, _, _ = form(name, wrong=twin).samples(ix[:RES, :RES], iy[:RES, :RES])
     inc = ~band
     return float((F.sample_error(rgb, L, inc)[inc] > 10 * bar_value).mean())
 

@@ -1,6 +1,8 @@
 """Float64 closed forms of what one Whitted camera sample computes in a scene of a few analytic surfaces lit by delta lights: cameras,
 ray / quad and ray / quadric intersection, point / spot / distant lights, the BSDFs of matte, plastic, uber, shinymetal and translucent
-as the reference assembles them, the mirror step and the transmittance of a homogeneous medium.  Plain numpy, vectorised over samples,
+as the reference assembles them, the mirror step and the transmittance of a homogeneous medium; and of what the hit itself carries: a
+triangle mesh's barycentrics, (u, v), geometric and shading normal (Mesh), the quadrics' (u, v), the texture classes and 2-D mappings evaluated
+at the hit (Texture, Mapping), materials resolved from them per sample (Textured) and the debug integrator's channels.  Plain numpy, vectorised over samples,
 independent of the package: tests/test_analytic_host.py proves on the reference's films that these are the reference's functions,
 tests/test_gpu_analytic.py holds the device's per-sample radiance to them.
 
@@ -23,6 +25,12 @@ def _norm(v):
 
 def _dot(a, b):
     return (a * b).sum(-1)
+
+
+def _cross(a, b):
+    """np.cross over the last axis, written out (broadcasting; several times faster on large blocks)"""
+    ax, ay, az, bx, by, bz = a[..., 0], a[..., 1], a[..., 2], b[..., 0], b[..., 1], b[..., 2]
+    return np.stack([ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx], -1)
 
 
 # ------------------------------------------------------------------------------------------------ transforms (4 x 4, column vectors)
@@ -245,15 +253,17 @@ class Quadric:
             if self.kind == "sphere":
                 th = lambda c: np.arccos(np.clip(c / self.radius, -1, 1))
                 v = (th(z) - th(self.zmin)) / (th(self.zmax) - th(self.zmin))
+                if self.twin == "sphere_v_linear_in_z":
+                    v = (z - self.zmin) / (self.zmax - self.zmin)
             elif self.kind == "disk":
                 v = 1 - (np.hypot(p[..., 0], p[..., 1]) - self.inner) / (self.radius - self.inner)
             elif self.kind == "cone":
-                v = z / self.height
+                v = z / (self.radius if self.twin == "cone_v_by_zmax_of_another_kind" else self.height)
             elif self.kind == "hyperboloid":
                 v = (z - self.p1[2]) / (self.p2[2] - self.p1[2])
             else:
                 v = (z - self.zmin) / (self.zmax - self.zmin)
-            return self._phi(p) / self.phimax, v
+            return self._phi(p) / (2 * PI if self.twin == "phimax_ignored_in_u" else self.phimax), v
 
     def _clipped(self, p):
         return (p[..., 2] < self.zmin) | (p[..., 2] > self.zmax) | (self._phi(p) > self.phimax)
@@ -334,6 +344,209 @@ class Quadric:
         return np.where(ok, t, np.inf), n, root
 
 
+class Mesh:
+    """A `trianglemesh` with optional per-vertex uv, N, S under an object-to-world matrix (shapes/trianglemesh.cpp).  The vertices go to world
+    space first (:167-168).  A hit has barycentrics (b0, b1, b2) and (u, v) = sum b_i uv_i (:270-272); without "uv" EVERY triangle has
+    (0,0) (1,0) (1,1) (GetUVs, :315-328), so the inner diagonal of a two-triangle quad is a discontinuity of (u, v).  The geometric normal is
+    Normalize(Cross(dpdu, dpdv)) (core/geometry DifferentialGeometry), the triangle's plane normal up to a sign that the (u, v) mapping decides.
+    GetShadingGeometry (:71-133): with N, ns = Normalize(ObjectToWorld(sum b_i N_i)), a Normal, so under the inverse transpose; without N,
+    ns is the geometric normal; ss = Normalize(ObjectToWorld(sum b_i S_i)) or Normalize(dpdu); ts = Normalize(Cross(ss, ns)), ss = Cross(ts, ns),
+    and the shading normal is Normalize(Cross(ss, ts)) = ns whenever ss is not parallel to ns: S turns the frame, not the normal.  The
+    barycentrics GetShadingGeometry solves from (u, v) are the hit's own while the triangle's uvs are not collinear.  ReverseOrientation and
+    a mirroring transform flip signs only; every consumer here takes the line of the normal (the debug integrator's fabsf, BSDFs without glass).
+    `twin`: a deliberately wrong variant (tests only)."""
+
+    def __init__(self, P, indices, o2w=None, uv=None, N=None, S=None, twin=None):
+        self.o2w = np.eye(4) if o2w is None else o2w
+        self.twin = twin
+        self.p = xpoint(self.o2w, f32(P).reshape(-1, 3))
+        self.idx = np.asarray(indices, np.int64).reshape(-1, 3)
+        self.uv = None if uv is None else f32(uv).reshape(-1, 2)
+        self.N = None if N is None else f32(N).reshape(-1, 3)
+        self.S = None if S is None else f32(S).reshape(-1, 3)
+        self._memo = None
+        self.sub_matters = self.uv is None or self.N is not None       # the triangle hit is a discrete outcome of the sample (band)
+        if twin == "default_uvs_always":
+            self.uv = None
+
+    def _tri_uv(self, k):
+        if self.uv is None:
+            return np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0]])
+        return self.uv[self.idx[k]]
+
+    def full(self, o, d, mint, maxt):
+        """-> dict(t (inf where missed), n, ns, u, v, tri)"""
+        if self._memo is not None and self._memo[0] is o and self._memo[1] is d and self._memo[2] is mint and self._memo[3] is maxt:
+            return self._memo[4]              # Scene.closest and Scene.details ask for the same rays
+        key = (o, d, mint, maxt)
+        shape = o.shape[:-1]
+        o, d = np.broadcast_to(o, shape + (3,)).reshape(-1, 3), np.broadcast_to(d, shape + (3,)).reshape(-1, 3)
+        mint, maxt = np.broadcast_to(mint, shape).reshape(-1, 1), np.broadcast_to(maxt, shape).reshape(-1, 1)
+        p1 = self.p[self.idx[:, 0]]
+        e1, e2 = self.p[self.idx[:, 1]] - p1, self.p[self.idx[:, 2]] - p1
+        n_all = len(o)
+        # only the rays whose line passes the vertices' bounding sphere (grown by a thousandth) can meet a triangle
+        centre = (self.p.min(0) + self.p.max(0)) / 2
+        near = np.linalg.norm(_cross(centre - o, _norm(d)), axis=-1) <= 1.001 * np.linalg.norm(self.p - centre, axis=1).max()
+        o, d, mint, maxt = o[near], d[near], mint[near], maxt[near]
+        best, tri, bb = np.full(len(o), np.inf), np.full(len(o), -1, np.int64), np.zeros((len(o), 3))
+        for lo in range(0, len(o), 4096):                 # every ray against every triangle (:213-246), a block of rays at a time
+            oo, dd = o[lo:lo + 4096, None, :], d[lo:lo + 4096, None, :]
+            s1 = _cross(dd, e2)
+            div = _dot(s1, e1)
+            with np.errstate(all="ignore"):
+                od = oo - p1
+                b1 = _dot(od, s1) / div
+                s2 = _cross(od, e1)
+                b2 = _dot(dd, s2) / div
+                t = _dot(s2, e2) / div
+            ok = (div != 0) & (b1 >= 0) & (b1 <= 1) & (b2 >= 0) & (b1 + b2 <= 1) & (t >= mint[lo:lo + 4096]) & (t <= maxt[lo:lo + 4096])
+            t = np.where(ok, t, np.inf)
+            k = np.argmin(t, axis=1)
+            rows = np.arange(len(k))
+            hit = np.isfinite(t[rows, k])
+            best[lo:lo + 4096] = t[rows, k]
+            tri[lo:lo + 4096] = np.where(hit, k, -1)
+            bb[lo:lo + 4096] = np.where(hit[:, None], np.stack([1 - b1[rows, k] - b2[rows, k], b1[rows, k], b2[rows, k]], -1), 0.0)
+
+        def scatter(a, fill):
+            out = np.full((n_all,) + a.shape[1:], fill, a.dtype)
+            out[near] = a
+            return out
+        best, tri, bb = scatter(best, np.inf).reshape(shape), scatter(tri, -1).reshape(shape), scatter(bb, 0.0).reshape(shape + (3,))
+        n, ns, u, v = np.zeros(shape + (3,)), np.zeros(shape + (3,)), np.zeros(shape), np.zeros(shape)
+        for k in np.unique(tri[tri >= 0]):
+            sel = tri == k
+            i = self.idx[k]
+            uv = self._tri_uv(k)
+            du1, du2, dv1, dv2 = uv[0, 0] - uv[2, 0], uv[1, 0] - uv[2, 0], uv[0, 1] - uv[2, 1], uv[1, 1] - uv[2, 1]
+            dp1, dp2 = self.p[i[0]] - self.p[i[2]], self.p[i[1]] - self.p[i[2]]
+            det = du1 * dv2 - dv1 * du2
+            assert det != 0, "a triangle with collinear uvs: the forms do not restate CoordinateSystem's fall-back"
+            dpdu, dpdv = (dv2 * dp1 - dv1 * dp2) / det, (-du2 * dp1 + du1 * dp2) / det
+            ng = _norm(np.cross(dpdu, dpdv))
+            b = bb[sel]
+            n[sel] = ng
+            u[sel], v[sel] = b @ uv[:, 0], b @ uv[:, 1]
+            if self.N is not None and self.twin != "geometric_for_shading_normal":
+                nn = b @ self.N[i]
+                nn = xvec(self.o2w, nn) if self.twin == "normal_transformed_as_vector" else xnormal(self.o2w, nn)
+                ns[sel] = nn if self.twin == "normal_not_renormalised" else _norm(nn)
+            else:
+                ns[sel] = ng
+        if self.twin == "u_v_swapped":
+            u, v = v, u
+        if self.twin == "shading_for_geometric_normal":
+            n = ns
+        self._memo = key + (dict(t=best, n=n, ns=ns, u=u, v=v, tri=tri),)
+        return self._memo[4]
+
+    def intersect(self, o, d, mint, maxt):
+        h = self.full(o, d, mint, maxt)
+        return h["t"], h["n"], np.zeros(h["t"].shape, np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ textures
+class Mapping:
+    """TextureMapping2D (core/texture.cpp:63-149): "uv": s = uscale u + udelta, t = vscale v + vdelta; "planar": s = udelta + p . v1,
+    t = vdelta + p . v2 (world p); "spherical": with w = Normalize(WorldToTexture(p)), s = acos(w.z) / pi, t = phi / 2 pi, phi = atan2(w.y, w.x)
+    in [0, 2 pi); "cylindrical": s = (pi + atan2(w.y, w.x)) / 2 pi, t = w.z.  WorldToTexture is the inverse of the CTM at the Texture statement.
+    map() -> s, t, wrap: the coordinate that jumps by 1 across the mapping's seam (phi = 0; atan2 = +-pi), or None."""
+
+    def __init__(self, kind="uv", t2w=None, twin=None, **kw):
+        self.kind, self.twin = kind, twin
+        g = lambda k, dflt: float(f32(kw.get(k, dflt)))
+        self.su, self.sv, self.du, self.dv = g("uscale", 1), g("vscale", 1), g("udelta", 0), g("vdelta", 0)
+        self.v1, self.v2 = f32(kw.get("v1", (1, 0, 0))), f32(kw.get("v2", (0, 1, 0)))
+        if twin == "deltas_dropped" and kind == "planar":
+            self.du = self.dv = 0.0
+        self.w2t = np.linalg.inv(np.eye(4) if (t2w is None or twin == "texture_ctm_ignored") else t2w)
+
+    def map(self, p, u, v):
+        if self.kind == "uv":
+            return self.su * u + self.du, self.sv * v + self.dv, None
+        if self.kind == "planar":
+            return self.du + _dot(p, self.v1), self.dv + _dot(p, self.v2), None
+        w = _norm(xpoint(self.w2t, p))
+        if self.kind == "spherical":
+            phi = np.arctan2(w[..., 1], w[..., 0])
+            t = np.where(phi < 0, phi + 2 * PI, phi) / (2 * PI)
+            return np.arccos(np.clip(w[..., 2], -1, 1)) / PI, t, t
+        if self.kind == "cylindrical":
+            s = (PI + np.arctan2(w[..., 1], w[..., 0])) / (2 * PI)
+            return s, w[..., 2], s
+        raise ValueError(self.kind)
+
+
+class Texture:
+    """The texture classes (textures/constant.cpp, scale.cpp, mix.cpp, bilerp.cpp, uv.cpp, checkerboard.cpp with aamode "none", dimension 2).
+    A float texture travels as (f, f, f).  kind "constant": value; "scale": tex1 * tex2; "mix": (1 - amount) tex1 + amount tex2; "bilerp":
+    (1-s)(1-t) v00 + (1-s) t v01 + s (1-t) v10 + s t v11; "uv": (s - floor s, t - floor t, 0); "checkerboard": tex1 where
+    floor s + floor t is even, else tex2.  Children (tex1, tex2, amount) are Textures.  `twin`: a deliberately wrong variant (tests only)."""
+
+    def __init__(self, kind, mapping=None, twin=None, **kw):
+        self.kind, self.mapping, self.twin, self.kw = kind, mapping, twin, kw
+        if kind == "bilerp":
+            self.corners = [f32(kw[k]) * np.ones(3) for k in ("v00", "v01", "v10", "v11")]
+            if twin == "corners_transposed":
+                self.corners[1], self.corners[2] = self.corners[2], self.corners[1]
+        if kind == "constant":
+            self.value = f32(kw["value"]) * np.ones(3)
+
+    def eval(self, p, u, v, trace):
+        """-> value [..., 3]; appends to trace["cells"] the integer cell of every checkerboard / uv node evaluated and to trace["wraps"] the
+        seam coordinate of every spherical / cylindrical mapping evaluated (the discrete outcomes the band needs)"""
+        k = self.kind
+        if k == "constant":
+            return np.broadcast_to(self.value, p.shape)
+        if k in ("scale", "mix"):
+            a, b = self.kw["tex1"].eval(p, u, v, trace), self.kw["tex2"].eval(p, u, v, trace)
+            if k == "scale":
+                return a + b if self.twin == "scale_adds" else a * b
+            amt = self.kw["amount"].eval(p, u, v, trace)
+            if self.twin == "amount_complemented":
+                amt = 1 - amt
+            if self.twin == "tex1_tex2_swapped":
+                a, b = b, a
+            return (1 - amt) * a + amt * b
+        s, t, wrap = self.mapping.map(p, u, v)
+        if wrap is not None:
+            trace["wraps"].append(wrap)
+        if k == "bilerp":
+            s, t = s[..., None], t[..., None]
+            c = self.corners
+            return (1 - s) * (1 - t) * c[0] + (1 - s) * t * c[1] + s * (1 - t) * c[2] + s * t * c[3]
+        fl = np.trunc if self.twin == "cells_truncated_toward_zero" else np.floor
+        cs, ct = fl(s).astype(np.int64), fl(t).astype(np.int64)
+        trace["cells"].append(cs * 4099 + ct)
+        if k == "uv":
+            if self.twin == "fraction_not_taken":
+                cs, ct = 0, 0
+            return np.stack([s - cs, t - ct, np.zeros_like(s)], -1)
+        if k == "checkerboard":
+            a, b = self.kw["tex1"].eval(p, u, v, trace), self.kw["tex2"].eval(p, u, v, trace)
+            return np.where((((cs + ct) % 2) == 0)[..., None], a, b)
+        raise ValueError(k)
+
+
+class Textured:
+    """A material whose parameters may be Textures: resolve() evaluates them at the hit (p, u, v) and hands the per-sample arrays to Material
+    (a float parameter takes the first channel)."""
+    FLOATS = ("sigma", "roughness", "index")
+
+    def __init__(self, kind, twin=None, **kw):
+        self.kind, self.twin, self.kw = kind, twin, kw
+
+    def resolve(self, p, u, v, trace):
+        vals = {}
+        for k, x in self.kw.items():
+            if isinstance(x, Texture):
+                x = x.eval(p, u, v, trace)
+                x = x[..., 0] if k in self.FLOATS else x
+            vals[k] = x
+        return Material(self.kind, twin=self.twin, **vals)
+
+
 # ------------------------------------------------------------------------------------------------ lights
 class Light:
     """kind "point" (lights/point.cpp:49-61), "spot" (lights/spot.cpp:52-78, :96-117), "distant" (lights/distant.cpp:54-68), under
@@ -409,9 +622,18 @@ def approx_eta(r):
 
 def blinn_exponent(roughness):
     """Blinn(1 / roughness) with the cap (core/reflection.h:313)"""
+    if isinstance(roughness, np.ndarray) and roughness.ndim:       # per sample, from a texture
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e = 1.0 / roughness
+        return np.where((e > 1000) | np.isnan(e), 1000.0, e)
     with np.errstate(divide="ignore"):
         e = 1.0 / float(f32(roughness))
     return 1000.0 if (e > 1000 or np.isnan(e)) else e
+
+
+def _param(x):
+    """a material parameter: a literal of the scene file (float32) or, from a texture, a float64 array over the samples"""
+    return x if isinstance(x, np.ndarray) and x.dtype == np.float64 and x.ndim else f32(x)
 
 
 def lambert(r, wo, wi, n):
@@ -457,13 +679,22 @@ class Material:
 
     def __init__(self, kind, twin=None, **kw):
         self.kind, self.twin = kind, twin
-        c = lambda k, d: np.clip(f32(kw.get(k, d)) * np.ones(3), 0, 1)          # Spectrum::Clamp()
+        # Spectrum::Clamp(): at 0 below, unbounded above (core/color.h:161)
+        c = (lambda k, d: _param(kw.get(k, d)) * np.ones(3)) if twin == "kd_unclamped" else (lambda k, d: np.maximum(_param(kw.get(k, d)) * np.ones(3), 0))
+        per_sample = any(isinstance(x, np.ndarray) and x.ndim for x in kw.values())          # a parameter evaluated from a texture
         self.refl, self.trans = [], []
         dielectric = (lambda ch: fr_dielectric(ch, 1.5, 1.0)[..., None]) if twin != "fresnel_one" else (lambda ch: np.ones(ch.shape + (1,)))
         geo = twin != "no_geometric_term"
         nadd = 1 if twin == "blinn_normalised_by_e_plus_1" else 2
         if kind == "matte":
-            kd, sig = c("Kd", 1), min(max(float(f32(kw.get("sigma", 0))), 0.0), 90.0)
+            kd = self.kd = c("Kd", 1)
+            if per_sample:
+                # Oren-Nayar at sigma = 0 has A = 1, B = 0: the Lambert branch (materials/matte.cpp:58-61) is the same function there
+                sg = _param(kw.get("sigma", 0)) * np.ones(kd.shape[:-1])
+                sig = sg if twin == "sigma_unclamped" else np.clip(sg, 0.0, 90.0)
+                self.refl.append(lambda wo, wi, n: oren_nayar(kd, sig, wo, wi, n, twin != "oren_nayar_without_b"))
+                return
+            sig = min(max(float(f32(kw.get("sigma", 0))), 0.0), 90.0)
             if twin == "sigma_unclamped":
                 sig = float(f32(kw.get("sigma", 0)))
             self.refl.append((lambda wo, wi, n: lambert(kd, wo, wi, n)) if sig == 0 else (lambda wo, wi, n: oren_nayar(kd, sig, wo, wi, n, twin != "oren_nayar_without_b")))
@@ -473,7 +704,7 @@ class Material:
                 op = np.ones(3)
             kd, ks, e = op * c("Kd", 1), op * c("Ks", 1), blinn_exponent(kw.get("roughness", .1))
             if twin == "exponent_uncapped":
-                e = 1.0 / float(f32(kw.get("roughness", .1)))
+                e = 1.0 / _param(kw.get("roughness", .1))
             if kd.any() or kind == "plastic":
                 self.refl.append(lambda wo, wi, n: lambert(kd, wo, wi, n))
             if ks.any() or kind == "plastic":
@@ -547,11 +778,50 @@ class Medium:
 # ------------------------------------------------------------------------------------------------ the integrator
 class Scene:
     """surfaces: [(shape, Material)], lights: [Light], medium or None, maxdepth of SurfaceIntegrator "whitted".
+    A surface's material may be a Textured: it is resolved at every hit, on every recursion level.
     twin: a deliberately wrong variant of the whole form (tests only): "near_root_always", "shadow_unclipped", "falloff_cubed",
-    "no_inverse_square", "no_cosine", "first_light_only", "mirror_unlit"."""
+    "no_inverse_square", "no_cosine", "first_light_only", "mirror_unlit", "wall_material_at_the_floor"."""
 
-    def __init__(self, camera, surfaces, lights, medium=None, maxdepth=0, twin=None):
+    def __init__(self, camera, surfaces, lights, medium=None, maxdepth=0, twin=None, debug=None):
+        """debug: the channel triple of SurfaceIntegrator "debug" (u v nx ny nz snx sny snz one zero hit), or None for "whitted" """
         self.camera, self.surfaces, self.lights, self.medium, self.maxdepth, self.twin = camera, surfaces, lights, medium, maxdepth, twin
+        self.debug = debug
+        self.trace = dict(cells=[], wraps=[])
+        self.mats = {}
+
+    def details(self, o, d, mint, maxt, idx):
+        """(u, v), the shading normal and the sub-outcome (the triangle, where it decides a value) of the closest hits: a mesh's from
+        Mesh.full, a quadric's own parametrisation with the shading normal its geometric one, a Quad's left at 0 (its cases read neither)"""
+        shape = o.shape[:-1]
+        u, v, ns, sub = np.zeros(shape), np.zeros(shape), np.zeros(shape + (3,)), np.zeros(shape, np.int64)
+        for i, (shp, _) in enumerate(self.surfaces):
+            sel = idx == i
+            if not sel.any():
+                continue
+            if isinstance(shp, Mesh):
+                h = shp.full(o, d, mint, maxt)
+                u, v, ns = np.where(sel, h["u"], u), np.where(sel, h["v"], v), np.where(sel[..., None], h["ns"], ns)
+                if shp.sub_matters:
+                    sub = np.where(sel, h["tri"] + 1, sub)
+            else:
+                t, n, _ = shp.intersect(o, d, mint, maxt)
+                ns = np.where(sel[..., None], n, ns)
+                if isinstance(shp, Quadric):
+                    qu, qv = shp.uv(o + np.where(sel, t, 0.0)[..., None] * d)
+                    u, v = np.where(sel, qu, u), np.where(sel, qv, v)
+        return u, v, ns, sub
+
+    def debug_li(self, o, d, mint, maxt):
+        """DebugIntegrator::Li (integrators/debug.cpp:61-133): per channel u, v, |ng|, |ns| of the camera ray's hit (0 on a miss), the
+        constants, the hit mask; alpha is 1 for every sample (:69), misses included"""
+        t, n, idx, root = self.closest(o, d, mint, maxt)
+        hit = idx >= 0
+        u, v, ns, sub = self.details(o, d, mint, maxt, idx)
+        one = np.ones(hit.shape)
+        val = dict(u=u, v=v, nx=np.abs(n[..., 0]), ny=np.abs(n[..., 1]), nz=np.abs(n[..., 2]), snx=np.abs(ns[..., 0]), sny=np.abs(ns[..., 1]),
+                   snz=np.abs(ns[..., 2]), one=one, zero=0 * one, hit=one)
+        L = np.stack([val[c] if c == "one" else np.where(hit, val[c], 0.0) for c in self.debug], -1)
+        return L, one, ((idx + 1) * 2 + root) * 100003 + sub
 
     def closest(self, o, d, mint, maxt):
         """-> t, n, surface index (-1: none), root"""
@@ -581,6 +851,22 @@ class Scene:
         ts = np.where(hit, t, 0.0)
         p = o + ts[..., None] * d
         wo = -d
+        surfaces = self.surfaces
+        if any(isinstance(m, Textured) for _, m in surfaces):
+            # the materials resolved at this hit; every integer cell a texture took is part of the sample's discrete outcome
+            u, v, _, sub = self.details(o, d, mint, maxt, idx)
+            surfaces = []
+            for m_no, (shp, m) in enumerate(self.surfaces):
+                if isinstance(m, Textured):
+                    tr = dict(cells=[], wraps=[])
+                    m = m.resolve(p, u, v, tr)
+                    sel = hit & (idx == m_no)
+                    for c in tr["cells"]:
+                        sig = sig * 8191 + np.where(sel, c, 0)
+                    self.trace["wraps"] += [np.where(sel, w, 0.0) for w in tr["wraps"]]
+                surfaces.append((shp, m))
+            sig = sig * 1031 + sub
+        self.mats[depth] = [m for _, m in surfaces]
         for li_no, light in enumerate(self.lights):
             if self.twin == "first_light_only" and li_no > 0:
                 break
@@ -600,7 +886,7 @@ class Scene:
             tr = 1.0
             if self.medium is not None:
                 tr = self.medium.transmittance(so, sd, lo, hi)
-            for m_no, (_, mat) in enumerate(self.surfaces):
+            for m_no, (_, mat) in enumerate(surfaces):
                 sel = hit & (idx == m_no) & ~occluded
                 if mat.kind in ("mirror", "glass") or not sel.any():
                     continue
@@ -609,7 +895,7 @@ class Scene:
                     term = mat.f(wo, wi, n) * lcol * cos * tr
                 L = np.where(sel[..., None], L + np.nan_to_num(term), L)
         if depth < self.maxdepth:
-            for m_no, (_, mat) in enumerate(self.surfaces):
+            for m_no, (_, mat) in enumerate(surfaces):
                 sel = hit & (idx == m_no)
                 if mat.kind not in ("mirror", "glass") or not sel.any():
                     continue
@@ -625,7 +911,10 @@ class Scene:
                     l2, _, s2 = self.li(p, wi, RAY_EPSILON, np.inf, depth + 1)
                     if self.twin == "mirror_unlit":
                         l2 = l2 * 0
-                    L = np.where(ok[..., None], L + mat.kr * fr[..., None] * l2, L)
+                    kr = mat.kr
+                    if self.twin == "wall_material_at_the_floor":     # the record of the reflected ray's hit read where the mirror's own is due
+                        kr = next(m.kd for m in self.mats[depth + 1] if m.kind == "matte")
+                    L = np.where(ok[..., None], L + kr * fr[..., None] * l2, L)
                     sig = np.where(ok, sig * 100003 + s2, sig)
                 if mat.kind == "glass":
                     # SpecularTransmission::Sample_f (core/reflection.cpp:104-127): the side is the sign of cos(wo) against the SHADING normal,
@@ -650,6 +939,9 @@ class Scene:
     def samples(self, ix, iy):
         """radiance, alpha and signature of the camera samples at image positions (ix, iy)"""
         o, d, mint, maxt = self.camera.rays(ix, iy)
+        self.trace = dict(cells=[], wraps=[])       # wraps: the seam coordinates met by this call (read by band())
+        if self.debug:
+            return self.debug_li(o, d, mint, maxt)
         return self.li(o, d, mint, maxt)
 
 
@@ -659,17 +951,22 @@ BAND_OFFSET = 0.02      # pixels
 def band(scene, ix, iy):
     """The exclusion band, in float64 geometric terms only: a sample is left out when the scene's discrete outcome (Scene.li's signature:
     which surface and root the camera ray meets, and per light whether the shadow segment is blocked, on which side of the normal wi and
-    wo lie (the terminator, the silhouette's far side) and whether the point is outside the spot's cone) differs at any of eight image
+    wo lie (the terminator, the silhouette's far side) and whether the point is outside the spot's cone; the integer cell of every
+    checkerboard and uv texture evaluated; the triangle hit where a mesh has no uvs or has N) differs, or the seam coordinate of a spherical
+    or cylindrical mapping jumps (Scene.trace["wraps"]: phi = 0, atan2 = +-pi), at any of eight image
     positions BAND_OFFSET pixels away.  At a 60 degree field of view over 64 pixels that is 3e-4 rad of the camera ray, a few hundred
     times the float32 rounding of a ray direction; no error of any renderer enters."""
     ix, iy = np.asarray(ix, np.float64), np.asarray(iy, np.float64)
     _, _, s0 = scene.samples(ix, iy)
+    w0 = scene.trace["wraps"]
     out = np.zeros(ix.shape, bool)
     for dx in (-1, 0, 1):
         for dy in (-1, 0, 1):
             if dx or dy:
                 _, _, s = scene.samples(ix + dx * BAND_OFFSET, iy + dy * BAND_OFFSET)
                 out |= s != s0
+                for a, b in zip(scene.trace["wraps"], w0):       # across a mapping's seam the coordinate jumps by 1
+                    out |= np.abs(a - b) > 0.5
     return out
 
 

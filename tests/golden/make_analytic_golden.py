@@ -9,7 +9,10 @@ pixel centres.  For each case the float64 form (tests/analytic_forms.py) is eval
 (analytic_forms.band: float64 geometry only) and <name>.npz stores the scene text, the film (rgb, alpha), the band mask, `ref_err` (the
 reference's largest error e outside the band, analytic_forms.sample_error) and `band_share`.  The generator refuses a fixture whose band
 exceeds 3 % of the samples, one whose spot light puts too few samples into the falloff zone, and one that is insensitive: the case's
-wrong twin must put at least 5 % of the included samples beyond 10 x the case's bar (analytic_cases.bar) against the reference's film.
+wrong twin must put at least 5 % of the included samples beyond 10 x the case's bar (analytic_cases.bar) against the reference's film
+(every twin of a case that names more than one: `also`).  It refuses too a hit share outside [5 %, 100 %), a ref_err of 2e-4 or more (the form
+would lack a term), a debug frame ("geometry" cases) whose alpha is not 1 on every pixel or whose `hit` channel is not the form's hit mask
+outside the band, and a fixture above 64 KB.
 probe_ortho_quadrics.npz, probe_env_quadrics.npz and probe_lens_quadrics.npz hold the records of the probe integrator plugin (oracle/ref/probe_integrator.cpp: camera ray
 and closest hit t, p, n, u, v per camera sample) for an orthographic camera with a screen window, an environment camera and a thin-lens perspective camera that look at one of
 every quadric, the band of analytic_forms.ray_band and the reference's deviations from the float64 camera and intersectors.
@@ -29,6 +32,7 @@ import __graft_entry__ as g  # noqa: E402
 import analytic_cases as A  # noqa: E402
 
 OUT = os.path.join(HERE, "analytic")
+MAX_BYTES = 64 * 1024          # what the other generators allow a fixture
 
 
 def main():
@@ -58,20 +62,27 @@ def main():
         m = A.measure(name, rgb, alpha)
         print("%-28s ref_err %.3g  band %.4f  hits %.3f  Lcase %.3g  film max %.3g  far roots %.3f  falloff share %.3f" %
               (name, m["ref_err"], m["band_share"], m["hit_share"], m["lcase"], float(rgb.max()), m["far_root_share"], m["falloff_share"]))
-        assert m["alpha_equal"], "%s: alpha differs from the form's hit mask outside the band" % name
+        assert m["alpha_equal"], "%s: alpha differs from the form's hit mask outside the band (a debug frame: alpha is not 1 everywhere, or its hit channel differs)" % name
+        assert 0.05 <= m["hit_share"] < 1.0 and m["ref_err"] < 2e-4, "%s: hit share %.3f, ref_err %.3g" % (name, m["hit_share"], m["ref_err"])
         assert m["band_share"] <= A.BAND_CAP, "%s: band %.4f" % (name, m["band_share"])
         assert m["falloff_share"] >= A.CASES[name].get("min_falloff_share", 0), name
-        done[name] = (text, rgb, alpha, m)
+        done[name] = (text, rgb, alpha, m, st)
     # the bars need every case's ref_err (the family median): the cases not regenerated now come from their fixtures
     ref_errs = {n: float(np.load(os.path.join(OUT, n + ".npz"))["ref_err"]) for n in A.CASES if n not in done and os.path.exists(os.path.join(OUT, n + ".npz"))}
     ref_errs.update({n: d[3]["ref_err"] for n, d in done.items()})
-    for name, (text, rgb, alpha, m) in done.items():
+    for name, (text, rgb, alpha, m, st) in done.items():
         bar = A.bar(name, ref_errs)
         share = A.twin_share(name, rgb, m["band"], bar)
         print("%-28s bar %.3g  twin %-26s beyond 10 x bar on %.3f" % (name, bar, A.CASES[name]["twin"], share))
         assert share >= A.MIN_TWIN_SHARE, "%s: the wrong twin %s differs on only %.3f of the samples" % (name, A.CASES[name]["twin"], share)
-        np.savez_compressed(os.path.join(OUT, name + ".npz"), scene=np.array(text), rgb=rgb, alpha=alpha, band=m["band"], ref_err=np.array(m["ref_err"]),
+        for also in A.CASES[name].get("also", ()):
+            more = A.twin_share(name, rgb, m["band"], bar, twin=also)
+            print("%-28s              twin %-26s beyond 10 x bar on %.3f" % ("", also, more))
+            assert more >= A.MIN_TWIN_SHARE, "%s: the wrong twin %s differs on only %.3f of the samples" % (name, also, more)
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, scene=np.array(text), rgb=rgb, alpha=alpha, band=m["band"], ref_err=np.array(m["ref_err"]),
                             band_share=np.array(m["band_share"]), twin_share=np.array(share), stats=np.array(json.dumps(st)))
+        assert os.path.getsize(path) < MAX_BYTES, (name, os.path.getsize(path))
 
 
 if __name__ == "__main__":

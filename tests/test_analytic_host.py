@@ -1,7 +1,8 @@
 """The proof that the float64 forms of tests/analytic_forms.py are the reference's functions: from the fixtures of tests/golden/analytic/
 alone (films of the UNMODIFIED reference, tests/golden/make_analytic_golden.py) the band and ref_err are recomputed and must equal what is
 stored, the band stays under its cap, the reference's film outside the band is within ref_err of the form, and every case's wrong twin
-is rejected by its fixture (at least 5 % of the included samples beyond 10 x the case's bar); the three camera probes (orthographic,
+is rejected by its fixture (at least 5 % of the included samples beyond 10 x the case's bar); the "geometry" cases (SurfaceIntegrator "debug":
+u, v, normals, hit mask) and the "textures" cases go through the same tests, a debug frame's alpha being 1 on every pixel; the three camera probes (orthographic,
 environment and thin-lens camera, every quadric) give the forms' rays, t, hit point, normal and (u, v).  No GPU, no package: numpy only."""
 import os
 
@@ -35,6 +36,7 @@ def test_every_case_has_its_fixture_and_the_table_covers_the_families():
     assert have == sorted(NAMES)
     assert {c["family"] for c in A.CASES.values()} == set(A.FAMILIES)
     assert len(NAMES) >= 29
+    assert sum(c["family"] == "geometry" for c in A.CASES.values()) >= 13 and sum(c["family"] == "textures" for c in A.CASES.values()) >= 13
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -53,7 +55,11 @@ def test_band_is_under_the_cap_and_the_reference_film_is_within_ref_err(measured
     assert m["band_share"] <= A.BAND_CAP
     inc = ~m["band"]
     assert m["e"][inc].max() <= float(g["ref_err"]) * (1 + 1e-6)
-    assert m["alpha_equal"]                                  # alpha is exactly 1 on hits and 0 on misses outside the band
+    # alpha is exactly 1 on hits and 0 on misses outside the band; a geometry case: exactly 1 on EVERY pixel, and its `hit` channel, where it has
+    # one, is the form's hit mask outside the band (analytic_cases.measure)
+    assert m["alpha_equal"]
+    if A.CASES[name]["family"] == "geometry":
+        assert (g["alpha"] == 1).all()
     assert m["falloff_share"] >= A.CASES[name].get("min_falloff_share", 0)
     assert 0.05 <= m["hit_share"] < 1.0                       # hits and misses in every frame
     # the reference is float32: a ref_err far above its rounding would mean a term the form does not have
@@ -67,6 +73,9 @@ def test_wrong_twin_is_rejected(measured, name):
     share = A.twin_share(name, g["rgb"], m["band"], A.bar(name, ref_errs))
     assert share >= A.MIN_TWIN_SHARE, (A.CASES[name]["twin"], share)
     assert abs(share - float(g["twin_share"])) <= 1.0 / (A.RES * A.RES)
+    for also in A.CASES[name].get("also", ()):
+        more = A.twin_share(name, g["rgb"], m["band"], A.bar(name, ref_errs), twin=also)
+        assert more >= A.MIN_TWIN_SHARE, (also, more)
 
 
 def test_quadric_cases_show_the_inside_through_the_cut(measured):

@@ -8,7 +8,10 @@ The error of a sample is e = max_c |got - L| / (max_c |L| + 0.01 Lcase) (analyti
 discontinuity of the float64 scene (analytic_forms.band) are left out, at most 3 % per case and never by the size of an error; a sample
 passes if e <= 4 max(ref_err(case), median ref_err of the case's family), ref_err being the UNMODIFIED reference's own largest e on the
 fixture's film (tests/golden/analytic/, tests/test_analytic_host.py).  The films go against the fixtures' films under the strict bar of
-tests/test_gpu_parity.py, every pixel within 1e-5, on every case, quadrics included, outside the fixture's band."""
+tests/test_gpu_parity.py, every pixel within 1e-5, on every case, quadrics included, outside the fixture's band.
+
+The "geometry" cases hold the debug integrator's records (u, v, |ng|, |ns|, the hit mask of each camera sample, alpha exactly 1) to the float64 meshes
+and quadrics, the "textures" cases a Whitted sample of a surface whose material is resolved from a Texture graph at the hit: same measure, band and bars."""
 import os
 
 import numpy as np
@@ -22,7 +25,8 @@ from gpu_checks import need_gpu
 pytestmark = pytest.mark.gpu
 
 NAMES = list(A.CASES)
-FLAVOUR_CASES = ["plastic_rough_.02", "quadric_hyperboloid", "medium_homogeneous"]      # one lobe, one quadric, the medium
+FLAVOUR_CASES = ["plastic_rough_.02", "quadric_hyperboloid", "medium_homogeneous",       # one lobe, one quadric, the medium,
+                 "geom_mesh_n_shading", "tex_mix_depth4"]                                 # one debug frame, one textured frame
 
 
 def load(name):
@@ -63,6 +67,8 @@ def check_samples(name, label, rec, bar):
     assert np.isfinite(rec[:, 0:4]).all(), name
     assert band.mean() <= A.BAND_CAP, (name, label, band.mean())
     assert np.array_equal(rec[inc, 3], hit[inc].astype(np.float32)), (name, label, "alpha is not exactly 1 on hits and 0 on misses")
+    if A.CASES[name]["family"] == "geometry":            # a debug frame: 1 for every sample, misses and the band included
+        assert (rec[:, 3] == 1).all(), (name, label, "a debug sample's alpha is not exactly 1")
     assert e[inc].max() <= bar, (name, label, float(e[inc].max()), bar, int((e[inc] > bar).sum()))
     return float(e[inc].max())
 
@@ -117,7 +123,7 @@ def test_jittered_samples(pkg, ref_errs, name):
 @pytest.mark.parametrize("name", FLAVOUR_CASES)
 def test_forced_flavours_give_the_same_records(pkg, name, monkeypatch):
     """The queue pipeline and both occupancy flavours of the timed megakernel give, sample by sample (matched by image position), the
-    bit-identical records of the default flavour."""
+    bit-identical records of the default flavour.  A debug frame always runs its own megakernel and reports pipeline 0."""
     need_gpu(pkg)
     ps = pkg.ParsedScene(text=A.scene_text(name, jitter=True))
     ds = pkg.DeviceScene(ps)
@@ -140,7 +146,7 @@ def test_forced_flavours_give_the_same_records(pkg, name, monkeypatch):
     for counting in (False, True):
         ds.set_counting(counting)
         got = records()
-        assert ds.last_stats()["pipeline"] == 1
+        assert ds.last_stats()["pipeline"] == (0 if A.CASES[name]["family"] == "geometry" else 1)
         assert np.array_equal(got, ref), (name, "PBRT_HIP_PIPELINE=1", counting, float(np.abs(got - ref).max()))
     ds.close()
 
