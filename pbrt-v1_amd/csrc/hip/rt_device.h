@@ -1,6 +1,7 @@
 // rt_device.h -- device-visible scene / frame descriptors (HBM layout; see DESIGN.md "Data layout")
 #pragma once
 #include "rt_math.h"
+#include "rt_fastdiv.h"
 #include "../../../include/pbrt_hip.h"
 #include "../../../include/pbrt_hip_texture.h"
 
@@ -135,6 +136,7 @@ struct DevFrame {
     int pipeline;                // host-side choice: the queue pipeline (rt_pipeline.h) instead of the megakernel (not read by the device)
     unsigned long long total_work;     // samples this shard renders
     unsigned long long total_pixels;   // pixels in the sample extent
+    FrameDiv div;                      // multipliers and shifts for the frame-constant divisors of the work fetch (rt_fastdiv.h; make_frame fills them last)
     // sampler dimension table (Sample::oneD/twoD, sampling.cpp:41-70)
     int n1d, n2d;
     unsigned lhs_total;          // draws consumed by LatinHypercube per sample

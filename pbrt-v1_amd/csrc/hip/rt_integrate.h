@@ -147,7 +147,7 @@ RT_DEV void sample_write(const DevFrame &fr, const Lane &ln, V3 Ls, float alpha,
     if (Ls.x != Ls.x || Ls.y != Ls.y || Ls.z != Ls.z) { Ls = mk3(0.f); ++bad; }
     else if (y < -1e-5) { Ls = mk3(0.f); ++bad; }
     else if (isinf(y)) { Ls = mk3(0.f); ++bad; }
-    const uint32_t lp = ln.work / uint32_t(fr.spp);
+    const uint32_t lp = fastdiv(ln.work, fr.div.spp);
     float4 RT_G *rec = RT_GPTR(float4, fr.samples) + sample_slot(lp, ln.work - lp * uint32_t(fr.spp), fr.spp);
 #if RT_SAMPLE_NT
     // written once, read once by the film gather after the kernel: keep the records out of the way of the tree's lines in L2 (non-temporal stores)
@@ -167,7 +167,7 @@ RT_DEV void sample_write(const DevFrame &fr, const Lane &ln, V3 Ls, float alpha,
 RT_DEV void stratified_camera_sample(const DevFrame &fr, uint32_t pixel_index, int s, int px, int py,
                                      uint32_t pix_base, float &ix, float &iy, float &lu, float &lv, bool need_lens) {
     const int n = fr.spp;
-    const int sx = s % fr.xs, sy = s / fr.xs;
+    const int sy = int(fastdiv(unsigned(s), fr.div.xs)), sx = s - sy * fr.xs;       // (0 <= s < spp: the unsigned quotient is the signed one)
     const float dx = 1.f / fr.xs, dy = 1.f / fr.ys;
     float jx = 0.5f, jy = 0.5f;
     if (fr.jitter) { jx = rng_f32(pix_base, 2 * s); jy = rng_f32(pix_base, 2 * s + 1); }
@@ -231,12 +231,12 @@ RT_DEV bool work_to_sample(const DevFrame &fr, unsigned long long w, unsigned lo
     if (fr.tile_w > 0) {                                    // 2-D tiles: a tile is a tile_w x tile_h block of the sample extent; the pixels of
         // the border tiles that fall off the extent are skipped.  make_frame guarantees n_tiles * tile_pixels * spp < 2^32: all 32-bit
         const unsigned w32 = unsigned(w), pt = unsigned(per_tile);
-        const unsigned lt = w32 / pt, rem = w32 - lt * pt;
+        const unsigned lt = fastdiv(w32, fr.div.per_tile), rem = w32 - lt * pt;
         const unsigned tile = lt * unsigned(fr.shard_count) + unsigned(fr.shard_index);
-        const unsigned q = rem / unsigned(fr.spp);
+        const unsigned q = fastdiv(rem, fr.div.spp);
         s = int(rem - q * unsigned(fr.spp));
-        const unsigned ty = tile / unsigned(fr.tiles_x), tx = tile - ty * unsigned(fr.tiles_x);
-        const unsigned qy = q / unsigned(fr.tile_w), qx = q - qy * unsigned(fr.tile_w);
+        const unsigned ty = fastdiv(tile, fr.div.tiles_x), tx = tile - ty * unsigned(fr.tiles_x);
+        const unsigned qy = fastdiv(q, fr.div.tile_w), qx = q - qy * unsigned(fr.tile_w);
         const unsigned px = tx * unsigned(fr.tile_w) + qx, py = ty * unsigned(fr.tile_h) + qy;
         const unsigned ew = unsigned(fr.x_end - fr.x_start), eh = unsigned(fr.y_end - fr.y_start);
         pixel = (unsigned long long)py * ew + px;
@@ -244,9 +244,9 @@ RT_DEV bool work_to_sample(const DevFrame &fr, unsigned long long w, unsigned lo
     }
     if (fr.total_work <= 0xffffffffull && per_tile <= 0xffffffffull) {
         const unsigned w32 = unsigned(w), pt = unsigned(per_tile);
-        const unsigned lt = w32 / pt, rem = w32 - lt * pt;
+        const unsigned lt = fastdiv(w32, fr.div.per_tile), rem = w32 - lt * pt;
         const unsigned long long tile = (unsigned long long)lt * unsigned(fr.shard_count) + unsigned(fr.shard_index);
-        const unsigned q = rem / unsigned(fr.spp);
+        const unsigned q = fastdiv(rem, fr.div.spp);
         pixel = tile * unsigned(fr.tile_pixels) + q;
         s = int(rem - q * unsigned(fr.spp));
         return pixel < fr.total_pixels;
@@ -266,19 +266,23 @@ RT_DEV bool work_to_sample(const DevFrame &fr, unsigned long long w, unsigned lo
 RT_DEV void tile_order_to_sample(const DevFrame &fr, unsigned w, unsigned &pixel, int &s) {
     const unsigned spp = unsigned(fr.spp), T = unsigned(fr.mega_tile);
     const unsigned W = unsigned(fr.x_end - fr.x_start), H = unsigned(fr.y_end - fr.y_start);
-    const unsigned wp = w / spp; s = int(w - wp * spp);
-    const unsigned row_px = W * T, ty = wp / row_px, rem = wp - ty * row_px;
-    const unsigned h_t = min(T, H - ty * T), full = T * h_t, tiles_x = (W + T - 1u) / T;
-    unsigned tx = rem / full; tx = tx < tiles_x ? tx : tiles_x - 1u;
+    // every divisor is a frame constant, the clipped blocks' height and width included (two values each): rt_fastdiv.h
+    const FrameDiv &dv = fr.div;
+    const unsigned wp = fastdiv(w, dv.spp); s = int(w - wp * spp);
+    const unsigned row_px = W * T, ty = fastdiv(wp, dv.row_px), rem = wp - ty * row_px;
+    const unsigned h_t = min(T, H - ty * T), full = T * h_t, tiles_x = dv.blocks_x;
+    const FastDiv &df = h_t < T ? dv.block[1] : dv.block[0];
+    unsigned tx = fastdiv(rem, df); tx = tx < tiles_x ? tx : tiles_x - 1u;
     const unsigned rem2 = rem - tx * full, w_t = min(T, W - tx * T);
-    const unsigned qy = rem2 / w_t, qx = rem2 - qy * w_t;
+    const FastDiv &dw = w_t < T ? dv.block_w[1] : dv.block_w[0];
+    const unsigned qy = fastdiv(rem2, dw), qx = rem2 - qy * w_t;
     pixel = (ty * T + qy) * W + tx * T + qx;
 }
 
 RT_DEV void setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned long long pixel, int s, Ray &ray) {
     const int w = fr.x_end - fr.x_start;
     int px, py;
-    if (fr.total_pixels <= 0xffffffffull) { const unsigned row = unsigned(pixel) / unsigned(w); px = fr.x_start + int(unsigned(pixel) - row * unsigned(w)); py = fr.y_start + int(row); }
+    if (fr.total_pixels <= 0xffffffffull) { const unsigned row = fastdiv(unsigned(pixel), fr.div.width); px = fr.x_start + int(unsigned(pixel) - row * unsigned(w)); py = fr.y_start + int(row); }
     else { px = fr.x_start + int(pixel % w); py = fr.y_start + int(pixel / w); }
     const uint32_t n0 = uint32_t(pixel * fr.spp);
     ln.sample_index = n0 + uint32_t(s);
@@ -353,6 +357,12 @@ RT_DEV int frame_pop(const DevFrame &fr, Lane &ln, unsigned gtid, V3 child) {
     ln.v.mat = __float_as_int(q[21 * st]);
     if (EXT) ln.v.ng = mk3(q[22 * st], q[23 * st], q[24 * st]);
     return after;
+}
+
+// UniformSampleAllLights' loop has run through every light (transport.cpp:31-50): L += its sum, then the specular recursion (directlighting.cpp:106-126)
+RT_DEV void all_lights_done(Lane &ln) {
+    ln.L = ln.L + ln.L_all;
+    ln.stage = ST_SPECULAR;
 }
 
 // DEFER (queue pipeline, rt_pipeline.h): the ray is only recorded; the trace kernel starts the traversal
@@ -833,7 +843,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         }
         if (INTEG == RT_INTEGRATOR_DIRECT) {
             // UniformSampleAllLights transport.cpp:31-50 with the dimensions of directlighting.cpp:46-53
-            if (ln.li >= nLights) { ln.L = ln.L + ln.L_all; ln.stage = ST_SPECULAR; return; }
+            if (ln.li >= nLights) { all_lights_done(ln); return; }
             const DimReq RT_G *ld = RT_GPTR(const DimReq, fr.light_dims) + 3 * ln.li;
             const DimReq rl = ld[0], rb = ld[1], rc = ld[2];
             if (ln.lj == 0) ln.Ld_light = mk3(0.f);
@@ -953,6 +963,9 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 ln.lj = 0; ++ln.li;
             }
             ln.stage = ST_DIRECT_NEXT;
+            // The last light's last sample: leave the loop here.  ST_DIRECT_NEXT ran earlier in this pass (advance_pass), so going back through it for its
+            // exit statements alone cost every hit sample a whole extra pass; ST_SPECULAR comes later in this one.
+            if (ln.li >= nLights) all_lights_done(ln);
         }
         return;
     }

@@ -553,6 +553,9 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
         }
         if (fr.trav_mode != 3 || fr.high_occupancy) fr.trav_mode = 2;  // (the high-occupancy kernels carry no pooled-leaf scratch)
     }
+    // the work fetch divides by these frame constants only (rt_fastdiv.h); nothing below or in rt_render changes one of them
+    fr.div = framediv_make(unsigned(fr.spp), unsigned(fr.xs), unsigned(fr.x_end - fr.x_start), unsigned(fr.y_end - fr.y_start), unsigned(fr.mega_tile),
+                           (unsigned long long)fr.tile_pixels * fr.spp, unsigned(fr.tile_w), unsigned(fr.tiles_x));
     fr.work_counter = s->work_counter; fr.counters = s->counters; fr.spill = s->spill; fr.n_threads = s->n_threads;
     fr.frames = s->frames;
     if (need_film && !s->accum) return fail(RT_ESTATE, "rt_render: no film bound (call rt_film_bind first)");
