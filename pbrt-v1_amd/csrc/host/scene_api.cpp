@@ -3,6 +3,7 @@
 #include "../../../include/pbrt_hip_desc.h"
 #include "../../../include/pbrt_hip_material.h"
 #include "exr_io.h"
+#include "shape_refine.h"
 #include "../../../include/pbrt_hip_plugin.h"
 #include <dlfcn.h>
 #include <unistd.h>
@@ -656,25 +657,44 @@ void PbrtApi::Shape(const std::string &n, const ParamList &p) {                 
     if (!verifyWorld("Shape")) return;
     ParamSet ps(p);
     if (n == "sphere" || n == "disk" || n == "cylinder" || n == "cone" || n == "paraboloid" || n == "hyperboloid") { quadricShape(n, ps); return; }
+    if (n == "heightfield" || n == "nurbs" || n == "loopsubdiv") {                   // Shape::Refine of the three CanIntersect() == false shapes (shape_refine.h)
+        RefinedMesh refined;
+        const bool made = n == "heightfield" ? RefineHeightfield(ps, &refined) : (n == "nurbs" ? RefineNurbs(ps, &refined) : RefineLoopSubdiv(ps, &refined));
+        if (!made) return;
+        MeshArrays a;
+        a.vi = refined.indices.data(); a.nvi = int(refined.indices.size()); a.P = refined.P.data(); a.npi = int(refined.P.size());
+        if (!refined.uv.empty()) { a.uvs = refined.uv.data(); a.nuvi = int(refined.uv.size()); }
+        if (!refined.N.empty()) { a.N = refined.N.data(); a.nni = int(refined.N.size()); }
+        triangleMesh(a, ps);
+        return;
+    }
     if (n != "trianglemesh") {
-        Error("Unable to load plugin \"%s\" (shape): \"trianglemesh\" and the quadrics are on the accelerated path (SURVEY.md rows 12-13)", n.c_str());
+        Error("Unable to load plugin \"%s\" (shape): \"trianglemesh\", the quadrics and the refined shapes are on the accelerated path (SURVEY.md rows 12-13)", n.c_str());
         return;
     }
     // CreateShape shapes/trianglemesh.cpp:350-406
-    int nvi = 0, npi = 0, nuvi = 0;
-    const int *vi = ps.FindInt("indices", &nvi);
-    const Float3 *P = ps.FindPoint("P", &npi);
-    const float *uvs = ps.FindFloat("uv", &nuvi); if (!uvs) uvs = ps.FindFloat("st", &nuvi);
-    if (!vi || !P) return;
+    MeshArrays a;
+    a.vi = ps.FindInt("indices", &a.nvi);
+    a.P = ps.FindPoint("P", &a.npi);
+    a.uvs = ps.FindFloat("uv", &a.nuvi); if (!a.uvs) a.uvs = ps.FindFloat("st", &a.nuvi);
+    if (!a.vi || !a.P) return;
+    a.S = ps.FindVector("S", &a.nsi);
+    a.N = ps.FindNormal("N", &a.nni);
+    triangleMesh(a, ps);
+}
+
+// The one mesh factory: CreateShape's checks (shapes/trianglemesh.cpp:357-393) and the TriangleMesh constructor, for a "trianglemesh" statement and for
+// the mesh a refined shape hands to MakeShape("trianglemesh").  `ps` is the STATEMENT's parameters: they are reported unused once, here, and come
+// before the Material's in makeMaterial (api.cpp:361, :368-375).
+void PbrtApi::triangleMesh(const MeshArrays &a, const ParamSet &ps) {
+    const int *vi = a.vi; const Float3 *P = a.P; const float *uvs = a.uvs; const Float3 *S = a.S, *N = a.N;
+    const int nvi = a.nvi, npi = a.npi, nuvi = a.nuvi, nsi = a.nsi, nni = a.nni;
     // the factory's checks, in its order (trianglemesh.cpp:357-393)
     if (uvs) {
         if (nuvi < 2 * npi) { Error("Not enough of \"uv\"s for triangle mesh.  Expencted %d, found %d.  Discarding.\n", 2 * npi, nuvi); uvs = nullptr; }
         else if (nuvi > 2 * npi) Warning("More \"uv\"s provided than will be used for triangle mesh.  (%d expcted, %d found)\n", 2 * npi, nuvi);
     }
-    int nni = 0, nsi = 0;
-    const Float3 *S = ps.FindVector("S", &nsi);
     if (S && nsi != npi) { Error("Number of \"S\"s for triangle mesh must match \"P\"s"); S = nullptr; }
-    const Float3 *N = ps.FindNormal("N", &nni);
     if (N && nni != npi) { Error("Number of \"N\"s for triangle mesh must match \"P\"s"); N = nullptr; }
     for (int i = 0; i < nvi && (uvs && N); ++i)
         if (vi[i] >= npi || vi[i] < 0) { Error("trianglemesh has out of-bounds vertex index %d (%d \"P\" values were given", vi[i], npi); return; }

@@ -7,8 +7,8 @@
 //   * the Make* plugin factories of core/dynload.cpp:112-260 for the plugins on the hot path
 //     (SURVEY.md section 8a): filters box/gaussian/mitchell/sinc/triangle, film "image", camera
 //     "perspective", samplers stratified/lowdiscrepancy/random, surface integrators
-//     whitted/directlighting/path/bidirectional/debug, volume integrators emission/single, accelerators kdtree/grid, shape
-//     "trianglemesh", materials matte/glass/mirror, lights point + area, volumes "homogeneous", "exponential", "volumegrid";
+//     whitted/directlighting/path/bidirectional/debug, volume integrators emission/single, accelerators kdtree/grid, shapes
+//     "trianglemesh", the quadrics and -- refined into a trianglemesh, shape_refine.h -- heightfield/nurbs/loopsubdiv, materials matte/glass/mirror, lights point + area, volumes "homogeneous", "exponential", "volumegrid";
 //     each takes the same parameters with the same defaults as the reference factory it replaces.
 //   * RenderOptions::MakeScene (core/api.cpp:484-529): instead of building C++ objects it flattens.
 // Plugins the reference has but this path does not accelerate produce the reference's own
@@ -139,6 +139,10 @@ class PbrtApi : public DirectiveSink {
     bool verifyOptions(const char *fn); bool verifyWorld(const char *fn);
     int makeMaterial(const ParamSet &shapeParams);
     void quadricShape(const std::string &name, const ParamSet &ps);
+    // what a "trianglemesh" is made of: indices, object-space P and the optional per-vertex uv / N / S, each with its count
+    struct MeshArrays { const int *vi = nullptr; const Float3 *P = nullptr; const float *uvs = nullptr; const Float3 *N = nullptr, *S = nullptr;
+                        int nvi = 0, npi = 0, nuvi = 0, nni = 0, nsi = 0; };
+    void triangleMesh(const MeshArrays &a, const ParamSet &ps);      // Shape "trianglemesh" and the mesh of a refined heightfield / nurbs / loopsubdiv
     // TextureParams::GetSpectrumTexture / GetFloatTexture (paramset.cpp:434-465): the value, and in *node the texture node that replaces it per hit (-1: a constant)
     Float3 spectrumParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, Float3 d, int *node = nullptr);
     float floatParam(const ParamSet &geom, const ParamSet &mat, const std::string &n, float d, int *node = nullptr);

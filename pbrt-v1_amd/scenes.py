@@ -206,6 +206,82 @@ def smooth_mesh_text(radius=80.0, nu=10, nv=6, with_n=True, with_uv=True, with_s
     return out + "\n"
 
 
+# ---- the shapes the host refines into a trianglemesh (csrc/host/shape_refine.h): control meshes as (P [n, 3], faces [m, 3]) and their statements
+def _f32(vals) -> str:
+    return _fmt(np.asarray(vals, np.float32).ravel())
+
+
+def heightfield_text(nu: int, nv: int, z, extra: str = "") -> str:
+    return 'Shape "heightfield" "integer nu" [%d] "integer nv" [%d] "float Pz" [%s]%s\n' % (nu, nv, _f32(z), (" " + extra) if extra else "")
+
+
+def loopsubdiv_text(P, faces, nlevels=None, extra: str = "") -> str:
+    lv = "" if nlevels is None else ' "integer nlevels" [%d]' % nlevels
+    return 'Shape "loopsubdiv"%s "integer indices" [%s] "point P" [%s]%s\n' % (
+        lv, " ".join(str(int(i)) for i in np.asarray(faces).ravel()), _f32(P), (" " + extra) if extra else "")
+
+
+def control_mesh_text(P, faces, extra: str = "") -> str:
+    """The control mesh itself as a plain trianglemesh: what a loopsubdiv statement must NOT render as."""
+    return 'Shape "trianglemesh" "integer indices" [%s] "point P" [%s]%s\n' % (
+        " ".join(str(int(i)) for i in np.asarray(faces).ravel()), _f32(P), (" " + extra) if extra else "")
+
+
+def nurbs_text(nu, uorder, uknots, nv, vorder, vknots, P=None, Pw=None, u0=None, u1=None, v0=None, v1=None, extra: str = "") -> str:
+    out = ('Shape "nurbs" "integer nu" [%d] "integer uorder" [%d] "float uknots" [%s] "integer nv" [%d] "integer vorder" [%d] "float vknots" [%s]'
+           % (nu, uorder, _f32(uknots), nv, vorder, _f32(vknots)))
+    for name, val in (("u0", u0), ("u1", u1), ("v0", v0), ("v1", v1)):
+        if val is not None:
+            out += ' "float %s" [%s]' % (name, _f32([val]))
+    if P is not None: out += ' "point P" [%s]' % _f32(P)
+    if Pw is not None: out += ' "float Pw" [%s]' % _f32(Pw)
+    return out + ((" " + extra) if extra else "") + "\n"
+
+
+def octahedron(radius=1.0):
+    P = radius * np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0], [-1, 0, 0], [0, -1, 0], [0, 0, -1]], np.float64)
+    F = np.array([[0, 1, 2], [0, 2, 3], [0, 3, 4], [0, 4, 1], [5, 2, 1], [5, 3, 2], [5, 4, 3], [5, 1, 4]])
+    return P, F
+
+
+def tetrahedron(radius=1.0):
+    """Faces in an order in which no vertex's last face is its first."""
+    P = radius * np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], np.float64) / np.sqrt(3.0)
+    F = np.array([[1, 3, 2], [0, 1, 2], [0, 2, 3], [0, 3, 1]])
+    return P, F
+
+
+def grid_mesh(nx=3, ny=3, size=1.0, height=None):
+    """nx x ny vertices over [0, size]^2, two triangles per cell; height(x, y) lifts z."""
+    P = np.array([[size * x / (nx - 1), size * y / (ny - 1), 0.0] for y in range(ny) for x in range(nx)], np.float64)
+    if height is not None:
+        P[:, 2] = [height(p[0], p[1]) for p in P]
+    F = []
+    for y in range(ny - 1):
+        for x in range(nx - 1):
+            a = x + y * nx
+            F += [[a, a + 1, a + 1 + nx], [a, a + 1 + nx, a + nx]]
+    return P, np.array(F)
+
+
+def fan_mesh(n=5, radius=1.0, sweep=np.pi, lift=0.0, closed=False):
+    """n triangles around vertex 0: an open fan over `sweep` (vertex 0 is a boundary vertex of valence n + 1), or, closed, an umbrella
+    (vertex 0 is an interior vertex of valence n, the rim vertices boundary vertices of valence 3); `lift` raises the hub."""
+    rim = n if closed else n + 1
+    ang = [2 * np.pi * i / n if closed else sweep * i / n for i in range(rim)]
+    P = np.array([[0, 0, lift]] + [[radius * np.cos(a), radius * np.sin(a), 0.0] for a in ang], np.float64)
+    F = np.array([[0, 1 + i, 1 + (i + 1) % rim] for i in range(n)])
+    return P, F
+
+
+def icosphere_mesh(radius=1.0, subdiv=1):
+    """icosphere() with shared vertices: (P, faces), 20 * 4^subdiv faces."""
+    tris = icosphere((0, 0, 0), radius, subdiv).astype(np.float64)
+    key = np.round(tris.reshape(-1, 3) / radius, 5)
+    _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    return tris.reshape(-1, 3)[first], np.asarray(inv).reshape(-1, 3)
+
+
 def options_block(xres=512, yres=512, integrator="whitted", integrator_params="", maxdepth=5,
                   sampler="stratified", xsamples=1, ysamples=1, jitter=False, pixelsamples=None,
                   pixel_filter="box", filter_params="", accelerator="kdtree", accel_params="",
