@@ -292,6 +292,13 @@ int rt_scene_create_prebuilt(const RtSceneDesc *desc, int device, const RtPrebui
  * nx*ny*nz >= 2^31, null grid), RT_ESTATE (called twice, or after rt_render), RT_EDEVICE (upload failed);
  * rt_last_error() says which. */
 int rt_scene_set_density(RtScene *s, const RtDensityRegion *region);
+/* The spot lights' LightToWorld (upper-left 3x3, row-major), 9 floats per light of the scene in the order of RtSceneDesc::lights; entries of other
+ * lights are not read.  The bidirectional integrator starts its light path with SpotLight::Sample_L(scene, ...) (spot.cpp:87-95), which multiplies
+ * by this matrix -- the product CreateLight formed, not the inverse of WorldToLight: the two differ in their last bits, and with them hit / miss and
+ * black / not black decisions further down the path.  Optional: without it the device inverts RtLight::world_to_light.  Call once, after
+ * rt_scene_create and before the first rt_render.  RT_EINVAL (null argument, n_lights differs from the scene's, an entry not finite), RT_ESTATE
+ * (after rt_render), RT_EDEVICE. */
+int rt_scene_set_light_transforms(RtScene *s, const float *light_to_world, uint32_t n_lights);
 /* Textured material parameters (include/pbrt_hip_texture.h has the records, the limits and the evaluation): what MakeMaterial keeps when
  * TextureParams::GetSpectrumTexture / GetFloatTexture (core/paramset.cpp:434-465) return something other than a ConstantTexture.  Call once,
  * after rt_scene_create or rt_scene_create_prebuilt and before the first rt_render.  `nodes` is a flat table of n_nodes texture nodes whose

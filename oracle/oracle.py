@@ -2,6 +2,7 @@
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg -- never by the product package."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -9,15 +10,17 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(_HERE, "_build", "libpbrt_oracle.so")
-_lib = None
+LIB_PLM = os.path.join(_HERE, "_build", "libpbrt_oracle_plm.so")      # the same source with -DORACLE_PORTABLE_LIBM (rt_libm_portable.h)
+_libs = {}
+_current = LIB
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB):
+    """The restatement's library: the glibc build, or inside `with portable_libm():` the build whose libm calls are the portable functions."""
+    if _current not in _libs:
+        if not os.path.exists(_current):
             subprocess.check_call(["make", "-s", "-C", _HERE])
-        L = C.CDLL(LIB)
+        L = C.CDLL(_current)
         L.oracle_render.restype = C.c_int
         L.oracle_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_trace.restype = C.c_int
@@ -27,8 +30,19 @@ def lib():
         L.oracle_set_mailbox.argtypes = [C.c_int]
         L.oracle_resolve.restype = None
         L.oracle_resolve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = L
-    return _lib
+        _libs[_current] = L
+    return _libs[_current]
+
+
+@contextlib.contextmanager
+def portable_libm():
+    """Within the block every call of this module goes to libpbrt_oracle_plm.so (its own globals: set_mailbox applies to the library in use)."""
+    global _current
+    prev, _current = _current, LIB_PLM
+    try:
+        yield
+    finally:
+        _current = prev
 
 
 def set_mailbox(mode: int):

@@ -27,7 +27,13 @@ static inline uint32_t pcg(uint32_t v) {
 static uint32_t g_base = 0, g_ctr = 0, g_seed = 0;
 unsigned long long g_keyed_draws = 0;
 void keyed_rng_set_seed(uint32_t seed) { g_seed = seed; }
-void keyed_rng_set_key(uint32_t key) { g_base = pcg(key + g_seed * 0x9E3779B9u); g_ctr = 0; }
+// portable_libm.cpp, linked into pbrt_ref_keyed_plm only: the first key of a camera sample (the first GetNextSample, the start of
+// Scene::Render's loop) ends set-up, and the render phase runs under the portable libm functions
+void plm_enable(int) __attribute__((weak));
+void keyed_rng_set_key(uint32_t key) {
+    if (key != 0xFFFFFFFFu && plm_enable) plm_enable(1);
+    g_base = pcg(key + g_seed * 0x9E3779B9u); g_ctr = 0;
+}
 uint32_t keyed_rng_counter() { return g_ctr; }
 }
 static struct KeyedInit { KeyedInit() { keyed_rng_set_key(0xFFFFFFFFu); } } g_keyedInit;

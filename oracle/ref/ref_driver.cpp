@@ -38,6 +38,8 @@ double g_ref_times[4] = {0, 0, 0, 0};                             // [0]=accel b
 double ref_now() { timeval tv; gettimeofday(&tv, NULL); return tv.tv_sec + 1e-6 * tv.tv_usec; }
 const void *g_keyed_inner_sampler = NULL;                         // set by keyed_sampler.cpp, read by hip_adapter.cpp
 unsigned g_keyed_seed = 0;
+// portable_libm.cpp (pbrt_ref_keyed_plm only): calls of sinf cosf sincosf acosf atan2f powf expf since plm_enable(1)
+const unsigned long long *plm_call_counts() __attribute__((weak));
 }
 
 static string g_outPath;
@@ -337,8 +339,14 @@ int main(int argc, char **argv) {
     if (quiet) { fflush(stdout); dup2(savedOut, 1); close(savedOut); }
     double render_s = (g_ref_times[1] > 0 && g_ref_times[2] > 0) ? g_ref_times[2] - g_ref_times[1] : -1.;
     printf("{\"ok\": %s, \"total_s\": %.6f, \"accel_build_s\": %.6f, \"render_s\": %.6f, "
-           "\"closest_rays\": %llu, \"any_rays\": %llu, \"closest_hits\": %llu, \"any_hits\": %llu}\n",
+           "\"closest_rays\": %llu, \"any_rays\": %llu, \"closest_hits\": %llu, \"any_hits\": %llu",
            ok ? "true" : "false", t1 - t0, g_ref_times[0], render_s,
            g_ref_counters[0], g_ref_counters[1], g_ref_counters[2], g_ref_counters[3]);
+    if (plm_call_counts) {
+        const unsigned long long *c = plm_call_counts();
+        printf(", \"libm_calls\": {\"sinf\": %llu, \"cosf\": %llu, \"sincosf\": %llu, \"acosf\": %llu, \"atan2f\": %llu, \"powf\": %llu, \"expf\": %llu}",
+               c[0], c[1], c[2], c[3], c[4], c[5], c[6]);
+    }
+    printf("}\n");
     return ok ? 0 : 1;
 }

@@ -25,12 +25,16 @@ def load_ref_film(path: str):
 REF_DIR = os.path.join(_HERE, "_ref")
 
 
-def run_reference(scene_text: str, keyed: bool = True, workdir: str | None = None, timeout: float = 3600, env: dict | None = None):
+def run_reference(scene_text: str, keyed: bool = True, workdir: str | None = None, timeout: float = 3600, env: dict | None = None, libm: str = "glibc"):
     """Run the compiled reference (oracle/_ref) on a scene; returns (rgb, alpha, stats dict).
+    libm="portable": the keyed binary whose render phase (from the first camera sample on) runs under the portable libm functions
+    (oracle/ref/portable_libm.cpp); stats["libm_calls"] then holds the calls per function since that moment.
     TEST/BENCH infrastructure only -- never on the product path."""
     import json
     import tempfile
-    exe = os.path.join(REF_DIR, "pbrt_ref_keyed" if keyed else "pbrt_ref")
+    if libm not in ("glibc", "portable") or (libm == "portable" and not keyed):
+        raise ValueError("libm is 'glibc' or 'portable', and the portable binary is a keyed one")
+    exe = os.path.join(REF_DIR, "pbrt_ref_keyed_plm" if libm == "portable" else "pbrt_ref_keyed" if keyed else "pbrt_ref")
     if not os.path.exists(exe):
         raise FileNotFoundError(exe)
     d = workdir or tempfile.mkdtemp(prefix="pbrtref_")

@@ -37,6 +37,34 @@ HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "r
              "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
+def _include_closure(path, seen=None):
+    """the files `path` includes with #include "..." (transitively): a unit is rebuilt only when one of ITS headers changed"""
+    import re
+    seen = set() if seen is None else seen
+    if path in seen or not os.path.exists(path):
+        return seen
+    seen.add(path)
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+        _include_closure(os.path.normpath(os.path.join(os.path.dirname(path), inc)), seen)
+    return seen
+
+
+def _compile_unit(cmd, verbose=False):
+    """one hipcc -c command (source at cmd[-3], object at cmd[-1]).  A .hip unit keeps the compiler's per-kernel resource report (VGPRs,
+    spills, occupancy) next to the object: tests/test_abi.py checks that the timed kernels stay inside their occupancy step (gfx950:
+    <= 168 VGPRs for 3 waves per SIMD, <= 64 for 8)"""
+    if verbose:
+        print(" ".join(cmd))
+    if not cmd[-3].endswith(".hip"):
+        subprocess.check_call(cmd)
+        return
+    r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    keep = [ln for ln in r.stderr.splitlines() if "remark:" in ln and any(k in ln for k in ("Function Name", " VGPRs:", "VGPRs Spill", "Occupancy", "ScratchSize", "LDS Size"))]
+    open(cmd[-1][:-2] + ".resources.txt", "w").write("\n".join(keep) + "\n")
+    if r.returncode != 0:
+        raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
+
+
 def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | None = None) -> None:
     """Compile both shared libraries in-tree (hipcc cross-compiles gfx950 without a GPU).  The HIP library is ten translation
     units (the megakernel and the pipeline's shade kernel per integrator, the trace kernel, the C ABI, the two host builders)
@@ -55,17 +83,6 @@ def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | No
     def stale(out, deps):
         return force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
 
-    def closure(path, seen=None):
-        """the files `path` includes with #include "..." (transitively): a unit is rebuilt only when one of ITS headers changed"""
-        import re
-        seen = set() if seen is None else seen
-        if path in seen or not os.path.exists(path):
-            return seen
-        seen.add(path)
-        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
-            closure(os.path.normpath(os.path.join(os.path.dirname(path), inc)), seen)
-        return seen
-
     stamp = os.path.join(obj_dir, "defines.txt")
     # the stamp holds the compiler flags too: an object built with other flags (e.g. before -fno-slp-vectorize, a correctness fix) must
     # not survive an incremental build just because it is newer than its sources
@@ -75,22 +92,10 @@ def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | No
     todo = []
     for u in HIP_UNITS:
         obj = os.path.join(obj_dir, u.rsplit(".", 1)[0] + ".o")
-        if stale(obj, sorted(closure(os.path.join(hip_dir, u)))):
+        if stale(obj, sorted(_include_closure(os.path.join(hip_dir, u)))):
             todo.append(["hipcc"] + [f for f in HIPCC_FLAGS if f != "-shared"] + list(defines) + ["-c", os.path.join(hip_dir, u), "-o", obj])
     if todo:
-        def run(cmd):
-            if verbose:
-                print(" ".join(cmd))
-            if not cmd[-3].endswith(".hip"):
-                subprocess.check_call(cmd)
-                return
-            # keep the compiler's per-kernel resource report (VGPRs, spills, occupancy) next to the object: tests/test_abi.py checks
-            # that the timed kernels stay inside their occupancy step (gfx950: <= 168 VGPRs for 3 waves per SIMD, <= 64 for 8)
-            r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-            keep = [ln for ln in r.stderr.splitlines() if "remark:" in ln and any(k in ln for k in ("Function Name", " VGPRs:", "VGPRs Spill", "Occupancy", "ScratchSize", "LDS Size"))]
-            open(cmd[-1][:-2] + ".resources.txt", "w").write("\n".join(keep) + "\n")
-            if r.returncode != 0:
-                raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
+        run = lambda cmd: _compile_unit(cmd, verbose)
         with ThreadPoolExecutor(max_workers=jobs or min(len(todo), os.cpu_count() or 4)) as ex:
             list(ex.map(run, todo))
         open(stamp, "w").write(dtext)
@@ -105,6 +110,50 @@ def build(force: bool = False, verbose: bool = False, defines=(), jobs: int | No
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+
+
+def build_variant(name: str, defines=(), units=None, arch: str | None = None, verbose: bool = False) -> str:
+    """A variant of libpbrt_hip.so next to the product library (tools/build_variant.py is its command line): the translation units `units`
+    (default: all) compiled with the extra `defines` into lib/obj_NAME/, the others taken from the product build, linked as
+    lib/libpbrt_hip_NAME.so.  Like build(): a stamp of flags and defines forces a rebuild when they change, otherwise a unit is compiled again
+    only when a file of its include closure is newer than its object.  A process picks the variant with PBRT_HIP_LIB_PATH (read only when
+    PBRT_HIP_TUNE is set).  Returns the library's path."""
+    from concurrent.futures import ThreadPoolExecutor
+    units = list(HIP_UNITS if units is None else units)
+    if len(units) < len(HIP_UNITS):
+        build()                                                  # the product objects the variant borrows
+    obj_dir = os.path.join(LIB_DIR, "obj_" + name)
+    os.makedirs(obj_dir, exist_ok=True)
+    hip_dir = os.path.join(CSRC, "hip")
+    flags = [f for f in HIPCC_FLAGS if f != "-shared"]
+    if arch:
+        flags = ["--offload-arch=" + arch if f.startswith("--offload-arch=") else f for f in flags]
+    out = os.path.join(LIB_DIR, "libpbrt_hip_%s.so" % name)
+    stamp = os.path.join(obj_dir, "defines.txt")
+    dtext = " ".join(flags) + " | " + " ".join(defines) + " | " + " ".join(units)
+    lib_ok = os.path.exists(out) and (open(stamp).read() if os.path.exists(stamp) else "") == dtext
+    obj_of = lambda d, u: os.path.join(d, u.rsplit(".", 1)[0] + ".o")
+
+    def stale(u):
+        # a tree that arrives with the linked library but without its objects is judged by the library's time: nothing is stale there
+        obj = obj_of(obj_dir, u)
+        if not lib_ok:
+            return True
+        t = os.path.getmtime(obj if os.path.exists(obj) else out)
+        return any(os.path.getmtime(d) > t for d in _include_closure(os.path.join(hip_dir, u)))
+    todo = [u for u in units if stale(u)]
+    borrowed = [obj_of(os.path.join(LIB_DIR, "obj"), u) for u in HIP_UNITS if u not in units]
+    if not todo and lib_ok and not any(os.path.getmtime(o) > os.path.getmtime(out) for o in borrowed):
+        return out
+    todo += [u for u in units if u not in todo and not os.path.exists(obj_of(obj_dir, u))]       # the link needs every object
+    cmds = [["hipcc"] + flags + list(defines) + ["-c", os.path.join(hip_dir, u), "-o", obj_of(obj_dir, u)] for u in todo]
+    if cmds:
+        with ThreadPoolExecutor(max_workers=min(len(cmds), os.cpu_count() or 4)) as ex:
+            list(ex.map(lambda cmd: _compile_unit(cmd, verbose), cmds))
+    objs = [obj_of(obj_dir if u in units else os.path.join(LIB_DIR, "obj"), u) for u in HIP_UNITS]
+    subprocess.check_call(["hipcc", "--offload-arch=" + (arch or "gfx950"), "-shared", "-fPIC"] + objs + ["-o", out])
+    open(stamp, "w").write(dtext)
+    return out
 
 
 # --------------------------------------------------------------------------- C ABI structs
@@ -260,10 +309,11 @@ def hip_lib():
                      "rt_counters_reset", "rt_last_render_ms", "rt_last_render_stats", "rt_samples_read", "rt_device_count", "rt_set_counting",
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
-                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures"):
+                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
+        L.rt_scene_set_light_transforms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rt_scene_set_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rt_scene_create_prebuilt.argtypes = [C.c_void_p, C.c_int, C.POINTER(RtPrebuiltAccel), C.POINTER(C.c_void_p)]
         L.rt_scene_destroy.argtypes = [C.c_void_p]
@@ -341,6 +391,8 @@ def host_lib():
         L.pbrt_host_accel_params.argtypes = [C.c_void_p]
         L.pbrt_host_volume.restype = C.POINTER(RtVolume)
         L.pbrt_host_volume.argtypes = [C.c_void_p]
+        L.pbrt_host_light_to_world.restype = C.c_void_p
+        L.pbrt_host_light_to_world.argtypes = [C.c_void_p, C.c_int]
         L.pbrt_host_density_desc.restype = C.POINTER(RtDensityRegion)
         L.pbrt_host_density_desc.argtypes = [C.c_void_p, C.c_int]
         L.pbrt_host_materials.restype = C.POINTER(RtMaterial)
@@ -815,6 +867,13 @@ class DeviceScene:
             for i in range(3):
                 pa.grid_nvoxels[i] = info.grid_nvoxels[i]; pa.grid_width[i] = info.grid_width[i]; pa.grid_inv_width[i] = info.grid_inv_width[i]
             _chk(hip_lib().rt_scene_create_prebuilt(parsed.scene_desc, device, C.byref(pa), C.byref(self._s)))
+        l2w = host_lib().pbrt_host_light_to_world(parsed._h, parsed.frame)
+        if l2w:                                   # spot lights: LightToWorld as the reference holds it (the bidirectional integrator's emission rays)
+            rc = hip_lib().rt_scene_set_light_transforms(self._s, l2w, parsed.n_lights)
+            if rc != 0:
+                err = hip_lib().rt_last_error().decode(errors="replace")
+                hip_lib().rt_scene_destroy(self._s); self._s = C.c_void_p()
+                raise RtError("rt_scene_set_light_transforms failed (%d): %s" % (rc, err))
         dens = parsed.density_desc()
         if dens:                                  # an exponential / volumegrid medium: DensityRegion on top of the scene's RtVolume
             rc = hip_lib().rt_scene_set_density(self._s, dens)

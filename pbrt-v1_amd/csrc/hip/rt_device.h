@@ -50,6 +50,9 @@ struct DevLight {
     int quadric;       // area light on a quadric: index into DevScene::quadrics, else -1 (read by the EXT kernels)
     float w2l[9];      // spot: WorldToLight 3x3
     float cos_total, cos_falloff;
+    // spot: LightToWorld 3x3 times v = (l2w v) * l2w_scale.  rt_scene_set_light_transforms stores the reference's own matrix (scale 1); without it
+    // rt_scene_create stores the cofactors of w2l and 1 / det: the inverse of WorldToLight, a few ulps from the matrix the reference multiplies by
+    float l2w[9], l2w_scale;
     // RT_LIGHT_INFINITE (infinite.cpp, constant radiance): color = L, n_samples; nothing else is read
 };
 

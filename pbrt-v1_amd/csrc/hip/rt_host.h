@@ -127,6 +127,7 @@ struct RtScene {
     // textured materials (rt_scene_set_textures): the scene's own resolved records (host copy) and the device array that holds them followed by
     // the records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
     std::vector<DevMaterial> materials_host;
+    std::vector<DevLight> lights_host;
     std::vector<int> tex_uv_idx_host; std::vector<float> tex_uv_host;   // uvs of the triangles whose mesh has "uv" ([n_tris] index or -1, 6 floats each): host only until upload_tex_uv
     bool has_textures = false;
     DevBuf<DevMaterial> mat_buf;

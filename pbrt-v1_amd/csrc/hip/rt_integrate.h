@@ -198,7 +198,7 @@ RT_DEV Ray camera_ray(const RtCamera &cam, float ix, float iy, float lensU, floa
         r.o = xform_point(cam.camera_to_world, mk3(0.f, 0.f, 0.f));               // rayOrigin = CameraToWorld(Point(0,0,0))
         const float theta = RT_PI * iy / cam.y_res;                               // M_PI is a float (pbrt.h:204); int -> float promotion
         const float phi = 2 * RT_PI * ix / cam.x_res;
-        const V3 dir = mk3(sinf(theta) * cosf(phi), cosf(theta), sinf(theta) * sinf(phi));
+        const V3 dir = mk3(rt_sinf(theta) * rt_cosf(phi), rt_cosf(theta), rt_sinf(theta) * rt_sinf(phi));
         r.d = xform_vector(cam.camera_to_world, dir);
         r.mint = cam.hither; r.maxt = cam.yon;
         return r;
@@ -414,7 +414,7 @@ RT_DEV V3 vol_transmittance(const RtVolume &v, V3 o, V3 d, float mint, float max
     if (!vol_intersect(v, o, d, mint, maxt, t0, t1)) return mk3(1.f);
     const float dist = len3((o + d * t0) - (o + d * t1));
     const V3 tau = (mat_color(v.sigma_a) + mat_color(v.sigma_s)) * dist;
-    return mk3(expf(-tau.x), expf(-tau.y), expf(-tau.z));
+    return mk3(rt_expf(-tau.x), rt_expf(-tau.y), rt_expf(-tau.z));
 }
 // ---- density media: DensityRegion (core/volume.h:62-90) with ExponentialDensity or VolumeGrid (DevScene::dens_kind, set by rt_scene_set_density).
 // Only the EXT kernels carry this code; the medium's kind is uniform over the frame, so every branch on it is wave-uniform.
@@ -427,7 +427,7 @@ RT_DEV float density_at(const DevScene &sc, V3 q) {
     if (!(q.x >= v.p0[0] && q.x <= v.p1[0] && q.y >= v.p0[1] && q.y <= v.p1[1] && q.z >= v.p0[2] && q.z <= v.p1[2])) return 0.f;   // extent.Inside
     if (sc.dens_kind == RT_DENSITY_EXPONENTIAL) {
         const float height = (q.x - v.p0[0]) * sc.dens_up[0] + (q.y - v.p0[1]) * sc.dens_up[1] + (q.z - v.p0[2]) * sc.dens_up[2];
-        return sc.dens_a * expf(-sc.dens_b * height);
+        return sc.dens_a * rt_expf(-sc.dens_b * height);
     }
     const int nx = sc.dens_n[0], ny = sc.dens_n[1], nz = sc.dens_n[2];
     const float voxx = (q.x - v.p0[0]) / (v.p1[0] - v.p0[0]) * float(nx) - .5f;
@@ -470,7 +470,7 @@ RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float 
     }
     return tau * step;
 }
-RT_DEV V3 exp_neg(V3 tau) { return mk3(expf(-tau.x), expf(-tau.y), expf(-tau.z)); }       // Exp(-tau)
+RT_DEV V3 exp_neg(V3 tau) { return mk3(rt_expf(-tau.x), rt_expf(-tau.y), rt_expf(-tau.z)); }       // Exp(-tau)
 
 // Scene::Transmittance(ray) (scene.cpp:127-129): sample == NULL => one RandomFloat() for the offset, which a homogeneous medium ignores
 // and a density region marches with at 4.f * stepSize (emission.cpp:47-59, single.cpp:48-56)
@@ -665,7 +665,7 @@ RT_DEV bool march_steps(const DevScene &sc, const DevFrame &fr, Lane &ln, const 
                 }
                 if (!is_black(L) && pdf > 0.f) {
                     const float costheta = dot3(w, -wo);                       // PhaseHG volume.cpp:44-48
-                    const float phase = in ? 1.f / (4.f * RT_PI) * (1.f - vol.g * vol.g) / powf(1.f + vol.g * vol.g - 2.f * vol.g * costheta, 1.5f) : 0.f;
+                    const float phase = in ? 1.f / (4.f * RT_PI) * (1.f - vol.g * vol.g) / rt_powf(1.f + vol.g * vol.g - 2.f * vol.g * costheta, 1.5f) : 0.f;
                     ln.pend = div_s((((Tr * ss) * phase) * L) * float(nLights), pdf);
                     m.i = i; m.t0 = t0; m.Tr = Tr; m.p = p; m.Lv = Lv;
                     if (PREFETCH) {                                            // row i + 1 (row N - 1 again past the end: never used)

@@ -475,6 +475,12 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         for (int c = 0; c < 3; ++c) o.dir[c] = L.dir[c];
         for (int c = 0; c < 9; ++c) o.w2l[c] = L.world_to_light[c];
         o.cos_total = L.cos_total_width; o.cos_falloff = L.cos_falloff_start;
+        {   // LightToWorld until rt_scene_set_light_transforms brings the reference's own: the inverse of WorldToLight by cofactors
+            const float a = o.w2l[0], b = o.w2l[1], c = o.w2l[2], d3 = o.w2l[3], e = o.w2l[4], f = o.w2l[5], g = o.w2l[6], h = o.w2l[7], i9 = o.w2l[8];
+            const float cof[9] = {e * i9 - f * h, c * h - b * i9, b * f - c * e, f * g - d3 * i9, a * i9 - c * g, c * d3 - a * f, d3 * h - e * g, b * g - a * h, a * e - b * d3};
+            for (int k = 0; k < 9; ++k) o.l2w[k] = cof[k];
+            o.l2w_scale = L.type == RT_LIGHT_SPOT ? 1.f / (a * cof[0] + b * cof[3] + c * cof[6]) : 0.f;
+        }
         o.quadric = L.quadric_plus1 - 1;
         if (L.quadric_plus1 < 0 || uint32_t(L.quadric_plus1) > d->n_quadrics) return fail(RT_EINVAL, "rt_scene_create: light refers to a quadric out of range");
         if (L.type < RT_LIGHT_POINT || L.type > RT_LIGHT_INFINITE) return fail(RT_EINVAL, "rt_scene_create: unknown light type");
@@ -502,6 +508,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         o.area = (L.n_tris == 1) ? areas[0] : area;
     }
     if ((rc = upload(s, lights.data(), lights.size(), &s->dev.lights))) return rc;
+    s->lights_host = lights;                                                       // rt_scene_set_light_transforms rewrites the spot lights' records
     if ((rc = upload(s, ltris.data(), ltris.size(), &s->dev.light_tris))) return rc;
     {
         std::vector<unsigned> flags(d->n_lights ? d->n_lights : 1, 0u);
@@ -625,6 +632,28 @@ int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
     std::memcpy(s->vol_world, wb, sizeof wb);
     s->density_kind = r->kind;
     s->has_ext = true;                                                          // the density code exists only in the EXT kernels
+    return RT_OK;
+}
+
+// The spot lights' LightToWorld as the reference holds it (pbrt_hip.h): 9 floats per light of the scene, read for the spot lights only.
+int rt_scene_set_light_transforms(RtScene *s, const float *light_to_world, uint32_t n_lights) {
+    if (!s || !light_to_world) return fail(RT_EINVAL, "rt_scene_set_light_transforms: null argument");
+    if (s->rendered) return fail(RT_ESTATE, "rt_scene_set_light_transforms: the scene has rendered a frame already");
+    if (n_lights != s->lights_host.size()) return fail(RT_EINVAL, "rt_scene_set_light_transforms: n_lights differs from the scene's number of lights");
+    for (uint32_t i = 0; i < n_lights; ++i) {
+        if (s->lights_host[i].type != RT_LIGHT_SPOT) continue;
+        for (int k = 0; k < 9; ++k) if (!std::isfinite(light_to_world[9 * size_t(i) + k])) return fail(RT_EINVAL, "rt_scene_set_light_transforms: a matrix entry is not finite");
+    }
+    if (n_lights == 0) return RT_OK;
+    for (uint32_t i = 0; i < n_lights; ++i) {
+        DevLight &o = s->lights_host[i];
+        if (o.type != RT_LIGHT_SPOT) continue;
+        for (int k = 0; k < 9; ++k) o.l2w[k] = light_to_world[9 * size_t(i) + k];
+        o.l2w_scale = 1.f;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(const_cast<DevLight *>(s->dev.lights), s->lights_host.data(), s->lights_host.size() * sizeof(DevLight), hipMemcpyHostToDevice));
     return RT_OK;
 }
 

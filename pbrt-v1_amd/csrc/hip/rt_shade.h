@@ -64,21 +64,21 @@ RT_DEV void quadric_frame(const DevScene &sc, unsigned qi, bool flip, V3 ow, V3 
         dpdv = mk3(phit.x / (2.f * phit.z), phit.y / (2.f * phit.z), 1.f) * (q.zmax - q.zmin);
     } else if (q.type == RT_QUADRIC_HYPERBOLOID) {                              // hyperboloid.cpp:122-130
         const float phi = quadric_phi(q, phit);
-        cosphi = cosf(phi); sinphi = sinf(phi);
+        cosphi = rt_cosf(phi); sinphi = rt_sinf(phi);
         dpdu = mk3(-phiMax * phit.y, phiMax * phit.x, 0.f);
         dpdv = mk3((q.p2[0] - q.p1[0]) * cosphi - (q.p2[1] - q.p1[1]) * sinphi, (q.p2[0] - q.p1[0]) * sinphi + (q.p2[1] - q.p1[1]) * cosphi, q.p2[2] - q.p1[2]);
     } else {
-    const float theta = acosf(clampf(phit.z / radius, -1.f, 1.f));
+    const float theta = rt_acosf(clampf(phit.z / radius, -1.f, 1.f));
     const float zradius = sqrtf(phit.x * phit.x + phit.y * phit.y);
     if (zradius == 0) {
         cosphi = 0; sinphi = 1;
-        dpdv = mk3(phit.z * cosphi, phit.z * sinphi, -radius * sinf(theta)) * (thetaMax - thetaMin);
+        dpdv = mk3(phit.z * cosphi, phit.z * sinphi, -radius * rt_sinf(theta)) * (thetaMax - thetaMin);
         dpdu = cross3(dpdv, phit);
     } else {
         const float invzradius = 1.f / zradius;
         cosphi = phit.x * invzradius; sinphi = phit.y * invzradius;
         dpdu = mk3(-phiMax * phit.y, phiMax * phit.x, 0.f);
-        dpdv = mk3(phit.z * cosphi, phit.z * sinphi, -radius * sinf(theta)) * (thetaMax - thetaMin);
+        dpdv = mk3(phit.z * cosphi, phit.z * sinphi, -radius * rt_sinf(theta)) * (thetaMax - thetaMin);
     }
     }
     vp = xform_point(q.o2w, phit);
@@ -246,8 +246,8 @@ RT_DEV void concentric_disk(float u1, float u2, float &dx, float &dy) {
         else { r = -sy; theta = 6.0f + sx / r; }
     }
     theta *= RT_PI / 4.f;
-    dx = r * cosf(theta);
-    dy = r * sinf(theta);
+    dx = r * rt_cosf(theta);
+    dy = r * rt_sinf(theta);
 }
 
 // Microfacet::f reflection.cpp:163-175 with Blinn::D (reflection.h:315-320), Microfacet::G (:293-301) and
@@ -272,7 +272,7 @@ RT_DEV V3 microfacet_lobe(V3 R, V3 eta, float exponent, V3 wo, V3 wi) {
     wh = normalize3(wh);
     const float cosThetaH = dot3(wi, wh);
     const V3 F = COND ? fr_cond(fabsf(cosThetaH), eta) : mk3(fresnel_dielectric(cosThetaH, 1.5f, 1.f));
-    const float D = (exponent + 2) * RT_INV_TWOPI * powf(fabsf(wh.z), exponent);
+    const float D = (exponent + 2) * RT_INV_TWOPI * rt_powf(fabsf(wh.z), exponent);
     const float NdotWh = fabsf(wh.z), NdotWo = fabsf(wo.z), NdotWi = fabsf(wi.z), WOdotWh = absdot3(wo, wh);
     const float G = min_std(1.f, min_std((2.f * NdotWh * NdotWo / WOdotWh), (2.f * NdotWh * NdotWi / WOdotWh)));
     return div_s(((R * D) * G) * F, 4.f * cosThetaI * cosThetaO);
@@ -291,7 +291,7 @@ RT_DEV V3 microfacet_t_f(MatRef m, V3 wo, V3 wi) { return microfacet_lobe<false>
 RT_DEV float blinn_pdf(float exponent, V3 wo, V3 wi) {
     const V3 H = normalize3(wo + wi);
     const float costheta = fabsf(H.z);
-    float p = ((exponent + 1.f) * powf(costheta, exponent)) / (2.f * RT_PI * 4.f * dot3(wo, H));
+    float p = ((exponent + 1.f) * rt_powf(costheta, exponent)) / (2.f * RT_PI * 4.f * dot3(wo, H));
     if (dot3(wo, H) <= 0.f) p = 0.f;
     return p;
 }
@@ -430,13 +430,13 @@ RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, fl
             if (glossy_t_has) pdf += glossy_t_pdf(m, wo, wi);
         } else {
             // Microfacet::Sample_f reflection.cpp:235-240 with Blinn::Sample_f :246-262
-            const float costheta = powf(u1, 1.f / (m.exponent + 1));
+            const float costheta = rt_powf(u1, 1.f / (m.exponent + 1));
             const float sintheta = sqrtf(fmaxf(0.f, 1.f - costheta * costheta));
             const float phi = u2 * 2.f * RT_PI;
-            V3 H = mk3(sintheta * cosf(phi), sintheta * sinf(phi), costheta);
+            V3 H = mk3(sintheta * rt_cosf(phi), sintheta * rt_sinf(phi), costheta);
             if (!(wo.z * H.z > 0.f)) H = -H;
             wi = -wo + H * (2.f * dot3(wo, H));
-            pdf = ((m.exponent + 1.f) * powf(costheta, m.exponent)) / (2.f * RT_PI * 4.f * dot3(wo, H));
+            pdf = ((m.exponent + 1.f) * rt_powf(costheta, m.exponent)) / (2.f * RT_PI * 4.f * dot3(wo, H));
             if (dot3(wo, H) <= 0.f) pdf = 0.f;
             if (pdf == 0.f) return mk3(0.f);
             sampled = through ? (BX_TRANSMISSION | BX_GLOSSY) : (BX_REFLECTION | BX_GLOSSY);
@@ -553,7 +553,7 @@ RT_DEV V3 infinite_sample_sphere(float u1, float u2, float &pdf) {
     const float r = sqrtf(fmaxf(0.f, 1.f - z * z));
     const float phi = 2.f * RT_PI * u2;
     pdf = 1.f / (4.f * RT_PI);
-    return mk3(r * cosf(phi), r * sinf(phi), z);
+    return mk3(r * rt_cosf(phi), r * rt_sinf(phi), z);
 }
 // the sum of Le(ray) over the lights, as the integrators form it for a ray that leaves the scene: `acc` += w * L per infinite light, in light order
 // (every other light's Le is black, light.cpp / light.h:60-62, and adding it changes nothing)
@@ -582,13 +582,13 @@ RT_DEV V3 quadric_sample_uniform(const DevQuadric RT_G &q, bool ro, float u1, fl
     } else if (q.type == RT_QUADRIC_CYLINDER) {
         const float z = (1.f - u1) * q.zmin + u1 * q.zmax;                         // Lerp
         const float t = u2 * q.phi_max;
-        p = mk3(q.radius * cosf(t), q.radius * sinf(t), z);
+        p = mk3(q.radius * rt_cosf(t), q.radius * rt_sinf(t), z);
         n = mk3(p.x, p.y, 0.f);
     } else {
         const float z = 1.f - 2.f * u1;                                             // UniformSampleSphere mc.cpp:74-81
         const float r = sqrtf(fmaxf(0.f, 1.f - z * z));
         const float phi = 2.f * RT_PI * u2;
-        p = mk3(0.f) + mk3(r * cosf(phi), r * sinf(phi), z) * q.radius;
+        p = mk3(0.f) + mk3(r * rt_cosf(phi), r * rt_sinf(phi), z) * q.radius;
         n = p;
     }
     ns = normalize3(xform_normal(q.w2o, n));
@@ -609,7 +609,7 @@ RT_DEV V3 quadric_sample(const DevScene &sc, unsigned qi, bool ro, V3 p, float u
     const float costheta = (1.f - u1) * cosThetaMax + u1 * 1.f;                     // UniformSampleCone mc.cpp:154-161
     const float sintheta = sqrtf(1.f - costheta * costheta);
     const float phi = u2 * 2.f * RT_PI;
-    const V3 rd = wcX * (cosf(phi) * sintheta) + wcY * (sinf(phi) * sintheta) + wc * costheta;
+    const V3 rd = wcX * (rt_cosf(phi) * sintheta) + wcY * (rt_sinf(phi) * sintheta) + wc * costheta;
     float thit;
     if (!quadric_test(sc, qi, p, rd, RT_RAY_EPSILON, RT_INF, thit)) thit = dot3(Pcenter - p, normalize3(rd));
     const V3 ps = p + rd * thit;
@@ -694,16 +694,13 @@ RT_DEV V3 uniform_sample_cone(float u1, float u2, float costhetamax) {
     const float costheta = (1.f - u1) * costhetamax + u1 * 1.f;                     // Lerp
     const float sintheta = sqrtf(1.f - costheta * costheta);
     const float phi = u2 * 2.f * RT_PI;
-    return mk3(cosf(phi) * sintheta, sinf(phi) * sintheta, costheta);
+    return mk3(rt_cosf(phi) * sintheta, rt_sinf(phi) * sintheta, costheta);
 }
 // the 3x3 of LightToWorld from the WorldToLight the light record carries (its inverse by cofactors; the reference keeps both matrices, light.h:39-40, :74)
 RT_DEV V3 light_to_world(LightRef Lt, V3 v) {
-    const float a = Lt.w2l[0], b = Lt.w2l[1], c = Lt.w2l[2], d = Lt.w2l[3], e = Lt.w2l[4], f = Lt.w2l[5], g = Lt.w2l[6], h = Lt.w2l[7], i = Lt.w2l[8];
-    const float A = e * i - f * h, B = c * h - b * i, C = b * f - c * e;
-    const float D = f * g - d * i, E = a * i - c * g, F = c * d - a * f;
-    const float G = d * h - e * g, H = b * g - a * h, I = a * e - b * d;
-    const float inv = 1.f / (a * A + b * D + c * G);
-    return mk3((A * v.x + B * v.y + C * v.z) * inv, (D * v.x + E * v.y + F * v.z) * inv, (G * v.x + H * v.y + I * v.z) * inv);
+    const float inv = Lt.l2w_scale;
+    return mk3((Lt.l2w[0] * v.x + Lt.l2w[1] * v.y + Lt.l2w[2] * v.z) * inv, (Lt.l2w[3] * v.x + Lt.l2w[4] * v.y + Lt.l2w[5] * v.z) * inv,
+               (Lt.l2w[6] * v.x + Lt.l2w[7] * v.y + Lt.l2w[8] * v.z) * inv);
 }
 template <bool EXT, class RNG>
 RT_DEV void light_sample_emission(const DevScene &sc, LightRef Lt, V3 wc, float wr, float u1, float u2, float u3, float u4, RNG &rng, V3 &o, V3 &d, float &pdf) {

@@ -29,7 +29,7 @@ RT_DEV void hit_point_uv(const DevScene &sc, const Trav &tv, unsigned bits, RtTe
         if (q.type == RT_QUADRIC_DISK) h.v = 1.f - ((sqrtf(phit.x * phit.x + phit.y * phit.y) - q.zmax) / (q.radius - q.zmax));
         else if (q.type == RT_QUADRIC_CONE) h.v = phit.z / q.zmax;
         else if (q.type == RT_QUADRIC_HYPERBOLOID) h.v = (phit.z - q.p1[2]) / (q.p2[2] - q.p1[2]);
-        else if (q.type == RT_QUADRIC_SPHERE) h.v = (acosf(clampf(phit.z / q.radius, -1.f, 1.f)) - q.theta_min) / (q.theta_max - q.theta_min);
+        else if (q.type == RT_QUADRIC_SPHERE) h.v = (rt_acosf(clampf(phit.z / q.radius, -1.f, 1.f)) - q.theta_min) / (q.theta_max - q.theta_min);
         else h.v = (phit.z - q.zmin) / (q.zmax - q.zmin);                        // cylinder, paraboloid
         return;
     }

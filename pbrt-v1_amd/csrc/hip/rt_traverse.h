@@ -16,6 +16,7 @@
 //   * no mailboxing: re-testing a triangle returns the same t (ties accepted, B6).
 #pragma once
 #include "rt_device.h"
+#include "rt_libm.h"
 
 // LDS stack entries per lane: 12 x 8 B x 256 lanes = 24 KB per workgroup, so LDS never limits residency below 6 workgroups
 // per CU; when the ring is full the oldest entry spills to HBM (counted) -- see stack_push / stack_pop.
@@ -107,15 +108,15 @@ RT_DEV bool quadratic(float A, float B, float C, float &t0, float &t1) {   // pb
     if (t0 > t1) { const float tmp = t0; t0 = t1; t1 = tmp; }
     return true;
 }
-// phi of an object-space hit point: atan2f(y, x) folded to [0, 2 pi); the hyperboloid measures it against the generating
+// phi of an object-space hit point: rt_atan2f(y, x) folded to [0, 2 pi); the hyperboloid measures it against the generating
 // segment's point at the hit's height (hyperboloid.cpp:105-111)
 RT_DEV float quadric_phi(const DevQuadric RT_G &q, V3 phit) {
     float phi;
     if (q.type == RT_QUADRIC_HYPERBOLOID) {
         const float v = (phit.z - q.p1[2]) / (q.p2[2] - q.p1[2]);
         const V3 pr = mk3(q.p1[0], q.p1[1], q.p1[2]) * (1.f - v) + mk3(q.p2[0], q.p2[1], q.p2[2]) * v;
-        phi = atan2f(pr.x * phit.y - phit.x * pr.y, phit.x * pr.x + phit.y * pr.y);
-    } else phi = atan2f(phit.y, phit.x);
+        phi = rt_atan2f(pr.x * phit.y - phit.x * pr.y, phit.x * pr.x + phit.y * pr.y);
+    } else phi = rt_atan2f(phit.y, phit.x);
     if (phi < 0.f) phi += 2.f * RT_PI;
     return phi;
 }
@@ -130,7 +131,7 @@ RT_DEV bool quadric_test(const DevScene &sc, unsigned qi, V3 ow, V3 dw, float mi
         const V3 phit = o + d * thit;
         const float dist2 = phit.x * phit.x + phit.y * phit.y;
         if (dist2 > radius * radius || dist2 < zmax * zmax) return false;
-        float phi = atan2f(phit.y, phit.x);
+        float phi = rt_atan2f(phit.y, phit.x);
         if (phi < 0) phi = float(double(phi) + 2. * double(RT_PI));             // "phi += 2. * M_PI": a double sum
         if (phi > phiMax) return false;
         t_out = thit;

@@ -560,6 +560,11 @@ void PbrtApi::LightSource(const std::string &n, const ParamList &p) {
         L.type = RT_LIGHT_SPOT; L.color[0] = I.x; L.color[1] = I.y; L.color[2] = I.z;
         const float origin[3] = {0, 0, 0}; l2w.point(origin, L.pos);
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) L.world_to_light[3 * r + c] = l2w.inv.m[r][c];   // Light::WorldToLight light.h:36
+        {   // Light::LightToWorld light.h:36: what SpotLight::Sample_L(scene, ...) multiplies by (pbrt_host_light_to_world)
+            std::array<float, 9> m;
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) m[size_t(3 * r + c)] = l2w.m.m[r][c];
+            spotLightToWorld[lights.size()] = m;
+        }
         L.cos_total_width = cosf(pbrthip::radians(coneangle));
         L.cos_falloff_start = cosf(pbrthip::radians(coneangle - conedelta));
     } else if (n == "distant") {
@@ -920,6 +925,7 @@ void PbrtApi::ObjectEnd() { if (!verifyWorld("ObjectEnd")) return; inObject = fa
 void PbrtApi::ObjectInstance(const std::string &n) { if (verifyWorld("ObjectInstance")) Error("Object instancing is not on the accelerated path; instance \"%s\" ignored", n.c_str()); }
 
 void PbrtApi::resetWorld() {
+    spotLightToWorld.clear();
     meshes.clear(); materials.clear(); lights.clear(); light_tris.clear(); quadrics.clear();
     std::memset(&volume, 0, sizeof volume); nVolumes = 0;
     std::memset(&density, 0, sizeof density); densityValues.clear();
@@ -961,6 +967,8 @@ void PbrtApi::WorldEnd() {                                                      
     }
     if (materials.size() > 65535) { Error("more than 65535 material instances"); all = false; }
     sd->materials = materials; sd->lights = lights; sd->light_tris = light_tris; sd->quadrics = quadrics;
+    sd->light_to_world.assign(9 * lights.size(), 0.f);
+    for (const auto &kv : spotLightToWorld) for (int k = 0; k < 9; ++k) sd->light_to_world[9 * kv.first + size_t(k)] = kv.second[size_t(k)];
     sd->scene.volume = volume; sd->scene.accel = acc.params;
     sd->density = density; sd->density_values.swap(densityValues);
     for (const RtMaterialTextures &mt : materialTextures) for (int k = 0; k < RT_MATSLOT_COUNT; ++k) sd->has_textures = sd->has_textures || mt.tex[k] >= 0;
@@ -1036,6 +1044,12 @@ const RtVolume *pbrt_host_volume(const RtSceneDesc *s) { return &s->volume; }
 const RtMaterial *pbrt_host_materials(const RtSceneDesc *s) { return s->materials; }
 const RtLight *pbrt_host_lights(const RtSceneDesc *s) { return s->lights; }      // the parsed light table (n_lights of pbrt_host_scene_counts)
 void pbrt_host_material_lobes(const RtMaterial *m, RtMaterialLobes *out) { rt_material_lobes(m, out); }
+// the frame's LightToWorld matrices for rt_scene_set_light_transforms: 9 floats per light (zeros for lights that are not spot lights), or NULL without a spot light
+const float *pbrt_host_light_to_world(PbrtHostScene *h, int i) {
+    const SceneDescription *sd = h->api.frames[i];
+    for (const RtLight &L : sd->lights) if (L.type == RT_LIGHT_SPOT) return sd->light_to_world.data();
+    return nullptr;
+}
 // the frame's DensityRegion for rt_scene_set_density, or NULL when its medium (if any) is homogeneous
 const RtDensityRegion *pbrt_host_density_desc(PbrtHostScene *h, int i) {
     const SceneDescription *sd = h->api.frames[i];

@@ -15,6 +15,7 @@
 // "unknown / missing plug-in" style Error and the documented fallback (matte / kdtree), never a silent
 // substitute.
 #pragma once
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -46,6 +47,7 @@ struct SceneDescription {
     // flattened arrays referenced by `scene`
     std::vector<float> tri_verts; std::vector<uint16_t> tri_material; std::vector<int32_t> tri_light; std::vector<uint8_t> tri_flags;
     std::vector<RtMaterial> materials; std::vector<RtLight> lights; std::vector<float> light_tris; std::vector<RtQuadric> quadrics;
+    std::vector<float> light_to_world;                      // 9 per light: the spot lights' LightToWorld 3x3 (rt_scene_set_light_transforms), zeros elsewhere
     std::vector<int32_t> tri_shading; std::vector<RtTriShading> shading; std::vector<float> xforms;   // per-vertex uv / N / S (trianglemesh)
     RtSceneDesc scene; RtRenderDesc render;
     RtDensityRegion density; std::vector<float> density_values;   // the medium's DensityRegion (kind RT_DENSITY_NONE: none), rt_scene_set_density
@@ -132,6 +134,7 @@ class PbrtApi : public DirectiveSink {
     std::vector<RtQuadric> quadrics;
     std::vector<Mesh> meshes;
     std::vector<RtMaterial> materials; std::vector<RtLight> lights; std::vector<float> light_tris;
+    std::map<size_t, std::array<float, 9>> spotLightToWorld;      // by index into lights
     RtVolume volume; int nVolumes;
     RtDensityRegion density; std::vector<float> densityValues;
     std::vector<RtTexture> texNodes; std::vector<std::string> texNames; std::vector<RtMaterialTextures> materialTextures;
