@@ -353,6 +353,53 @@ int rt_trace_closest(RtScene *s, const RtRay *rays, uint32_t n, RtHit *hits_out)
 /* Scene::IntersectP (kdtree.cpp:404-488 + trianglemesh.cpp:279-314); occluded_out[i] in {0,1} */
 int rt_trace_any(RtScene *s, const RtRay *rays, uint32_t n, uint8_t *occluded_out);
 
+/* ---- Rays and hits in DEVICE memory (additive; the three entry points above are unchanged) ----
+ * For a caller whose rays are already on the GPU (a tensor of origins and directions: a G-buffer, a custom camera model, a collision query)
+ * and who wants the answers there too.  Contract of all four calls:
+ *  - Asynchronous on the scene's stream (rt_scene_set_stream / rt_scene_get_stream).  They never copy to or from the host and never wait for
+ *    the stream, with two exceptions that happen at most once per size / scene: the workspace (two float4 planes of n rays; n more float4s for
+ *    rt_trace_any_device) grows only when n exceeds the largest n seen so far on that scene -- a call with a smaller or equal n allocates
+ *    nothing -- and growing waits for the work queued on the stream before the old block goes; and the first rt_hit_geometry_device call that
+ *    asks for `uv` on a scene with a mesh that has "uv" uploads those uvs (as the first debug frame of rt_render does).  The stream the scene
+ *    creates itself is non-blocking: it is NOT ordered against the null stream or anybody else's -- order it with events, or hand the scene
+ *    your stream.
+ *  - The queue counters of the trace launch are written by a kernel (the host-array entry points upload them from the host).
+ *  - dev_rays is RtRay[n] (32 bytes each: o, d, mint, maxt -- a contiguous float32 [n][8] array), dev_hits is RtHit[n] (16 bytes); both must be
+ *    16-byte aligned.
+ *  - The trace is the kernel of rt_trace_closest / rt_trace_any (rt::pipe_trace_kernel) and the caller's dev_hits is its hit plane: for the same
+ *    rays the hits are those of rt_trace_closest bit for bit; a miss is prim = -1, t = b1 = b2 = 0.  rt_set_counting is honoured: the counting
+ *    twin when enabled (nodes_visited, leaf_refs, tri_tests advance), the timed kernel otherwise; the hits are the same either way.
+ *  - Refused before any launch with RT_EINVAL (rt_last_error says which): a null scene, ray or output pointer; an RtHitGeometry whose fields
+ *    are all null; a ray or hit pointer that is not 16-byte aligned; n above 2^30.  n == 0 is RT_OK and launches nothing.
+ *  - Unusable rays never reach traversal (GridAccel's DDA would turn their values into voxel indices).  A ray is unusable when a component of
+ *    o or d is not finite, when d is (0, 0, 0), or when mint or maxt is NaN; the kernel that lays the rays out for the trace kernel replaces
+ *    it by an empty ray, i.e. it misses.  maxt = +inf is an ordinary ray (geometry.h:204-217), and so is mint > maxt (it is empty by itself).
+ *    The predicate is rt::ray_usable in pbrt-v1_amd/csrc/hip/rt_ray_guard.h (no HIP header; tested on the host). */
+/* Scene::Intersect (core/scene.h:60-62 -> Primitive::Intersect, kdtree.cpp:313-403 / grid.cpp:224-286) for n rays */
+int rt_trace_closest_device(RtScene *s, const RtRay *dev_rays, uint32_t n, RtHit *dev_hits);
+/* Scene::IntersectP (core/scene.h:63-65, kdtree.cpp:404-488 / grid.cpp:331-390); dev_occluded[i] in {0,1}, any alignment */
+int rt_trace_any_device(RtScene *s, const RtRay *dev_rays, uint32_t n, uint8_t *dev_occluded);
+/* What Scene::Intersect leaves in Intersection (core/primitive.h:107-121): its DifferentialGeometry dg (core/shape.h:34-51: p, nn, u, v), the
+ * shading normal of the BSDF Intersection::GetBSDF builds (primitive.cpp:160-167: Shape::GetShadingGeometry + Material::GetBSDF, bsdf->dgShading.nn),
+ * the primitive's material and GetAreaLight() (primitive.cpp:155-158).  Computed from (ray, hit) with the render kernels' code: triangles with
+ * and without per-vertex uv / N / S, ReverseOrientation, handedness-swapping transforms and the six quadrics.  dev_hits are the records
+ * rt_trace_closest_device wrote for dev_rays (a record whose prim is no primitive of the scene counts as a miss).  Only the fields whose pointer
+ * is not NULL are computed and stored.  A miss yields zeros in every float field and -1 in both index fields. */
+typedef struct RtHitGeometry {      /* device pointers, each may be NULL (field not wanted) */
+    float   *p;          /* [n][3] dg.p                                                   */
+    float   *ng;         /* [n][3] dg.nn: geometric normal, orientation flips applied     */
+    float   *ns;         /* [n][3] shading normal (bsdf->dgShading.nn)                    */
+    float   *uv;         /* [n][2] dg.u, dg.v                                             */
+    int32_t *material;   /* [n] index into RtSceneDesc.materials, -1 on a miss            */
+    int32_t *light;      /* [n] area-light index of the primitive, -1 if none or a miss   */
+} RtHitGeometry;
+int rt_hit_geometry_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uint32_t n, const RtHitGeometry *out);
+/* Camera::GenerateRay (core/camera.h:33-34; perspective.cpp:51-82, orthographic.cpp:48-79, environment.cpp:47-61) as rt_camera_rays, into
+ * dev_rays[count]: the rays of camera samples first .. first + count - 1, bit for bit those of rt_camera_rays */
+int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays);
+/* The stream the scene's calls are queued on: its own (non-blocking) one, or what rt_scene_set_stream was given */
+int rt_scene_get_stream(RtScene *s, void **hip_stream_out);
+
 /* Film accumulators, ImageFilm::Pixel (image.cpp:57-65) as planes:
  * float accum[5][y_pixel_count][x_pixel_count] = sum w*L.r, .g, .b, sum w*alpha, sum w.
  * rt_film_bind: accumulate into caller-provided DEVICE memory (e.g. a torch tensor that is

@@ -34,7 +34,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse",
 
 
 HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
-             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
+             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
 def _include_closure(path, seen=None):
@@ -263,6 +263,13 @@ class RtRenderDesc(C.Structure):                   # include/pbrt_hip.h (1128 by
                [(n, C.c_int32) for n in ("shard_index", "shard_count", "tile_pixels")]
 
 
+class RtHitGeometry(C.Structure):                  # include/pbrt_hip.h: six device pointers, NULL = field not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("p", "ng", "ns", "uv", "material", "light")]
+
+
+HIT_FIELDS = ("p", "ng", "ns", "uv", "material", "light")      # DeviceScene.intersect(fields=...): name -> (columns, integer?)
+_HIT_FIELD_SHAPE = {"p": (3, False), "ng": (3, False), "ns": (3, False), "uv": (2, False), "material": (0, True), "light": (0, True)}
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -309,7 +316,8 @@ def hip_lib():
                      "rt_counters_reset", "rt_last_render_ms", "rt_last_render_stats", "rt_samples_read", "rt_device_count", "rt_set_counting",
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
-                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms"):
+                     "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
+                     "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -323,6 +331,11 @@ def hip_lib():
         L.rt_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_trace_any.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_trace_closest_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_trace_any_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
+        L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.rt_scene_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.rt_film_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
         L.rt_film_clear.argtypes = [C.c_void_p]
         L.rt_film_read.argtypes = [C.c_void_p, C.c_void_p]
@@ -826,6 +839,16 @@ class ParsedScene:
         p = host_lib().pbrt_host_tri_verts(self.scene_desc)
         return np.ctypeslib.as_array(p, shape=(self.n_tris, 3, 3)).copy()
 
+    def tri_tables(self):
+        """(tri_material uint16 [n_tris], tri_light int32 [n_tris]) of the flat scene (RtSceneDesc, include/pbrt_hip.h): per primitive the index
+        into materials() and the area-light index or -1 -- what DeviceScene.intersect returns as `material` and `light` for a hit on it."""
+        class _Head(C.Structure):                  # the leading fields of RtSceneDesc
+            _fields_ = [("n_tris", C.c_uint32), ("tri_verts", C.c_void_p), ("tri_material", C.POINTER(C.c_uint16)), ("tri_light", C.POINTER(C.c_int32))]
+        h = C.cast(self.scene_desc, C.POINTER(_Head)).contents
+        if h.n_tris == 0:
+            return np.zeros(0, np.uint16), np.zeros(0, np.int32)
+        return (np.ctypeslib.as_array(h.tri_material, shape=(h.n_tris,)).copy(), np.ctypeslib.as_array(h.tri_light, shape=(h.n_tris,)).copy())
+
     def serialize(self) -> bytes:
         """Canonical byte image of this frame's descriptors (include/pbrt_hip_desc.h rt_desc_serialize)."""
         H = host_lib()
@@ -856,6 +879,7 @@ class DeviceScene:
         DeviceScene.accel_arrays() / accel_info(), e.g. through publish_accel / attach_accel): rt_scene_create_prebuilt."""
         self.parsed = parsed
         self._s = C.c_void_p()
+        self._device = device
         if prebuilt is None:
             _chk(hip_lib().rt_scene_create(parsed.scene_desc, device, C.byref(self._s)))
         else:
@@ -1001,6 +1025,101 @@ class DeviceScene:
         occ = np.zeros(len(rays), np.uint8)
         _chk(hip_lib().rt_trace_any(self._s, rays.ctypes.data, len(rays), occ.ctypes.data))
         return occ
+
+    # ---- rays and hits in device memory (include/pbrt_hip.h, "Rays and hits in DEVICE memory"): torch tensors in, torch tensors out.  The library's
+    # calls are asynchronous on the scene's stream, which is not ordered against torch's: each wrapper makes the scene's stream wait for torch's
+    # current stream before its launches and torch's current stream wait for the scene's after them (events, no host synchronisation), so the
+    # next torch op may use the result.  torch is imported only here.  A process that uses them imports torch BEFORE this package loads libpbrt_hip.so (hip_lib():
+    # the first DeviceScene), as bench.py does: torch carries a HIP runtime of its own, the first one loaded serves both, and a stream of one
+    # runtime means nothing to another (loaded after the library, torch finds no device at all).
+    @staticmethod
+    def _check_ray_tensor(torch, rays, device):
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("rays: a torch tensor is needed, got %s" % type(rays).__name__)
+        if rays.dtype != torch.float32:
+            raise ValueError("rays: dtype float32 is needed, got %s" % rays.dtype)
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: shape [n, 8] (o, d, mint, maxt) is needed, got %s" % (tuple(rays.shape),))
+        if not rays.is_contiguous():
+            raise ValueError("rays: a contiguous tensor is needed")
+        if not rays.is_cuda:
+            raise ValueError("rays: a tensor in device memory is needed, got one on %s" % rays.device)
+        if device is not None and device >= 0 and rays.device.index != device:
+            raise ValueError("rays: the tensor is on %s, the scene on device %d" % (rays.device, device))
+
+    def _scene_stream(self, torch, device):
+        """(torch's current stream, the scene's stream as a torch stream or None when they are the same)"""
+        p = C.c_void_p()
+        _chk(hip_lib().rt_scene_get_stream(self._s, C.byref(p)))
+        cur = torch.cuda.current_stream(device)
+        if (p.value or 0) == cur.cuda_stream:
+            return cur, None
+        return cur, (torch.cuda.ExternalStream(p.value, device=device) if p.value else torch.cuda.default_stream(device))
+
+    def intersect(self, rays, fields=HIT_FIELDS) -> dict:
+        """Scene::Intersect for rays in device memory (rt_trace_closest_device) and the hit geometry asked for (rt_hit_geometry_device).
+        rays: contiguous float32 [n, 8] torch tensor on the scene's device.  Returns torch tensors on that device: `prim` (int32 [n], -1 = miss),
+        `t`, `b1`, `b2` (float32 [n]; views of one [n, 4] record array) and per requested field `p`, `ng`, `ns` (float32 [n, 3]), `uv` ([n, 2]),
+        `material`, `light` (int32 [n]).  fields=() gives the hits only."""
+        import torch
+        fields = tuple(fields)
+        for f in fields:
+            if f not in _HIT_FIELD_SHAPE:
+                raise ValueError("fields: unknown field %r (known: %s)" % (f, ", ".join(HIT_FIELDS)))
+        self._check_ray_tensor(torch, rays, getattr(self, "_device", None))
+        n, dev = int(rays.shape[0]), rays.device
+        hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        extra = {f: (torch.empty(n, dtype=torch.int32, device=dev) if _HIT_FIELD_SHAPE[f][1] else torch.empty((n, _HIT_FIELD_SHAPE[f][0]), dtype=torch.float32, device=dev))
+                 for f in fields}
+        if n:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_trace_closest_device(self._s, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
+            if fields:
+                g = RtHitGeometry(**{f: t.data_ptr() for f, t in extra.items()})
+                _chk(hip_lib().rt_hit_geometry_device(self._s, C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr()), n, C.byref(g)))
+            if mine is not None:
+                cur.wait_stream(mine)
+        out = {"prim": hits.view(torch.int32)[:, 0], "t": hits[:, 1], "b1": hits[:, 2], "b2": hits[:, 3]}
+        out.update(extra)
+        return out
+
+    def occluded(self, rays):
+        """Scene::IntersectP for rays in device memory (rt_trace_any_device): a uint8 [n] torch tensor, 1 = something lies in (mint, maxt)."""
+        import torch
+        self._check_ray_tensor(torch, rays, getattr(self, "_device", None))
+        n, dev = int(rays.shape[0]), rays.device
+        occ = torch.empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_trace_any_device(self._s, C.c_void_p(rays.data_ptr()), n, C.c_void_p(occ.data_ptr())))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return occ
+
+    def camera_rays_device(self, first: int, count: int):
+        """rt_camera_rays_device: the rays of camera samples first .. first + count - 1 of the parsed frame as a float32 [count, 8] torch tensor on
+        the scene's device (bit for bit camera_rays(first, count))."""
+        import torch
+        if first < 0 or count < 0:
+            raise ValueError("camera_rays_device: first and count must not be negative")
+        if not torch.cuda.is_available():
+            raise RtError("torch sees no HIP device.  torch carries a HIP runtime of its own and the first one a process loads serves both: "
+                          "import torch before this package loads libpbrt_hip.so (before the first DeviceScene), as bench.py does")
+        d = getattr(self, "_device", -1)
+        dev = torch.device("cuda", d if d is not None and d >= 0 else torch.cuda.current_device())
+        rays = torch.empty((int(count), 8), dtype=torch.float32, device=dev)
+        if count:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_camera_rays_device(self._s, self.parsed.render_desc, int(first), int(count), C.c_void_p(rays.data_ptr())))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return rays
 
     def close(self):
         if self._s:

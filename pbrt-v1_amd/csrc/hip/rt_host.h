@@ -1,6 +1,7 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
 // the owners of its device memory, events and stream, the kernel tables and their resident grids (rt_flavour.h).  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
-// rt_kernels.hip renders (make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*).  Round 6: split out of a 2 300-line rt_kernels.hip.
+// rt_kernels.hip renders (make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
+// memory (rt_trace_*_device, rt_hit_geometry_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
 #include "rt_flavour.h"
 #include "rt_render_kernel.h"
@@ -142,6 +143,9 @@ struct RtScene {
     DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;
     DevBuf<unsigned> trace_qc;
+    // rt_trace_*_device (rt_rays.hip): the two ray planes the trace kernel reads, and the hit plane of an any-hit call (a closest-hit call
+    // writes the caller's RtHit array); each grows only when a call brings more rays than any before it
+    DevBuf<float4> ray_planes, any_hits;
 };
 #define RT_PIPE_QN 4096          // ring of per-iteration queue counters
 #define RT_PIPE_TIMED 256        // iterations whose trace launch is bracketed by events

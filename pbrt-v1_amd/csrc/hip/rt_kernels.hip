@@ -577,6 +577,24 @@ int rt_camera_rays(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t 
     HIPCHK(hipMemcpy(rays_out, dev, size_t(count) * sizeof(RtRay), hipMemcpyDeviceToHost));
     return RT_OK;
 }
+// The same into the caller's DEVICE buffer, asynchronous on the scene's stream: no allocation, no copy, no wait (rt_rays.hip traces such rays).
+int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays) {
+    if (!s) return fail(RT_EINVAL, "rt_camera_rays_device: null scene");
+    if (!rd) return fail(RT_EINVAL, "rt_camera_rays_device: null render description");
+    if (!dev_rays) return fail(RT_EINVAL, "rt_camera_rays_device: null ray pointer");
+    if ((reinterpret_cast<uintptr_t>(dev_rays) & 15u) != 0) return fail(RT_EINVAL, "rt_camera_rays_device: dev_rays is not 16-byte aligned");
+    if (count > (1u << 30)) return fail(RT_EINVAL, "rt_camera_rays_device: count = " + std::to_string(count) + " is above 2^30");
+    HIPCHK(hipSetDevice(s->device));
+    // A camera ray depends on the sampler, the film and the camera, not on the integrator's sample requests (setup_sample, rt_integrate.h); the two
+    // integrators whose requests make_frame keeps in a device table (a blocking copy) are described as Whitted here
+    RtRenderDesc d = *rd;
+    if (d.integrator == RT_INTEGRATOR_BIDIRECTIONAL || (d.integrator == RT_INTEGRATOR_DIRECT && d.strategy == RT_STRATEGY_ALL)) d.integrator = RT_INTEGRATOR_WHITTED;
+    DevFrame fr; int rc = make_frame(s, &d, fr, false); if (rc) return rc;
+    if (count == 0) return RT_OK;
+    hipLaunchKernelGGL(camera_kernel, dim3((count + 255) / 256), dim3(256), 0, s->stream, s->dev, fr, (unsigned long long)first, count, dev_rays);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
 
 // Scene::Intersect / IntersectP for caller-supplied rays: the rays form one queue of the pipeline's trace kernel (counting
 // twin with the quadric code), so the unit parity tests exercise the very kernel the large-scene renders spend their time in.

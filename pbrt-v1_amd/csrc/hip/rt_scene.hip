@@ -587,6 +587,11 @@ int rt_scene_set_stream(RtScene *s, void *hip_stream) {
     s->stream = static_cast<hipStream_t>(hip_stream);
     return RT_OK;
 }
+int rt_scene_get_stream(RtScene *s, void **hip_stream_out) {
+    if (!s || !hip_stream_out) return fail(RT_EINVAL, "rt_scene_get_stream: null argument");
+    *hip_stream_out = s->stream;
+    return RT_OK;
+}
 
 // DensityRegion (volume.h:62-90) for the scene's medium: the region's parameters go into DevScene (read by the EXT kernels only), a grid into HBM.
 int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
