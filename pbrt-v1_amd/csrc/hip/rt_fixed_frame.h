@@ -1,0 +1,94 @@
+// rt_fixed_frame.h -- the "fixed frame": what the large-scene megakernels may assume at compile time.  The between-rays code of rt_integrate.h and the
+// work fetch of rt_render_kernel.h select the sampler, the camera model, the lens and the work order at run time (a scalar load of a descriptor field, a
+// wait, a compare and a branch each, and the code of every alternative in every instantiation).  A traits type as their trailing template parameter turns
+// those selections into constants: fixed::Any (the default) is the code as it always was, fixed::Frame the twin for the frames qualifies() admits.  What a
+// fixed kernel still computes are the expressions the generic kernel runs for such a frame, so the films are bit-identical.  The family of the fixed
+// kernels (flavour::Fixed, rt_mega_f.hip) is declared here too.  No HIP header: tests/fixed_frame_host_test.cpp checks the rules with a host compiler.
+#pragma once
+#include "rt_flavour.h"
+
+// Each axis can be switched off alone with -DRT_FIXED_<AXIS>=0 (measurements: profiles/fixed_frame_kernels.txt); qualifies() stays as strict as it is.
+#ifndef RT_FIXED_SAMPLER
+#define RT_FIXED_SAMPLER 1
+#endif
+#ifndef RT_FIXED_N1
+#define RT_FIXED_N1 1
+#endif
+#ifndef RT_FIXED_CAMERA
+#define RT_FIXED_CAMERA 1
+#endif
+#ifndef RT_FIXED_TILE_ORDER
+#define RT_FIXED_TILE_ORDER 1
+#endif
+
+namespace rt {
+namespace fixed {
+
+// nothing known at compile time: every selection is made at run time
+struct Any {
+    static constexpr int sampler = -1;               // RT_SAMPLER_*, or -1: any (DevFrame::sampler decides)
+    static constexpr bool no_lens = false;           // RtCamera::lens_radius == 0
+    static constexpr bool no_env_camera = false;     // RtCamera::type is perspective or orthographic (still a run-time value between those two)
+    static constexpr bool tile_order = false;        // single shard with DevFrame::mega_tile > 0: tile_order_to_sample hands out the work, fewer than 2^32 samples
+    static constexpr bool all_n1 = false;            // every DimReq of the frame has n == 1 (one_d, two_d, light_dims)
+};
+// the frames of qualifies()
+struct Frame {
+    static constexpr int sampler = RT_FIXED_SAMPLER ? int(RT_SAMPLER_STRATIFIED) : -1;
+    static constexpr bool no_lens = RT_FIXED_CAMERA != 0;
+    static constexpr bool no_env_camera = RT_FIXED_CAMERA != 0;
+    static constexpr bool tile_order = RT_FIXED_TILE_ORDER != 0;
+    static constexpr bool all_n1 = RT_FIXED_N1 != 0;
+};
+
+// what the host knows of a frame and its scene when it picks the kernel (render_mega, rt_kernels.hip)
+struct Facts {
+    int integrator;          // RtRenderDesc::integrator
+    int sampler;             // DevFrame::sampler
+    bool weighted;           // DirectLighting "weighted": a kernel family of its own
+    float lens_radius;       // RtCamera::lens_radius
+    int camera_type;         // RtCamera::type
+    int shard_count;         // DevFrame::shard_count
+    int mega_tile;           // DevFrame::mega_tile
+    int dims_max_n;          // DevFrame::dims_max_n: the largest n of the frame's sample requests (a light's nsamples); 0 when it has none
+    bool counting, ext, vol; // RtScene::counting, has_ext, a medium
+    bool high_occ;           // DevFrame::high_occupancy
+};
+// A frame takes the fixed kernel when everything Frame states holds, and the kernel it would take otherwise is one of the six that have a fixed twin
+// (Whitted, DirectLighting "all" / "one", Path; timed, no EXT code, no medium, high occupancy).  Jitter stays a run-time value.
+constexpr bool qualifies(const Facts &f) {
+    return f.integrator >= RT_INTEGRATOR_WHITTED && f.integrator <= RT_INTEGRATOR_PATH && !f.weighted &&
+           f.sampler == RT_SAMPLER_STRATIFIED &&
+           f.lens_radius == 0.f &&
+           (f.camera_type == RT_CAMERA_PERSPECTIVE || f.camera_type == RT_CAMERA_ORTHOGRAPHIC) &&
+           f.shard_count == 1 && f.mega_tile > 0 &&
+           f.dims_max_n <= 1 &&
+           !f.counting && !f.ext && !f.vol && f.high_occ;
+}
+
+}  // namespace fixed
+
+namespace flavour {
+// rt::render_kernel_fixed<..., fixed::Frame> (rt_mega_f.hip): the fixed twins of Mega's entries 8 and 9 (high occupancy, timed, no EXT, no medium; kd-tree and
+// grid) of the three integrators, in one table: entry 2 * integrator + grid
+struct Fixed {
+    static constexpr int N = 6;
+    static constexpr int index(const Request &r) { return 2 * r.integ + (r.grid ? 1 : 0); }
+    static constexpr int integrator(int k) { return k >> 1; }
+    static constexpr Flavour flavour(int k) { return Flavour{false, k & 1, false, false, RT_HIGH_OCC_WAVES, true}; }
+    // the request entry k serves (Flavour::request() does not know the integrator)
+    static constexpr Request request(int k) { Request r = flavour(k).request(); r.integ = integrator(k); return r; }
+    // ... and the entry of Mega's table it is the twin of
+    static constexpr int generic(int k) { return Mega::index(request(k)); }
+};
+constexpr bool fixed_round_trips() {
+    for (int k = 0; k < Fixed::N; ++k) {
+        if (Fixed::index(Fixed::request(k)) != k) return false;
+        const Flavour g = Mega::flavour(Fixed::generic(k), Fixed::integrator(k)), f = Fixed::flavour(k);
+        if (g.count != f.count || g.accel != f.accel || g.vol != f.vol || g.ext != f.ext || g.waves != f.waves || g.high_occ != f.high_occ) return false;
+    }
+    return true;
+}
+static_assert(fixed_round_trips(), "Fixed: index(request(k)) != k, or entry k is not the twin of a Mega entry");
+}  // namespace flavour
+}  // namespace rt

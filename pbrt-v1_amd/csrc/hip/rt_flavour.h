@@ -1,7 +1,8 @@
 // rt_flavour.h -- which kernel instantiation a frame runs.  A frame asks with a Request; each of the eight kernel families has index(request), the
 // entry of its table that serves the request, flavour(k), the template arguments of entry k, and N, the table's size.  The translation units build
 // their tables from flavour(k) (RT_FLAVOUR_TABLE below), rt_host.h sizes the resident grids by N and rt_kernels.hip picks entries with index():
-// a table's order, its size and the host's choice cannot disagree.  No HIP header: tests/flavour_host_test.cpp checks the rules with a host compiler.
+// a table's order, its size and the host's choice cannot disagree.  (A ninth family, flavour::Fixed -- the twins of six Mega entries compiled for a
+// fixed frame -- lives in rt_fixed_frame.h with the traits it is built from.)  No HIP header: tests/flavour_host_test.cpp checks the rules with a host compiler.
 #pragma once
 #include "../../../include/pbrt_hip.h"
 #include <array>

@@ -45,6 +45,7 @@ using namespace rt;
 // entries and index(), the entry a frame takes.  The megakernel and the pipeline's shade kernel have a table per integrator (Whitted, DirectLighting, Path).
 namespace rt {
 extern const flavour::Table<RenderKernelFn, flavour::Mega> g_render_kernels_whitted, g_render_kernels_direct, g_render_kernels_path;
+extern const flavour::Table<RenderKernelFn, flavour::Fixed> g_render_kernels_fixed;        // the fixed-frame twins of six Mega entries (rt_fixed_frame.h), all integrators in one table
 extern const flavour::Table<RenderKernelFn, flavour::Weighted> g_render_kernels_weighted;
 extern const flavour::Table<RenderKernelFn, flavour::Bidir> g_render_kernels_bidir;
 extern const flavour::Table<RenderKernelFn, flavour::Debug> g_render_kernels_debug;
@@ -59,6 +60,7 @@ static const flavour::Table<PipeShadeFn, flavour::Shade> *const g_pipe_shade[RT_
 // The persistent families are launched with as many blocks as stay resident (scene_create): a grid per table entry
 struct ResidentGrids {
     flavour::Table<unsigned, flavour::Mega> mega[RT_INTEGRATOR_PATH + 1];
+    flavour::Table<unsigned, flavour::Fixed> fixed;
     flavour::Table<unsigned, flavour::Weighted> weighted;
     flavour::Table<unsigned, flavour::Bidir> bidir;
     flavour::Table<unsigned, flavour::Debug> debug;
@@ -139,6 +141,7 @@ struct RtScene {
     // queue pipeline (rt_pipeline.h)
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
     Pinned<unsigned> h_qcount;                          // page-locked mirror of q_count (termination test)
+    bool last_fixed = false;                            // the last frame ran a fixed-frame kernel (rt_fixed_frame.h)
     bool last_pipeline = false, last_marches = false; int pipe_iters = 0, pipe_timed = 0; unsigned pipe_slots = 0;
     DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;

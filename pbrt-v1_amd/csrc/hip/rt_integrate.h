@@ -14,6 +14,7 @@
 #pragma once
 #include "rt_shade.h"
 #include "rt_texture.h"
+#include "rt_fixed_frame.h"
 
 namespace rt {
 
@@ -121,8 +122,10 @@ RT_DEV uint32_t pixel_stream(const DevFrame &fr, const Lane &ln) {
 //   random          one RandomFloat() per value, in request order (random.cpp:107-112)
 //   lowdiscrepancy  per-pixel scrambled (0,2)-sequence tables, shuffled within each sample's block and then across
 //                   the pixel's samples (lowdiscrepancy.cpp:93-104, sampling.h:152-174); every draw addressable
+template <class FX = fixed::Any>
 RT_DEV float dim_value(const DevFrame &fr, const Lane &ln, const DimReq &r, int j, int d) {
-    if (fr.sampler == RT_SAMPLER_STRATIFIED) return lhs_value(ln, r, j, d);
+    if constexpr (FX::sampler == RT_SAMPLER_STRATIFIED && FX::all_n1) return (0 + rng_f32(ln.rng.base, ln.dim_base + r.f_base + d)) * 1.f;    // lhs_value's n == 1
+    if (FX::sampler == RT_SAMPLER_STRATIFIED || fr.sampler == RT_SAMPLER_STRATIFIED) return lhs_value(ln, r, j, d);
     if (fr.sampler == RT_SAMPLER_RANDOM) return rng_f32(ln.rng.base, ln.dim_base + r.f_base + j * r.dims + d);
     const uint32_t pb = pixel_stream(fr, ln);
     const int P = fr.spp, n = r.n, s = int(ln.work % uint32_t(P));
@@ -192,9 +195,10 @@ RT_DEV void stratified_camera_sample(const DevFrame &fr, uint32_t pixel_index, i
 
 // {Perspective,Ortho,Environment}Camera::GenerateRay (cameras/perspective.cpp:51-82, orthographic.cpp:48-79,
 // environment.cpp:47-61)
+template <class FX = fixed::Any>
 RT_DEV Ray camera_ray(const RtCamera &cam, float ix, float iy, float lensU, float lensV) {
     Ray r;
-    if (cam.type == RT_CAMERA_ENVIRONMENT) {
+    if (!FX::no_env_camera && cam.type == RT_CAMERA_ENVIRONMENT) {
         r.o = xform_point(cam.camera_to_world, mk3(0.f, 0.f, 0.f));               // rayOrigin = CameraToWorld(Point(0,0,0))
         const float theta = RT_PI * iy / cam.y_res;                               // M_PI is a float (pbrt.h:204); int -> float promotion
         const float phi = 2 * RT_PI * ix / cam.x_res;
@@ -206,7 +210,7 @@ RT_DEV Ray camera_ray(const RtCamera &cam, float ix, float iy, float lensU, floa
     V3 Pcamera = xform_point(cam.raster_to_camera, mk3(ix, iy, 0.f));
     r.o = Pcamera;
     r.d = cam.type == RT_CAMERA_ORTHOGRAPHIC ? mk3(0.f, 0.f, 1.f) : Pcamera;
-    if (cam.lens_radius > 0.f) {
+    if (!FX::no_lens && cam.lens_radius > 0.f) {
         float lu, lv; concentric_disk(lensU, lensV, lu, lv);
         lu *= cam.lens_radius; lv *= cam.lens_radius;
         float ft = (cam.focal_distance - cam.hither) / r.d.z;
@@ -279,18 +283,19 @@ RT_DEV void tile_order_to_sample(const DevFrame &fr, unsigned w, unsigned &pixel
     pixel = (ty * T + qy) * W + tx * T + qx;
 }
 
+template <class FX = fixed::Any>
 RT_DEV void setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned long long pixel, int s, Ray &ray) {
     const int w = fr.x_end - fr.x_start;
     int px, py;
-    if (fr.total_pixels <= 0xffffffffull) { const unsigned row = fastdiv(unsigned(pixel), fr.div.width); px = fr.x_start + int(unsigned(pixel) - row * unsigned(w)); py = fr.y_start + int(row); }
+    if (FX::tile_order || fr.total_pixels <= 0xffffffffull) { const unsigned row = fastdiv(unsigned(pixel), fr.div.width); px = fr.x_start + int(unsigned(pixel) - row * unsigned(w)); py = fr.y_start + int(row); }
     else { px = fr.x_start + int(pixel % w); py = fr.y_start + int(pixel / w); }
     const uint32_t n0 = uint32_t(pixel * fr.spp);
     ln.sample_index = n0 + uint32_t(s);
     ln.rng.base = rng_base(ln.sample_index, fr.seed);
     // the first pixel's strata are drawn by the sampler's constructor, before any sample key exists
     float lu = 0.5f, lv = 0.5f;
-    const bool need_lens = sc.cam.lens_radius > 0.f;
-    if (fr.sampler == RT_SAMPLER_STRATIFIED) {
+    const bool need_lens = !FX::no_lens && sc.cam.lens_radius > 0.f;
+    if (FX::sampler == RT_SAMPLER_STRATIFIED || fr.sampler == RT_SAMPLER_STRATIFIED) {
         // the first pixel's strata are drawn by the sampler's constructor, before any sample key exists
         const uint32_t pix_base = (pixel == 0) ? rng_base(0xFFFFFFFFu, fr.seed) : rng_base(n0, fr.seed);
         ln.dim_base = (s == 0 && pixel != 0) ? fr.pixgen_draws : 0u;
@@ -314,8 +319,8 @@ RT_DEV void setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
             lu = van_der_corput(uint32_t(lp), rng_u32(pix_base, lb)); lv = sobol2(uint32_t(lp), rng_u32(pix_base, lb + 1));
         }
     }
-    ln.rng.ctr = ln.dim_base + ((fr.sampler == RT_SAMPLER_LOWDISCREPANCY) ? 0u : fr.lhs_total);
-    ray = camera_ray(sc.cam, ln.image_x, ln.image_y, lu, lv);
+    ln.rng.ctr = ln.dim_base + ((FX::sampler != RT_SAMPLER_STRATIFIED && fr.sampler == RT_SAMPLER_LOWDISCREPANCY) ? 0u : fr.lhs_total);
+    ray = camera_ray<FX>(sc.cam, ln.image_x, ln.image_y, lu, lv);
     // scene.cpp:47-53 generates the differential's offset rays with ++ / -- on sample->imageX / imageY: Film::AddSample later sees
     // (x + 1) - 1 in float arithmetic, not x (found by the reference-side binding test, tests/test_boundary.py)
     ln.image_x = (ln.image_x + 1.f) - 1.f; ln.image_y = (ln.image_y + 1.f) - 1.f;
@@ -731,7 +736,7 @@ RT_DEV void debug_vertex(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
 }
 
 // The body of ONE stage.  Returns when the lane has a ray in flight or has changed stage.
-template <bool COUNT, int INTEG_, bool VOL, bool EXT, int STAGE, bool DEFER = false, bool PARK = false>
+template <bool COUNT, int INTEG_, bool VOL, bool EXT, int STAGE, bool DEFER = false, bool PARK = false, class FX = fixed::Any>
 RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid,
                        unsigned *c_closest, unsigned *c_any, unsigned *c_bad) {
     // RT_INTEG_DIRECT_WEIGHTED: DirectLighting with strategy "weighted", a kernel family of its own so that the all / one kernels keep their code
@@ -805,11 +810,11 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 if (ln.li >= nLights) { ++ln.ord; ln.stage = ST_SPECULAR; return; }                // (the counter stands where one estimate leaves it)
                 ln.rng.ctr = ln.ctr0;
             }
-            const float ls1 = dim_value(fr, ln, fr.two_d[0], 0, 0), ls2 = dim_value(fr, ln, fr.two_d[0], 0, 1);
-            ln.bs1 = dim_value(fr, ln, fr.two_d[1], 0, 0); ln.bs2 = dim_value(fr, ln, fr.two_d[1], 0, 1);
-            ln.bcs = dim_value(fr, ln, fr.one_d[1], 0, 0);
+            const float ls1 = dim_value<FX>(fr, ln, fr.two_d[0], 0, 0), ls2 = dim_value<FX>(fr, ln, fr.two_d[0], 0, 1);
+            ln.bs1 = dim_value<FX>(fr, ln, fr.two_d[1], 0, 0); ln.bs2 = dim_value<FX>(fr, ln, fr.two_d[1], 0, 1);
+            ln.bcs = dim_value<FX>(fr, ln, fr.one_d[1], 0, 0);
             if (fr.weighted_phase == 2) {
-                if (ln.li == 0 && ln.lj == 0) RT_GPTR(float, fr.wt_rec)[weighted_record(fr, ln, nLights)] = dim_value(fr, ln, fr.one_d[0], 0, 0);
+                if (ln.li == 0 && ln.lj == 0) RT_GPTR(float, fr.wt_rec)[weighted_record(fr, ln, nLights)] = dim_value<FX>(fr, ln, fr.one_d[0], 0, 0);
                 estimate_direct_begin<EXT, DEFER>(sc, ln, ln.li, ls1, ls2);
             } else {
                 const float2 pick = RT_GPTR(const float2, fr.wt_pick)[ln.ord++];
@@ -828,10 +833,10 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             if (from_sampler) {
                 const int i1 = (INTEG == RT_INTEGRATOR_PATH) ? 3 * k : 0;
                 const int i2 = (INTEG == RT_INTEGRATOR_PATH) ? 3 * k : 0;
-                un = dim_value(fr, ln, fr.one_d[i1], 0, 0);
-                ls1 = dim_value(fr, ln, fr.two_d[i2], 0, 0); ls2 = dim_value(fr, ln, fr.two_d[i2], 0, 1);
-                ln.bs1 = dim_value(fr, ln, fr.two_d[i2 + 1], 0, 0); ln.bs2 = dim_value(fr, ln, fr.two_d[i2 + 1], 0, 1);
-                ln.bcs = dim_value(fr, ln, fr.one_d[i1 + 1], 0, 0);
+                un = dim_value<FX>(fr, ln, fr.one_d[i1], 0, 0);
+                ls1 = dim_value<FX>(fr, ln, fr.two_d[i2], 0, 0); ls2 = dim_value<FX>(fr, ln, fr.two_d[i2], 0, 1);
+                ln.bs1 = dim_value<FX>(fr, ln, fr.two_d[i2 + 1], 0, 0); ln.bs2 = dim_value<FX>(fr, ln, fr.two_d[i2 + 1], 0, 1);
+                ln.bcs = dim_value<FX>(fr, ln, fr.one_d[i1 + 1], 0, 0);
             } else {
                 un = ln.rng.next_float();
                 ls1 = ln.rng.next_float(); ls2 = ln.rng.next_float();           // transport.cpp:141-145
@@ -847,9 +852,9 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             const DimReq RT_G *ld = RT_GPTR(const DimReq, fr.light_dims) + 3 * ln.li;
             const DimReq rl = ld[0], rb = ld[1], rc = ld[2];
             if (ln.lj == 0) ln.Ld_light = mk3(0.f);
-            const float ls1 = dim_value(fr, ln, rl, ln.lj, 0), ls2 = dim_value(fr, ln, rl, ln.lj, 1);
-            ln.bs1 = dim_value(fr, ln, rb, ln.lj, 0); ln.bs2 = dim_value(fr, ln, rb, ln.lj, 1);
-            ln.bcs = dim_value(fr, ln, rc, ln.lj, 0);
+            const float ls1 = dim_value<FX>(fr, ln, rl, ln.lj, 0), ls2 = dim_value<FX>(fr, ln, rl, ln.lj, 1);
+            ln.bs1 = dim_value<FX>(fr, ln, rb, ln.lj, 0); ln.bs2 = dim_value<FX>(fr, ln, rb, ln.lj, 1);
+            ln.bcs = dim_value<FX>(fr, ln, rc, ln.lj, 0);
             estimate_direct_begin<EXT, DEFER>(sc, ln, ln.li, ls1, ls2);
             return;
         }
@@ -957,7 +962,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             ln.stage = ST_SPECULAR;
         } else {
             ln.Ld_light = ln.Ld_light + ln.Ld;
-            const int ns = RT_GPTR(const DimReq, fr.light_dims)[3 * ln.li].n;
+            const int ns = FX::all_n1 ? 1 : int(RT_GPTR(const DimReq, fr.light_dims)[3 * ln.li].n);
             if (++ln.lj >= ns) {
                 ln.L_all = ln.L_all + ln.Ld_light * (1.f / float(ns));           // L += Ld / nSamples
                 ln.lj = 0; ++ln.li;
@@ -974,8 +979,8 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         const int k = ln.depth;
         float bs1, bs2, bcs;
         if (k < 3) {
-            bs1 = dim_value(fr, ln, fr.two_d[3 * k + 2], 0, 0); bs2 = dim_value(fr, ln, fr.two_d[3 * k + 2], 0, 1);
-            bcs = dim_value(fr, ln, fr.one_d[3 * k + 2], 0, 0);
+            bs1 = dim_value<FX>(fr, ln, fr.two_d[3 * k + 2], 0, 0); bs2 = dim_value<FX>(fr, ln, fr.two_d[3 * k + 2], 0, 1);
+            bcs = dim_value<FX>(fr, ln, fr.one_d[3 * k + 2], 0, 0);
         } else { bs1 = ln.rng.next_float(); bs2 = ln.rng.next_float(); bcs = ln.rng.next_float(); }
         V3 wi; float pdf; int flags;
         V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, bs1, bs2, bcs, pdf, BX_ALL, flags);
@@ -1111,10 +1116,10 @@ RT_DEV void byv_ray_advance(const DevScene &sc, Lane &ln, unsigned *c_closest, u
     if (ACCEL == RT_ACCEL_GRID) grid_begin(ln.tv, sc, r, false); else trav_begin(ln.tv, sc, r, false);
 }
 // one pass: every lane without a ray finishes its previous vertex and runs its next one up to its rays (or ends the path: ST_FETCH)
-template <bool COUNT, int ACCEL, bool EXT>
+template <bool COUNT, int ACCEL, bool EXT, class FX = fixed::Any>
 RT_DEV void advance_pass_byv(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid, unsigned *c_closest, unsigned *c_any, unsigned *c_bad) {
     constexpr int INTEG = RT_INTEGRATOR_PATH;
-#define RT_BV_BODY(S) stage_body<COUNT, INTEG, false, EXT, S, true>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
+#define RT_BV_BODY(S) stage_body<COUNT, INTEG, false, EXT, S, true, false, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
     const int nLights = int(sc.n_lights);
     if (!ln.has_ray && (ln.stage == ST_VERTEX || ln.stage == ST_ED_DONE)) {
         byv_ray_result<COUNT, EXT>(sc, ln, c_closest, c_any);          // the vertex's last ray (the earlier ones were read when the next ray started)
@@ -1183,16 +1188,16 @@ RT_DEV bool stage_in_phase(int stage, int phase) {
 }
 // PARK (queue pipeline with a medium): only the head of a ray march is run here (march_begin) -- the lane then sits in ST_VOL_STEP without a ray
 // and its steps are run by rt::pipe_march_kernel (rt_pipe_march.h), which hands it back in ST_POP.
-template <bool COUNT, int INTEG_, bool VOL, bool EXT, bool DEFER = false, bool PARK = false>
+template <bool COUNT, int INTEG_, bool VOL, bool EXT, bool DEFER = false, bool PARK = false, class FX = fixed::Any>
 RT_DEV void advance_pass(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid,
                          unsigned *c_closest, unsigned *c_any, unsigned *c_bad, int phase) {
     constexpr int INTEG = INTEG_ == RT_INTEG_DIRECT_WEIGHTED ? int(RT_INTEGRATOR_DIRECT) : INTEG_;
 #ifdef RT_PROFILE_STAGES
 #define RT_RUN(S) { const unsigned long long m_ = __ballot(!ln.has_ray && ln.stage == S); if (m_) { const unsigned long long t_ = __builtin_readcyclecounter(); \
-        if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK>(sc, fr, ln, gtid, c_closest, c_any, c_bad); \
+        if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad); \
         if (__lane_id() == 0) { atomicAdd(fr.counters + 24 + 2 * S, __builtin_readcyclecounter() - t_); atomicAdd(fr.counters + 24 + 2 * S + 1, (unsigned long long)__popcll(m_) | (1ull << 40)); } } }
 #else
-#define RT_RUN(S) if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
+#define RT_RUN(S) if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
 #endif
     if constexpr (INTEG_ == RT_INTEGRATOR_DEBUG) {            // one camera ray per sample: its hit data, then Scene::Li's medium and the sample record
         RT_RUN(ST_VERTEX);

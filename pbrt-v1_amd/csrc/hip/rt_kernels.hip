@@ -216,9 +216,16 @@ static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
 static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
     const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
-    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
-    const unsigned grid = debug ? s->grids.debug[k] : s->grids.mega[rd->integrator][k];
-    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : (*g_render_kernels[rd->integrator])[k];
+    // A frame whose sampler, camera, work order and sample requests are what fixed::Frame states takes the twin compiled for them (rt_fixed_frame.h);
+    // PBRT_HIP_FIXED_FRAME=0 keeps it on the generic kernel (the films are the same bits: tests/test_gpu_fixed_frame.py)
+    bool fixed_frame = fixed::qualifies(fixed::Facts{rd->integrator, fr.sampler, rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED,
+                                                     s->dev.cam.lens_radius, s->dev.cam.type, fr.shard_count, fr.mega_tile, fr.dims_max_n,
+                                                     s->counting, s->has_ext, s->volume.present != 0, fr.high_occupancy != 0});
+    if (const char *e = knob("PBRT_HIP_FIXED_FRAME")) fixed_frame = fixed_frame && std::atoi(e) != 0;
+    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : fixed_frame ? flavour::Fixed::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
+    const unsigned grid = debug ? s->grids.debug[k] : fixed_frame ? s->grids.fixed[k] : s->grids.mega[rd->integrator][k];
+    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : fixed_frame ? g_render_kernels_fixed[k] : (*g_render_kernels[rd->integrator])[k];
+    s->last_fixed = fixed_frame;
     if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
 #ifdef RT_TAIL_PROBE
     static unsigned long long *probe = nullptr;
@@ -620,7 +627,7 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
     const int k = flavour::Trace::index(rq);
     HIPWARN(hipEventRecord(s->ev0, s->stream));
     hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
-    HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream)); s->have_timing = true; s->last_pipeline = false;
+    HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream)); s->have_timing = true; s->last_pipeline = false; s->last_fixed = false;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host.data(), s->trace_buf + 2 * size_t(n), size_t(n) * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
@@ -732,6 +739,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (debug) { rc = upload_tex_uv(s); if (rc) return rc; }    // dg.u / dg.v of a mesh with "uv": on the device from the first debug frame on
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
     s->rendered = true;
+    s->last_fixed = false;                                     // (render_mega sets it)
     // ---- the frame, by one of the four launch functions
     rc = fr.pipeline ? render_pipeline(s, rd, fr) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr);
     if (rc) return rc;
@@ -826,6 +834,7 @@ int rt_last_render_stats(RtScene *s, RtRenderStats *out) {
         out->slots = s->pipe_slots;
     } else out->trace_ms = out->render_ms;
     out->bands = s->last_pipeline ? 0 : 1;
+    out->fixed_frame = s->last_fixed ? 1 : 0;
     if (s->last_weighted) {
         out->weighted_points = s->wt_points;
         hipEvent_t seq[6] = {s->ev0, s->wt_ev[0], s->wt_ev[1], s->wt_ev[2], s->wt_ev[3], s->ev1};

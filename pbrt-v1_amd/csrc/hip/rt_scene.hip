@@ -546,6 +546,12 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     };
     ResidentGrids &g = s->grids;
     for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) if ((rc = resident(*g_render_kernels[i], g.mega[i]))) return rc;
+    {   // a fixed kernel shares its generic twin's scratch (n_threads, the spill area): never a larger grid than the twin's
+        const unsigned others = mx;
+        if ((rc = resident(g_render_kernels_fixed, g.fixed))) return rc;
+        for (int k = 0; k < flavour::Fixed::N; ++k) g.fixed[k] = std::min(g.fixed[k], g.mega[flavour::Fixed::integrator(k)][flavour::Fixed::generic(k)]);
+        mx = others;
+    }
     if ((rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir))) return rc;
     s->grid = mx;                                               // ... of the megakernels
     {   // the debug integrator's kernels need fewer registers than any of those: their grids stop at the largest of the others, so that the scratch
