@@ -16,13 +16,9 @@
 
 namespace rt {
 
-#define RT_BD_MAX_VERTS 4
 #define RT_BD_WORDS 21                    // floats of one stored vertex: p, nn, sn, ng, wi, wo, material, bsdfWeight, rrWeight
 #define RT_BD_FRAME_WORDS (2 * RT_BD_MAX_VERTS * RT_BD_WORDS)
-// RequestSamples (bidirectional.cpp:65-79) in HBM, where DirectLighting "all" keeps its per-light requests (DevFrame::light_dims, idle for this integrator):
-// for vertex i the 1-D requests eyeBSDFComp, lightBSDFComp, directLightNum, directBSDFComp at one_d[4 i ..] and the 2-D requests eyeBSDF, lightBSDF,
-// directLight, directBSDF at two_d[4 i ..], then lightNum (one_d[16]), lightPos and lightDir (two_d[16], [17]); and the world's bounding sphere
-struct BidirTable { DimReq one_d[4 * RT_BD_MAX_VERTS + 1], two_d[4 * RT_BD_MAX_VERTS + 2]; float wc[3], wr; };
+// (RT_BD_MAX_VERTS and the BidirTable the host packs the integrator's sample requests into: rt_frame_plan.h)
 
 struct BidirVertex { Vertex v; V3 wnext; float bsdfWeight, rrWeight; };      // v.wo is the reference's `wi` (towards the previous vertex), wnext its `wo`
 

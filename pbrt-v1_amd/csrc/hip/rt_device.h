@@ -2,6 +2,7 @@
 #pragma once
 #include "rt_math.h"
 #include "rt_fastdiv.h"
+#include "rt_frame_plan.h"       // DimReq, RT_MAX_DIM_REQ, BidirTable: the request tables the host plans
 #include "../../../include/pbrt_hip.h"
 #include "../../../include/pbrt_hip_texture.h"
 
@@ -55,10 +56,6 @@ struct DevLight {
     float l2w[9], l2w_scale;
     // RT_LIGHT_INFINITE (infinite.cpp, constant radiance): color = L, n_samples; nothing else is read
 };
-
-#define RT_MAX_DIM_REQ 12         // requests the frame descriptor itself carries (PathIntegrator: 11 one-dimensional, 9 two-dimensional); DirectLighting "all"
-                                  // has three per light, without bound (directlighting.cpp:39-66): DevFrame::light_dims
-struct DimReq { unsigned f_base, u_base; unsigned short n; unsigned short dims; };
 
 struct DevScene {
     const DevTri *tris;
@@ -139,7 +136,7 @@ struct DevFrame {
     int pipeline;                // host-side choice: the queue pipeline (rt_pipeline.h) instead of the megakernel (not read by the device)
     unsigned long long total_work;     // samples this shard renders
     unsigned long long total_pixels;   // pixels in the sample extent
-    FrameDiv div;                      // multipliers and shifts for the frame-constant divisors of the work fetch (rt_fastdiv.h; make_frame fills them last)
+    FrameDiv div;                      // multipliers and shifts for the frame-constant divisors of the work fetch (rt_fastdiv.h; made with the work extent: bind_extent, rt_kernels.hip)
     // sampler dimension table (Sample::oneD/twoD, sampling.cpp:41-70)
     int n1d, n2d;
     unsigned lhs_total;          // draws consumed by LatinHypercube per sample

@@ -1,7 +1,7 @@
 // rt_fastdiv.h -- exact unsigned 32-bit division by a frame constant without a divide instruction (no HIP header: tests/fastdiv_host_test.cpp
 // runs it on the host).  gfx950 has no integer divider: `n / d` with a run-time d expands to ~25 VALU instructions around a float reciprocal, and the
 // work fetch of the megakernel divides by frame constants half a dozen times per camera sample.  The host finds, once per frame, a multiplier and two
-// shifts per divisor (make_frame, rt_kernels.hip); the device then needs one multiply-high, a subtract, an add and two shifts.
+// shifts per divisor (make_frame's bind_extent, rt_kernels.hip); the device then needs one multiply-high, a subtract, an add and two shifts.
 //
 // The form is the round-up multiplier with the add-and-shift fix-up (Granlund & Montgomery, "Division by Invariant Integers using Multiplication",
 // PLDI 1994, figure 4.1): with l = ceil(log2 d), m = floor(2^32 * (2^l - d) / d) + 1 -- the low 32 bits of the 33-bit multiplier ceil(2^(32+l) / d) --

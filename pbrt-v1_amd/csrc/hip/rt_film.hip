@@ -6,7 +6,7 @@ namespace rt {
 
 // Which of this shard's local pixels (work index / spp, rt_integrate.h work_to_sample) is sample pixel (sx, sy) of the sample extent, and
 // does this shard render it at all?  1-D tiles are tile_pixels consecutive scanline pixels dealt round-robin to the shards, 2-D tiles
-// tile_w x tile_h blocks; the whole frame holds < 2^32 camera samples (make_frame), so 32-bit divisions do.
+// tile_w x tile_h blocks; the whole frame holds < 2^32 camera samples (plan_extent, rt_frame_plan.h), so 32-bit divisions do.
 __device__ inline void gather_local_pixel(const DevFrame &fr, int sx, int sy, bool &mine, unsigned long long &lp) {
     const unsigned px = unsigned(sx - fr.x_start), py = unsigned(sy - fr.y_start);
     if (fr.tile_w > 0) {

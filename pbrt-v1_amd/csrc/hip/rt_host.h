@@ -1,6 +1,6 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
 // the owners of its device memory, events and stream, the kernel tables and their resident grids (rt_flavour.h).  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
-// rt_kernels.hip renders (make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
+// rt_kernels.hip renders (make_frame binds what rt_frame_plan.h plans, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
 // memory (rt_trace_*_device, rt_hit_geometry_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
 #include "rt_flavour.h"
@@ -93,9 +93,7 @@ struct RtScene {
     std::vector<Event> pipe_fence;
     KdTree tree;
     GridAccelData gridacc;
-    int accel_kind = RT_ACCEL_KDTREE;
-    double per_leaf = -1.0;             // average primitives per non-empty kd leaf (traversal heuristics), computed on first use
-    bool has_ext = false;               // plastic materials or quadrics present: use the kernels that carry that code (EXT)
+    plan::SceneFacts facts;             // what the frame planners read of the scene (rt_frame_plan.h): filled by scene_create and the setters that change a fact
     DevScene dev{};
     std::vector<DevBuf<char>> allocs;   // what was uploaded once and lives as long as the scene (scene_alloc)
     // film
@@ -107,12 +105,11 @@ struct RtScene {
     DevBuf<float> frames;
     unsigned grid = 0, n_threads = 0;
     ResidentGrids grids{};             // grid: the largest of the megakernel families, n_threads: of all
-    DevBuf<DimReq> light_dims;         // DirectLighting "all": the per-light sample requests (make_frame); the bidirectional integrator: its BidirTable
+    DevBuf<DimReq> light_dims;         // DirectLighting "all": the per-light sample requests (plan_requests, rt_frame_plan.h; make_frame uploads them); the bidirectional integrator: its BidirTable
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
     DevBuf<unsigned> wt_recbase;
     unsigned n_infinite = 0;           // RT_LIGHT_INFINITE lights (each estimate draws one RandomFloat(), infinite.cpp:104: refused with strategy "weighted")
-    int light_draws = 0;               // RandomFloat()s one EstimateDirect draws: the same for every light (0 / 1), or -1 when the lights differ
     DevBuf<unsigned> wt_base; DevBuf<float> wt_rec; DevBuf<float2> wt_pick;
     DevBuf<unsigned long long> wt_sums;                        // per-block sums of the point-count scan
     Pinned<unsigned long long> wt_total;                       // page-locked: the frame's shading points (weighted_scan_top_kernel)
@@ -124,8 +121,6 @@ struct RtScene {
     DevBuf<float> resolve_buf;
     DevBuf<float> vol_buf;                                 // volume scratch: rays | state | samp
     RtVolume volume{};
-    int density_kind = RT_DENSITY_NONE;                    // rt_scene_set_density
-    double vol_world[6] = {0, 0, 0, 0, 0, 0};             // density region: the volume's world bound (WorldToVolume^-1 of its extent)
     bool rendered = false;                                 // an rt_render has been accepted
     // textured materials (rt_scene_set_textures): the scene's own resolved records (host copy) and the device array that holds them followed by
     // the records for the materials resolved per hit (rt_texture.h); dev.materials points at it once the scene has textures
@@ -136,7 +131,6 @@ struct RtScene {
     DevBuf<DevMaterial> mat_buf;
     int spill_depth = 0;
     bool have_timing = false;
-    bool counting = true;
     uint32_t n_tris = 0;
     // queue pipeline (rt_pipeline.h)
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;

@@ -233,7 +233,7 @@ RT_DEV bool work_to_sample(const DevFrame &fr, unsigned long long w, unsigned lo
     // every frame of practical size has fewer than 2^32 samples: 32-bit divisions (a 64-bit division is ~150 VALU instructions
     // on gfx950, and this runs in the sparsely populated fetch path)
     if (fr.tile_w > 0) {                                    // 2-D tiles: a tile is a tile_w x tile_h block of the sample extent; the pixels of
-        // the border tiles that fall off the extent are skipped.  make_frame guarantees n_tiles * tile_pixels * spp < 2^32: all 32-bit
+        // the border tiles that fall off the extent are skipped.  plan_extent (rt_frame_plan.h) guarantees n_tiles * tile_pixels * spp < 2^32: all 32-bit
         const unsigned w32 = unsigned(w), pt = unsigned(per_tile);
         const unsigned lt = fastdiv(w32, fr.div.per_tile), rem = w32 - lt * pt;
         const unsigned tile = lt * unsigned(fr.shard_count) + unsigned(fr.shard_index);

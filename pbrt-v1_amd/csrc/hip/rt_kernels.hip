@@ -1,4 +1,4 @@
-// rt_kernels.hip -- the render path of libpbrt_hip.so's C ABI (include/pbrt_hip.h): make_frame, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*.
+// rt_kernels.hip -- the render path of libpbrt_hip.so's C ABI (include/pbrt_hip.h): make_frame (the binder of what rt_frame_plan.h plans), the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*.
 // (Scene create: rt_scene.hip.  Film kernels and rt_film_*: rt_film.hip.  Shared host declarations: rt_host.h.  Which kernel instantiation: rt_flavour.h.)
 //
 // Kernels
@@ -87,17 +87,15 @@ static int bind_scratch(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, size_t
 
 // What a frame asks of the kernel tables (rt_flavour.h: each family's index() turns it into the entry to launch); rt_trace_* have no frame
 static flavour::Request request_of(const RtScene *s, const RtRenderDesc *rd = nullptr, const DevFrame *fr = nullptr) {
-    return flavour::Request{rd ? rd->integrator : 0, s->accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->counting, s->has_ext, fr && fr->high_occupancy};
+    return flavour::Request{rd ? rd->integrator : 0, s->facts.accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->facts.counting, s->facts.has_ext, fr && fr->high_occupancy};
 }
 
 // The queue pipeline: alternate a shade kernel (pipe_shade_kernel, or pipe_vertex_kernel for a path without a medium) and pipe_trace_kernel
 // until a shade pass enqueues no ray.  The host learns the queue sizes RT_PIPE_BATCH iterations late (page-locked copy + fence event per
 // batch), so the GPU never waits for it; the iterations launched after the last productive one find every slot in ST_EXIT and return at once.
-static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Schedule &sc, const plan::FrameKnobs &kn) {
     const int integ = rd->integrator;
-    // PathIntegrator without a medium: one shade pass per path vertex, all of a vertex's rays in one trace launch (rt_pipe_vertex.h)
-    bool by_vertex = integ == RT_INTEGRATOR_PATH && !s->volume.present;
-    if (const char *e = knob("PBRT_HIP_PIPE_VERTEX")) by_vertex = by_vertex && std::atoi(e) != 0;
+    const bool by_vertex = sc.by_vertex;          // PathIntegrator without a medium: one shade pass per path vertex (plan_schedule)
     // ---- pool size: 32 M slots with a medium, 8 M without, unless the frame is smaller or the per-slot scratch would not fit (a fine ray march: 3 floats per step)
     const ScratchWords w = scratch_words(s, rd, fr);
     size_t slot_bytes = (w.frame + w.vol) * 4 + (s->has_textures ? w.mat_levels * sizeof(DevMaterial) : 0);   // ... and the materials resolved per hit
@@ -110,10 +108,10 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
         size_t budget = (free_b + held) / 2;                                      // leave half of what is free to the caller (film, other scenes)
-        if (const char *e = knob("PBRT_HIP_PIPE_MEM_MB")) budget = size_t(std::max(1, std::atoi(e))) << 20;      // tests: a small budget
+        if (kn.pipe_mem_mb) budget = size_t(std::max(1, *kn.pipe_mem_mb)) << 20;      // tests: a small budget
         if (slot_bytes * want > budget) want = unsigned(std::max<size_t>(budget / slot_bytes, 2 * RT_BLOCK));
     }
-    if (const char *e = knob("PBRT_HIP_PIPE_SLOTS")) want = unsigned(std::max(256, std::atoi(e)));
+    if (kn.pipe_slots) want = unsigned(std::max(256, *kn.pipe_slots));
     unsigned long long tw = fr.total_work ? fr.total_work : 1;
     unsigned n_slots = unsigned(std::min<unsigned long long>(want, tw));
     n_slots = (n_slots + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK;
@@ -213,15 +211,10 @@ static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
 }
 
 // The megakernel of Whitted, DirectLighting "all" / "one", Path and the debug integrator (a table of its own, flavour::Debug): one launch of rt::render_kernel
-static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Schedule &sc) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
     const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
-    // A frame whose sampler, camera, work order and sample requests are what fixed::Frame states takes the twin compiled for them (rt_fixed_frame.h);
-    // PBRT_HIP_FIXED_FRAME=0 keeps it on the generic kernel (the films are the same bits: tests/test_gpu_fixed_frame.py)
-    bool fixed_frame = fixed::qualifies(fixed::Facts{rd->integrator, fr.sampler, rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED,
-                                                     s->dev.cam.lens_radius, s->dev.cam.type, fr.shard_count, fr.mega_tile, fr.dims_max_n,
-                                                     s->counting, s->has_ext, s->volume.present != 0, fr.high_occupancy != 0});
-    if (const char *e = knob("PBRT_HIP_FIXED_FRAME")) fixed_frame = fixed_frame && std::atoi(e) != 0;
+    const bool fixed_frame = sc.fixed_frame;      // the twin compiled for a fixed frame (rt_fixed_frame.h), where plan_schedule found that the frame qualifies
     const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : fixed_frame ? flavour::Fixed::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
     const unsigned grid = debug ? s->grids.debug[k] : fixed_frame ? s->grids.fixed[k] : s->grids.mega[rd->integrator][k];
     const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : fixed_frame ? g_render_kernels_fixed[k] : (*g_render_kernels[rd->integrator])[k];
@@ -303,7 +296,7 @@ static int render_weighted(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     auto late_fail = [&](int code, const char *msg) { s->last_weighted = false; s->last_pipeline = false; s->have_timing = false; s->wt_points = 0; return fail(code, msg); };
     if (n_points >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 shading points in the frame");
     s->wt_points = n_points;
-    const bool mixed = s->light_draws < 0;
+    const bool mixed = s->facts.light_draws < 0;
     const int nD = int(s->n_drawing_lights);
     size_t rec_floats = size_t(n_points) * size_t(R);
     fr.wt_mixed = mixed ? 1 : 0; fr.wt_nd = unsigned(nD); fr.wt_recbase = nullptr;
@@ -372,197 +365,76 @@ int rt_device_count(int *count) {
     if (e != hipSuccess) { *count = 0; return fail(RT_EDEVICE, std::string("hipGetDeviceCount: ") + hipGetErrorString(e)); }
     *count = n; return RT_OK;
 }
-// Build the per-frame device descriptor: film geometry + the Sample layout the integrators request
-// (Sample::Sample sampling.cpp:41-70; RequestSamples of directlighting.cpp:39-66, path.cpp:47-57,
-// emission.cpp:42-46 / single.cpp:43-47; LatinHypercube draw counts sampling.cpp:98-113).
-static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool need_film) {
-    auto round_up_pow2 = [](unsigned v) { v--; v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16; return v + 1; };   // pbrt.h:590-598
-    if (rd->sampler < RT_SAMPLER_STRATIFIED || rd->sampler > RT_SAMPLER_RANDOM) return fail(RT_EINVAL, "unknown sampler");
-    if (rd->sampler == RT_SAMPLER_LOWDISCREPANCY) { if (rd->pixel_samples < 1) return fail(RT_EINVAL, "bad pixelsamples"); }
-    else if (rd->x_samples < 1 || rd->y_samples < 1) return fail(RT_EINVAL, "bad xsamples/ysamples");
+// The PBRT_HIP_* knobs of the render path as values (rt_frame_plan.h FrameKnobs), read through knob(), so that PBRT_HIP_TUNE gates them: the one
+// place in this file that names them
+static plan::FrameKnobs frame_knobs() {
+    auto num = [](const char *name) -> std::optional<int> { const char *e = knob(name); return e ? std::optional<int>(std::atoi(e)) : std::nullopt; };
+    plan::FrameKnobs k;
+    k.high_occ = num("PBRT_HIP_HIGH_OCC"); k.leaf_min = num("PBRT_HIP_LEAF_MIN"); k.trav_mode = num("PBRT_HIP_TRAV_MODE");
+    k.xcd_bands = num("PBRT_HIP_XCD_BANDS"); k.exit_thresh = num("PBRT_HIP_EXIT_THRESH"); k.phase_sync = num("PBRT_HIP_PHASE_SYNC");
+    k.pipeline = num("PBRT_HIP_PIPELINE"); k.mega_tile = num("PBRT_HIP_MEGA_TILE"); k.fixed_frame = num("PBRT_HIP_FIXED_FRAME");
+    k.pipe_vertex = num("PBRT_HIP_PIPE_VERTEX"); k.pipe_mem_mb = num("PBRT_HIP_PIPE_MEM_MB"); k.pipe_slots = num("PBRT_HIP_PIPE_SLOTS");
+    k.debug_nofilm = num("PBRT_HIP_DEBUG_NOFILM");
+    if (const char *e = knob("PBRT_HIP_DEBUG_PIXEL")) std::sscanf(e, "%d,%d", &k.dbg_x, &k.dbg_y);
+    return k;
+}
+
+// The descriptor's sampler, film window and work extent, with the divisors of the work fetch (rt_fastdiv.h; they are these frame constants only, and
+// nothing in make_frame or rt_render changes one of them afterwards): all a camera ray needs (camera_frame), and where make_frame starts
+static void bind_extent(const RtRenderDesc *rd, const plan::Extent &e, int mega_tile, DevFrame &fr) {
     std::memset(&fr, 0, sizeof fr);
     fr.integrator = rd->integrator; fr.max_depth = rd->max_depth; fr.strategy = rd->strategy;
     fr.volume_integrator = rd->volume_integrator; fr.step_size = rd->step_size;
     fr.sampler = rd->sampler; fr.xs = rd->x_samples; fr.ys = rd->y_samples; fr.jitter = rd->jitter;
-    fr.spp = rd->sampler == RT_SAMPLER_LOWDISCREPANCY ? int(round_up_pow2(unsigned(rd->pixel_samples))) : rd->x_samples * rd->y_samples;
+    fr.spp = e.spp;
     fr.seed = rd->seed;
     fr.x_pixel_start = rd->x_pixel_start; fr.y_pixel_start = rd->y_pixel_start;
     fr.x_pixel_count = rd->x_pixel_count; fr.y_pixel_count = rd->y_pixel_count;
     fr.x_start = rd->x_start; fr.x_end = rd->x_end; fr.y_start = rd->y_start; fr.y_end = rd->y_end;
-    if (fr.x_end <= fr.x_start || fr.y_end <= fr.y_start) return fail(RT_EINVAL, "empty sample extent");
     fr.fxw = rd->filter_x_width; fr.fyw = rd->filter_y_width;
     fr.inv_fxw = 1.f / fr.fxw; fr.inv_fyw = 1.f / fr.fyw;
-    fr.filter_table = s->filter_dev; fr.accum = s->accum;
-    fr.shard_index = rd->shard_index; fr.shard_count = rd->shard_count < 1 ? 1 : rd->shard_count;
-    fr.tile_pixels = rd->tile_pixels < 1 ? 1 : rd->tile_pixels;
-    if (fr.shard_index < 0 || fr.shard_index >= fr.shard_count) return fail(RT_EINVAL, "bad shard index");
-    fr.total_pixels = (unsigned long long)(fr.x_end - fr.x_start) * (unsigned long long)(fr.y_end - fr.y_start);
-    if (fr.total_pixels * fr.spp > 0xFFFFFFFFull) return fail(RT_EINVAL, "more than 2^32 camera samples per frame");
-    unsigned long long n_tiles = 0;
-    if (rd->tile_pixels < 0) {                               // 2-D tiles: width in the low 16 bits of -tile_pixels, height above (pbrt_hip.h)
-        const int tw = (-rd->tile_pixels) & 0xffff, th = (-rd->tile_pixels) >> 16;
-        if (tw < 1 || th < 1 || tw > 4096 || th > 4096) return fail(RT_EINVAL, "bad 2-D tile size");
-        fr.tile_w = tw; fr.tile_h = th; fr.tile_pixels = tw * th;
-        fr.tiles_x = (fr.x_end - fr.x_start + tw - 1) / tw;
-        n_tiles = (unsigned long long)fr.tiles_x * (unsigned long long)((fr.y_end - fr.y_start + th - 1) / th);
-        if (n_tiles * fr.tile_pixels * fr.spp > 0xFFFFFFFFull) return fail(RT_EINVAL, "more than 2^32 camera samples per frame (2-D tiles, border tiles included)");
-    } else n_tiles = (fr.total_pixels + fr.tile_pixels - 1) / fr.tile_pixels;
-    const unsigned long long my_tiles = n_tiles > (unsigned long long)fr.shard_index
-        ? (n_tiles - fr.shard_index + fr.shard_count - 1) / fr.shard_count : 0;
-    fr.total_work = my_tiles * fr.tile_pixels * fr.spp;
+    fr.shard_index = e.shard_index; fr.shard_count = e.shard_count; fr.tile_pixels = e.tile_pixels;
+    fr.tile_w = e.tile_w; fr.tile_h = e.tile_h; fr.tiles_x = e.tiles_x;
+    fr.total_pixels = e.total_pixels; fr.total_work = e.total_work;
+    fr.mega_tile = mega_tile;
+    fr.div = framediv_make(unsigned(fr.spp), unsigned(fr.xs), unsigned(fr.x_end - fr.x_start), unsigned(fr.y_end - fr.y_start), unsigned(fr.mega_tile),
+                           (unsigned long long)fr.tile_pixels * fr.spp, unsigned(fr.tile_w), unsigned(fr.tiles_x));
+}
 
-    // sample layout
-    std::vector<int> n1, n2;
-    const int nl = int(s->dev.n_lights);
-    if (rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_ALL) {
-        std::vector<DevLight> lights(nl);
-        if (nl) HIPCHK(hipMemcpy(lights.data(), s->dev.lights, nl * sizeof(DevLight), hipMemcpyDeviceToHost));
-        for (int i = 0; i < nl; ++i) { int ns = lights[i].n_samples; if (rd->sampler == RT_SAMPLER_LOWDISCREPANCY) ns = int(round_up_pow2(unsigned(ns)));   // Sampler::RoundSize
-            if (ns > 65535) return fail(RT_EINVAL, "rt_render: more than 65535 samples per light (the sample table holds counts in 16 bits)");
-            n2.push_back(ns); n2.push_back(ns); n1.push_back(ns); }
-    } else if (rd->integrator == RT_INTEGRATOR_DIRECT) { n2 = {1, 1}; n1 = {1, 1}; }
-    else if (rd->integrator == RT_INTEGRATOR_PATH) { n1.assign(9, 1); n2.assign(9, 1); }
-    else if (rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL) { n1.assign(4 * RT_BD_MAX_VERTS + 1, 1); n2.assign(4 * RT_BD_MAX_VERTS + 2, 1); }     // bidirectional.cpp:65-79
-    else if (rd->integrator != RT_INTEGRATOR_WHITTED && rd->integrator != RT_INTEGRATOR_DEBUG) return fail(RT_EINVAL, "unknown integrator");     // (neither requests samples)
-    n1.push_back(1); n1.push_back(1);                   // the volume integrator's tau / scatter samples
-    // The requests in the reference's order (every 1-D request, then every 2-D one: Sample::Sample sampling.cpp:41-70).  DirectLighting "all" asks for
-    // 2 x 2-D and 1 x 1-D per light WITHOUT bound (directlighting.cpp:39-66): its per-light requests go to a table in HBM (DevFrame::light_dims, three
-    // records per light, indexed by the lane's light cursor); the frame descriptor itself carries the bounded rest.
-    const bool all_lights = rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_ALL;
-    std::vector<DimReq> d1(n1.size()), d2(n2.size());
-    unsigned c = 0;
-    const unsigned P = unsigned(fr.spp);
-    if (rd->sampler == RT_SAMPLER_STRATIFIED) {             // LatinHypercube: n*d floats then n*d shuffles per request
-        for (size_t i = 0; i < n1.size(); ++i) { d1[i] = DimReq{c, c + unsigned(n1[i]), (unsigned short)n1[i], 1}; c += 2u * n1[i]; }
-        for (size_t i = 0; i < n2.size(); ++i) { d2[i] = DimReq{c, c + 2u * n2[i], (unsigned short)n2[i], 2}; c += 4u * n2[i]; }
-        fr.lhs_total = c;
-        fr.pixgen_draws = fr.jitter ? 7u * P : 2u * P;      // stratified.cpp:99-117
-    } else if (rd->sampler == RT_SAMPLER_RANDOM) {          // one float per value (random.cpp:107-112)
-        for (size_t i = 0; i < n1.size(); ++i) { d1[i] = DimReq{c, 0, (unsigned short)n1[i], 1}; c += unsigned(n1[i]); }
-        for (size_t i = 0; i < n2.size(); ++i) { d2[i] = DimReq{c, 0, (unsigned short)n2[i], 2}; c += 2u * n2[i]; }
-        fr.lhs_total = c;
-        fr.pixgen_draws = 5u * P;                           // random.cpp:88-92
-    } else {                                                // per-pixel tables (lowdiscrepancy.cpp:93-104, sampling.h:152-174)
-        c = (2 + 2 * P) + (2 + 2 * P) + (1 + 2 * P);        // image, lens, time blocks
-        for (size_t i = 0; i < n1.size(); ++i) { d1[i] = DimReq{c, 0, (unsigned short)n1[i], 1}; c += 1u + unsigned(n1[i]) * P + P; }
-        for (size_t i = 0; i < n2.size(); ++i) { d2[i] = DimReq{c, 0, (unsigned short)n2[i], 2}; c += 2u + unsigned(n2[i]) * P + P; }
-        fr.lhs_total = 0;
-        fr.pixgen_draws = c;
-    }
-    {   // the draws of one camera sample are addressed by a 32-bit counter: the tables above must fit well inside it
-        unsigned long long draws = 0;
-        for (int n : n1) draws += 2ull * unsigned(n) * (P + 1);
-        for (int n : n2) draws += 4ull * unsigned(n) * (P + 1);
-        if (draws > 0x3fffffffull) return fail(RT_EINVAL, "rt_render: the lights' sample requests need more than 2^30 random numbers per camera sample");
-    }
-    fr.light_dims = nullptr;
-    fr.dims_max_n = 0;
-    for (const DimReq &r : d2) fr.dims_max_n = std::max(fr.dims_max_n, int(r.n));
-    const bool bidir = rd->integrator == RT_INTEGRATOR_BIDIRECTIONAL;
-    if (all_lights || bidir) {
-        std::vector<DimReq> tab;
-        if (all_lights) {
-            tab.assign(size_t(nl) * 3 + 1, DimReq{0, 0, 0, 0});
-            for (int i = 0; i < nl; ++i) { tab[3 * size_t(i)] = d2[2 * size_t(i)]; tab[3 * size_t(i) + 1] = d2[2 * size_t(i) + 1]; tab[3 * size_t(i) + 2] = d1[size_t(i)]; }
-        } else {
-            // the bidirectional integrator: its 17 + 18 requests (more than the descriptor's arrays hold) and the world's bounding sphere, one BidirTable
-            BidirTable bt; std::memset(&bt, 0, sizeof bt);
-            for (int i = 0; i < 4 * RT_BD_MAX_VERTS + 1; ++i) bt.one_d[i] = d1[size_t(i)];
-            for (int i = 0; i < 4 * RT_BD_MAX_VERTS + 2; ++i) bt.two_d[i] = d2[size_t(i)];
-            // Scene::WorldBound() (scene.cpp:114-119; a medium is refused, so it is the accelerator's bound) -> BBox::BoundingSphere (geometry.cpp:47-50)
-            const float *b = s->dev.bounds;
-            const float cx = .5f * b[0] + .5f * b[3], cy = .5f * b[1] + .5f * b[4], cz = .5f * b[2] + .5f * b[5];
-            const bool inside = cx >= b[0] && cx <= b[3] && cy >= b[1] && cy <= b[4] && cz >= b[2] && cz <= b[5];
-            const float dx = cx - b[3], dy = cy - b[4], dz = cz - b[5];
-            bt.wc[0] = cx; bt.wc[1] = cy; bt.wc[2] = cz; bt.wr = inside ? std::sqrt(dx * dx + dy * dy + dz * dz) : 0.f;
-            tab.assign((sizeof bt + sizeof(DimReq) - 1) / sizeof(DimReq), DimReq{0, 0, 0, 0});
-            std::memcpy(tab.data(), &bt, sizeof bt);
-        }
+// The frame of rt_camera_rays / rt_camera_rays_device: a camera ray depends on the sampler, the film and the camera, not on the integrator's sample
+// requests (setup_sample, rt_integrate.h), so no request table is planned, and nothing is copied or waited for
+static int camera_frame(const RtRenderDesc *rd, DevFrame &fr) {
+    plan::Extent ext;
+    if (plan::Refusal r = plan::plan_extent(*rd, ext)) return fail(r.code, r.msg);
+    bind_extent(rd, ext, 0, fr);
+    return RT_OK;
+}
+
+// Build the per-frame device descriptor: what rt_frame_plan.h plans for the frame (work extent, sample requests, schedule; `sc` keeps the host-side
+// choices), bound to the scene's device memory.
+static int make_frame(RtScene *s, const RtRenderDesc *rd, const plan::FrameKnobs &kn, DevFrame &fr, plan::Schedule &sc, bool need_film) {
+    plan::Extent ext; plan::Requests rq;
+    if (plan::Refusal r = plan::plan_extent(*rd, ext)) return fail(r.code, r.msg);
+    if (plan::Refusal r = plan::plan_requests(*rd, s->facts, ext.spp, rq)) return fail(r.code, r.msg);
+    sc = plan::plan_schedule(*rd, s->facts, ext, rq, kn);
+    bind_extent(rd, sc.extent, sc.mega_tile, fr);
+    fr.n1d = rq.n1d; fr.n2d = rq.n2d; fr.lhs_total = rq.lhs_total; fr.pixgen_draws = rq.pixgen_draws; fr.dims_max_n = rq.dims_max_n;
+    std::memcpy(fr.one_d, rq.one_d, sizeof fr.one_d); std::memcpy(fr.two_d, rq.two_d, sizeof fr.two_d);
+    fr.trav_mode = sc.trav_mode; fr.exit_thresh = sc.exit_thresh; fr.high_occupancy = sc.high_occupancy; fr.leaf_min = sc.leaf_min;
+    fr.xcd_bands = sc.xcd_bands; fr.phase_sync = sc.phase_sync; fr.pipeline = sc.pipeline; fr.dbg_x = sc.dbg_x; fr.dbg_y = sc.dbg_y;
+    if (!rq.table.empty()) {
         std::vector<DimReq> &up = s->light_dims_host;          // what the device holds: uploaded again only when a frame asks for other requests
-        if (!s->light_dims || up.size() != tab.size() || std::memcmp(up.data(), tab.data(), tab.size() * sizeof(DimReq)) != 0) {
-            int rc = ensure(s, s->light_dims, tab.size()); if (rc) return rc;
-            up.swap(tab);
+        if (!s->light_dims || up.size() != rq.table.size() || std::memcmp(up.data(), rq.table.data(), rq.table.size() * sizeof(DimReq)) != 0) {
+            int rc = ensure(s, s->light_dims, rq.table.size()); if (rc) return rc;
+            up.swap(rq.table);
             // rt_render is asynchronous: a frame queued earlier may still be reading the table, and the source is pageable host memory that the next make_frame
             // may swap away -- wait for the stream, then copy synchronously (36 bytes per light; only when a frame asks for other requests than the last one)
             HIPCHK(hipStreamSynchronize(s->stream));
             HIPCHK(hipMemcpy(s->light_dims, up.data(), up.size() * sizeof(DimReq), hipMemcpyHostToDevice));
         }
         fr.light_dims = s->light_dims;
-        d1.erase(d1.begin(), d1.begin() + (all_lights ? nl : 4 * RT_BD_MAX_VERTS + 1));     // what stays in the descriptor: the volume integrator's two 1-D requests
-        d2.clear();
     }
-    if (d1.size() > RT_MAX_DIM_REQ || d2.size() > RT_MAX_DIM_REQ) return fail(RT_ESTATE, "rt_render: sample table overflow");      // (cannot happen: 11 / 9 for the path integrator)
-    fr.n1d = int(d1.size()); fr.n2d = int(d2.size());
-    std::memset(fr.one_d, 0, sizeof fr.one_d); std::memset(fr.two_d, 0, sizeof fr.two_d);
-    for (size_t i = 0; i < d1.size(); ++i) fr.one_d[i] = d1[i];
-    for (size_t i = 0; i < d2.size(); ++i) fr.two_d[i] = d2[i];
-    // traversal scheduling knobs (performance only; results and counters do not depend on them)
-    {
-        const size_t nn = s->tree.nodes.size();
-        if (s->per_leaf < 0.0) {                              // once per scene: a pass over 36 M nodes costs 12 ms, not something to pay per frame
-            size_t leaves = 0, refs = 0;
-            if (s->accel_kind == RT_ACCEL_KDTREE) for (const Node &n : s->tree.nodes) if ((n.x & 3u) == 3u && (n.x >> 2)) { ++leaves; refs += n.x >> 2; }
-            s->per_leaf = leaves ? double(refs) / double(leaves) : 1.0;
-        }
-        const double per_leaf = s->per_leaf;
-        const bool tiny = nn <= 4096 && per_leaf >= 1.5;       // few fat leaves: triangle tests dominate -> lock-step rounds
-        const bool tiny_path = tiny && rd->integrator == RT_INTEGRATOR_PATH;
-        fr.trav_mode = (tiny && !tiny_path) ? 3 : 2;           // tiny trees, Whitted / DirectLighting: lock-step rounds with pooled leaf tests; else batched
-                                                               // rounds (measured best on 100k-1M triangle soups and, since the spill-free round-3 build,
-                                                               // for the path integrator on tiny trees too: profiles/r03_c2_knobs.txt)
-        // long divergent rays: let finished lanes refill early.  Tiny scenes: only with phase gating (path integrator), where 8
-        // measured +1.5 % (16: -13 %); Whitted / DirectLighting on Cornell lose 10 % with any early exit
-        fr.exit_thresh = tiny ? (rd->integrator == RT_INTEGRATOR_PATH ? 8 : 0) : 32;
-        // round 5, the path integrator by vertex (a lane comes back for shading once per vertex, not once per ray): 16 on tiny trees (C2's kernel 49.8 -> 48.5 ms;
-        // 24: 48.7, 32: 50.1), 32-40 alike on the 1 M-triangle frames (profiles/r05_by_vertex_scan.txt)
-        if (RT_MEGA_BYV && tiny && rd->integrator == RT_INTEGRATOR_PATH && !s->volume.present && !s->has_ext) fr.exit_thresh = 16;
-        fr.high_occupancy = (tiny && !tiny_path) ? 0 : 1;      // C2 (round 3): 4-wave flavour + batched rounds + exit threshold 8 = 54.0 ms, natural allocation + pooled lock-step 56.5
-        if (const char *e = knob("PBRT_HIP_HIGH_OCC")) fr.high_occupancy = std::atoi(e);
-        fr.leaf_min = tiny ? 8 : RT_TRACE_LEAF_MIN;          // C2: 50.8 ms at 8, 54.0 at 24 (few fat leaves: waiting for a fuller batch only idles lanes)
-        if (const char *e = knob("PBRT_HIP_LEAF_MIN")) fr.leaf_min = std::max(1, std::atoi(e));
-        if (const char *e = knob("PBRT_HIP_TRAV_MODE")) fr.trav_mode = std::atoi(e);
-        // XCD bands of the work list (rt_render_kernel.h): frames whose rays stay coherent (Whitted / DirectLighting: camera, shadow and specular rays)
-        // gain from each private L2 holding one band's lines -- C3 13.37 -> 12.62 ms; path frames, whose rays scatter after the first bounce, lose
-        // 5 % (1 M path 62.2 -> 65.5 ms, C4 64.1 -> 67.5; profiles/r04_xcd_bands_scan.txt)
-        fr.xcd_bands = rd->integrator != RT_INTEGRATOR_PATH ? 1 : 0;
-        if (const char *e = knob("PBRT_HIP_XCD_BANDS")) fr.xcd_bands = std::atoi(e) != 0;
-        if (const char *e = knob("PBRT_HIP_EXIT_THRESH")) fr.exit_thresh = std::atoi(e);
-        fr.dbg_x = fr.dbg_y = -1000000;
-        if (const char *e = knob("PBRT_HIP_DEBUG_PIXEL")) std::sscanf(e, "%d,%d", &fr.dbg_x, &fr.dbg_y);
-        fr.phase_sync = tiny ? 1 : 0;                          // C2: 63.6 vs 82.4 ms; 100k/1M soups (early-exit rounds): 8 % slower
-        if (const char *e = knob("PBRT_HIP_PHASE_SYNC")) fr.phase_sync = std::atoi(e);
-        // large trees (traversal bound by memory latency): the queue pipeline of rt_pipeline.h; tiny cache-resident ones: the megakernel
-        // (measured on the 1 M-triangle frames, 1x MI355X: the pipeline's trace kernel is faster than the megakernel's traversal, but its
-        // state traffic and sparse last iterations cost more than that gains, except where shading suspends often: volume marching)
-        // round 3: a path without a medium can take the by-vertex form (rt_pipe_vertex.h: 1 M-triangle frame 69.9 ms); since the kernels are
-        // built without the SLP vectorizer the 4-wave megakernel no longer spills and is as fast there (69.3 ms) and faster on C4's
-        // material mix (71.3 vs 76.3 ms), so it stays the default for frames without a medium
-        fr.pipeline = (!tiny && s->volume.present) ? 1 : 0;
-        if (const char *e = knob("PBRT_HIP_PIPELINE")) fr.pipeline = std::atoi(e) != 0;
-        if (fr.max_depth > 250 || fr.max_depth < 0) fr.pipeline = 0;     // the slot's control word holds depth in 8 bits
-        if (fr.dims_max_n >= 65535) fr.pipeline = 0;                     // ... and the light / sample cursors in 16 bits each
-        if (s->dev.n_lights >= 65535u) fr.pipeline = 0;
-        if (rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED) fr.pipeline = 0;    // three megakernel passes (rt_weighted.h)
-        if (bidir) { fr.pipeline = 0; fr.xcd_bands = 0; }   // rt::bidir_kernel (rt_bidir.h): a persistent kernel of its own, one work counter
-        if (rd->integrator == RT_INTEGRATOR_DEBUG) { fr.pipeline = 0; fr.high_occupancy = 0; }     // flavour::Debug: the megakernel, one kernel per (medium, accelerator, counting), whatever the knobs say
-        if (fr.shard_count == 1 && !fr.pipeline) {
-            // One shard: the tiles partition nothing, and the megakernel then renders the sample extent in scanline order.  2-D tiles pad the extent to
-            // whole tiles and every dropped padding item idles a lane for about a ray's time: 64 x 64 tiles cost C3 5 % of its frame
-            // (profiles/r03_work_order.txt).  The queue pipeline keeps the caller's tiles: with millions of paths in flight their compactness is
-            // worth more (C5: L2 misses 5.3 G per frame in 64 x 64 tiles, 6.3 G in scanline order; 328 vs 332 ms).
-            fr.tile_w = fr.tile_h = fr.tiles_x = 0; fr.tile_pixels = 1;
-            fr.total_work = fr.total_pixels * fr.spp;
-            // The counter hands the scanline-addressed samples out in 32 x 32-pixel blocks (clipped at the extent's edges: no padding, nothing dropped):
-            // C3's kernel 12.68 -> 12.18 ms on top of the XCD bands, the path frames and C2 unchanged (profiles/r04_mega_tile_scan.txt).
-            fr.mega_tile = 32;
-            if (const char *e = knob("PBRT_HIP_MEGA_TILE")) fr.mega_tile = std::max(0, std::atoi(e));
-            if (fr.mega_tile > 4096 || fr.total_work > 0xffffffffull) fr.mega_tile = 0;
-        }
-        if (fr.trav_mode != 3 || fr.high_occupancy) fr.trav_mode = 2;  // (the high-occupancy kernels carry no pooled-leaf scratch)
-    }
-    // the work fetch divides by these frame constants only (rt_fastdiv.h); nothing below or in rt_render changes one of them
-    fr.div = framediv_make(unsigned(fr.spp), unsigned(fr.xs), unsigned(fr.x_end - fr.x_start), unsigned(fr.y_end - fr.y_start), unsigned(fr.mega_tile),
-                           (unsigned long long)fr.tile_pixels * fr.spp, unsigned(fr.tile_w), unsigned(fr.tiles_x));
+    fr.filter_table = s->filter_dev; fr.accum = s->accum;
     fr.work_counter = s->work_counter; fr.counters = s->counters; fr.spill = s->spill; fr.n_threads = s->n_threads;
     fr.frames = s->frames;
     if (need_film && !s->accum) return fail(RT_ESTATE, "rt_render: no film bound (call rt_film_bind first)");
@@ -574,7 +446,7 @@ static int make_frame(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, bool nee
 int rt_camera_rays(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *rays_out) {
     if (!s || !rd || !rays_out) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
-    DevFrame fr; int rc = make_frame(s, rd, fr, false); if (rc) return rc;
+    DevFrame fr; int rc = camera_frame(rd, fr); if (rc) return rc;
     DevBuf<RtRay> dev;
     if ((rc = dev.grow(count ? count : 1))) return rc;
     hipLaunchKernelGGL(camera_kernel, dim3((count + 255) / 256), dim3(256), 0, s->stream, s->dev, fr,
@@ -592,11 +464,7 @@ int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, ui
     if ((reinterpret_cast<uintptr_t>(dev_rays) & 15u) != 0) return fail(RT_EINVAL, "rt_camera_rays_device: dev_rays is not 16-byte aligned");
     if (count > (1u << 30)) return fail(RT_EINVAL, "rt_camera_rays_device: count = " + std::to_string(count) + " is above 2^30");
     HIPCHK(hipSetDevice(s->device));
-    // A camera ray depends on the sampler, the film and the camera, not on the integrator's sample requests (setup_sample, rt_integrate.h); the two
-    // integrators whose requests make_frame keeps in a device table (a blocking copy) are described as Whitted here
-    RtRenderDesc d = *rd;
-    if (d.integrator == RT_INTEGRATOR_BIDIRECTIONAL || (d.integrator == RT_INTEGRATOR_DIRECT && d.strategy == RT_STRATEGY_ALL)) d.integrator = RT_INTEGRATOR_WHITTED;
-    DevFrame fr; int rc = make_frame(s, &d, fr, false); if (rc) return rc;
+    DevFrame fr; int rc = camera_frame(rd, fr); if (rc) return rc;
     if (count == 0) return RT_OK;
     hipLaunchKernelGGL(camera_kernel, dim3((count + 255) / 256), dim3(256), 0, s->stream, s->dev, fr, (unsigned long long)first, count, dev_rays);
     HIPCHK(hipGetLastError());
@@ -661,7 +529,8 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
         if (s->dev.n_lights == 0) return fail(RT_EINVAL, "rt_render: the bidirectional integrator needs at least one light (the reference indexes lights[-1] in a scene with no lights)");
     }
     if (!rd->filter_table) return fail(RT_EINVAL, "rt_render: no filter table");
-    DevFrame fr; int rc = make_frame(s, rd, fr, true); if (rc) return rc;
+    const plan::FrameKnobs kn = frame_knobs();
+    DevFrame fr; plan::Schedule sc; int rc = make_frame(s, rd, kn, fr, sc, true); if (rc) return rc;
     const bool weighted = rd->integrator == RT_INTEGRATOR_DIRECT && rd->strategy == RT_STRATEGY_WEIGHTED;
     if (rd->integrator == RT_INTEGRATOR_DIRECT && (rd->strategy < RT_STRATEGY_ALL || rd->strategy > RT_STRATEGY_WEIGHTED)) return fail(RT_EINVAL, "rt_render: unknown direct lighting strategy");
     if (weighted) {                                           // WeightedSampleOneLight: rt_weighted.h
@@ -672,7 +541,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
         // the light AND on occlusion: the survey pass (every light, the counter left where the LAST light's estimate ends) and the frame pass (the chosen
         // light only) then reach the sample's next shading point with different counters, and a light that draws (ShapeSet::Sample's triangle pick) is fed
         // a different random number than the one its surveyed luminance came from.  Delta lights never draw: their Ld does not depend on it.
-        if (s->volume.present && s->light_draws != 0) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" in a participating medium needs lights whose estimates draw no random numbers "
+        if (s->volume.present && s->facts.light_draws != 0) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" in a participating medium needs lights whose estimates draw no random numbers "
                                                                             "(point / spot / distant / single-triangle / quadric lights): an emitter of several triangles draws its triangle, and the medium makes "
                                                                             "the draw's position in the stream depend on occlusion");
         // An infinite light draws one RandomFloat() per estimate (infinite.cpp:104), whatever the light sample: the survey would have to keep one estimate of it
@@ -682,46 +551,12 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
         if (s->dev.n_lights > 2048u) return fail(RT_EINVAL, "rt_render: strategy \"weighted\" holds the per-light tables of its recurrence in LDS: at most 2048 lights");
         if (fr.total_work >= 0xffffffffull) return fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 camera samples in the frame");
     }
-    const bool skip_film = knob("PBRT_HIP_DEBUG_NOFILM") != nullptr;   // perf experiments only
+    const bool skip_film = kn.debug_nofilm.has_value();                // perf experiments only
     FilmGather fg; rc = film_gather_plan(s, fr, fg); if (rc) return rc;
-    int vol_nmax = 0;
-    fr.dens_cap = 0;
-    if (s->volume.present) {
-        if (!(rd->step_size > 0.f)) return fail(RT_EINVAL, "rt_render: volume integrator stepsize must be positive");
-        if (rd->volume_integrator != RT_VOLUME_EMISSION && rd->volume_integrator != RT_VOLUME_SINGLE) return fail(RT_EINVAL, "rt_render: unknown volume integrator");
-        const float ex = s->volume.p1[0] - s->volume.p0[0], ey = s->volume.p1[1] - s->volume.p0[1], ez = s->volume.p1[2] - s->volume.p0[2];
-        const double diag = std::sqrt(double(ex) * ex + double(ey) * ey + double(ez) * ez);
-        const double nsteps = std::ceil(diag / rd->step_size) + 2;
-        if (nsteps > 65536) return fail(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
-        vol_nmax = int(nsteps);
-        if (s->density_kind != RT_DENSITY_NONE) {
-            // DensityRegion::Tau (volume.cpp:137-153) marches `while (t0 < t1) t0 += step` along the normalised world-space ray: its samples are bounded by
-            // the volume's world diagonal over the smallest step (.5f * stepsize), and the loop only ends if t + .5f * stepsize > t for every t a ray can
-            // reach -- bounded by the union of the scene bound, the camera position and the volume's world bound (ray parameters start at mint >= 0)
-            const double *wb = s->vol_world;
-            const double wx = wb[3] - wb[0], wy = wb[4] - wb[1], wz = wb[5] - wb[2];
-            const double wdiag = std::sqrt(wx * wx + wy * wy + wz * wz);
-            const float half = .5f * rd->step_size;
-            const double taus = std::ceil(wdiag / double(half)) + 2;
-            if (taus > double(1 << 20)) return fail(RT_EINVAL, "rt_render: stepsize too small for the density region (an optical-depth march would take more than 2^20 samples)");
-            double u[6] = {wb[0], wb[1], wb[2], wb[3], wb[4], wb[5]};
-            const float *c2w = s->dev.cam.camera_to_world;                          // the camera position, CameraToWorld(0,0,0)
-            const double cam[3] = {c2w[3], c2w[7], c2w[11]};
-            for (int i = 0; i < 3; ++i) { u[i] = std::min(u[i], cam[i]); u[3 + i] = std::max(u[3 + i], cam[i]); }
-            const float *sb = s->dev.bounds;
-            if (sb[0] <= sb[3] && sb[1] <= sb[4] && sb[2] <= sb[5])
-                for (int i = 0; i < 3; ++i) { u[i] = std::min(u[i], double(sb[i])); u[3 + i] = std::max(u[3 + i], double(sb[3 + i])); }
-            const double ux = u[3] - u[0], uy = u[4] - u[1], uz = u[5] - u[2];
-            const float tmax = std::nextafter(float(std::sqrt(ux * ux + uy * uy + uz * uz)), INFINITY);
-            volatile float tv = tmax;                                               // the device's float addition, not a wider one
-            const float adv = tv + half;
-            if (!std::isfinite(tmax) || !(adv > tmax))
-                return fail(RT_EINVAL, "rt_render: stepsize too small for the density region: at the scene's ray parameters t + .5 * stepsize == t, the optical-depth march would not advance");
-            fr.dens_cap = int(taus);
-            vol_nmax = std::max(vol_nmax, int(std::ceil(wdiag / rd->step_size)) + 2);     // march steps along a world-space ray (a scaled volume)
-            if (vol_nmax > 65536) return fail(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
-        }
-        fr.vol_nmax = vol_nmax;                                  // (bind_scratch sizes the march samples from it)
+    {   // the medium's march bounds (bind_scratch sizes the march samples from vol_nmax)
+        plan::March m;
+        if (plan::Refusal r = plan::plan_march(*rd, s->facts, m)) return fail(r.code, r.msg);
+        fr.vol_nmax = m.vol_nmax; fr.dens_cap = m.dens_cap;
     }
     // ---- scratch
     {
@@ -741,7 +576,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     s->rendered = true;
     s->last_fixed = false;                                     // (render_mega sets it)
     // ---- the frame, by one of the four launch functions
-    rc = fr.pipeline ? render_pipeline(s, rd, fr) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr);
+    rc = fr.pipeline ? render_pipeline(s, rd, fr, sc, kn) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr, sc);
     if (rc) return rc;
     s->last_pipeline = fr.pipeline != 0; s->last_weighted = weighted;
     // ---- film gather and events
@@ -795,7 +630,7 @@ int rt_counters_reset(RtScene *s) {
 }
 int rt_set_counting(RtScene *s, int enabled) {
     if (!s) return fail(RT_EINVAL, "null scene");
-    s->counting = enabled != 0;
+    s->facts.counting = enabled != 0;
     return RT_OK;
 }
 int rt_last_render_ms(RtScene *s, float *total_ms, float *kernel_ms) {

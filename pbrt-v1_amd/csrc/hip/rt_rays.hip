@@ -100,7 +100,7 @@ static int trace_device(RtScene *s, const RtRay *dev_rays, uint32_t n, int any, 
     job.q_o = q_o; job.q_d = q_d; job.q_slot = nullptr; job.q_count = s->trace_qc; job.hit = hit_plane;
     job.n_slots = 0; job.spill = s->spill; job.n_threads = s->n_threads; job.counters = s->counters;
     // rt_set_counting is honoured: the counting twin or the timed kernel (the hits are the same, rt_flavour.h)
-    const flavour::Request rq{0, s->accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->counting, s->has_ext, false};
+    const flavour::Request rq{0, s->facts.accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->facts.counting, s->facts.has_ext, false};
     const int k = flavour::Trace::index(rq);
     hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
     HIPCHK(hipGetLastError());

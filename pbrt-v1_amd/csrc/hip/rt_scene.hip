@@ -279,29 +279,36 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         const auto now = std::chrono::steady_clock::now();
         std::fprintf(stderr, "CREATE %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_prev).count()); t_prev = now;
     };
-    s->accel_kind = d->accel.kind;
+    s->facts.accel_kind = d->accel.kind;
     if (pre) {
         const Node *pn = reinterpret_cast<const Node *>(pre->nodes);
         s->tree.nodes.assign(pn, pn + pre->n_nodes); s->tree.leaf_refs.assign(pre->leaf_refs, pre->leaf_refs + pre->n_leaf_refs);
         s->tree.max_depth = int(pre->max_depth); s->tree.build_seconds = 0.0;
         std::memcpy(s->tree.bounds, pre->bounds, sizeof s->tree.bounds);
-        if (s->accel_kind == RT_ACCEL_GRID) {
+        if (s->facts.accel_kind == RT_ACCEL_GRID) {
             s->gridacc.voxels = s->tree.nodes; s->gridacc.refs = s->tree.leaf_refs; s->gridacc.build_seconds = 0.0;
             std::memcpy(s->gridacc.bounds, pre->bounds, sizeof s->gridacc.bounds);
             for (int a = 0; a < 3; ++a) { s->gridacc.nvox[a] = pre->grid_nvoxels[a]; s->gridacc.width[a] = pre->grid_width[a]; s->gridacc.inv_width[a] = pre->grid_inv_width[a]; }
         }
-    } else if (s->accel_kind == RT_ACCEL_GRID) {
+    } else if (s->facts.accel_kind == RT_ACCEL_GRID) {
         build_grid(d->tri_verts, d->n_tris, s->gridacc);
         s->tree.nodes = s->gridacc.voxels; s->tree.leaf_refs = s->gridacc.refs; s->tree.max_depth = 0;
         std::memcpy(s->tree.bounds, s->gridacc.bounds, sizeof s->tree.bounds); s->tree.build_seconds = s->gridacc.build_seconds;
     } else build_kdtree(d->tri_verts, d->n_tris, d->accel, s->tree);
 
+    {   // what the scheduling policy asks of the tree (plan_schedule, rt_frame_plan.h): its size and how fat its leaves are.  Here, where the nodes are at
+        // hand, once per scene: a pass over 36 M nodes costs 12 ms, not something to pay per frame
+        size_t leaves = 0, refs = 0;
+        if (s->facts.accel_kind == RT_ACCEL_KDTREE) for (const Node &n : s->tree.nodes) if ((n.x & 3u) == 3u && (n.x >> 2)) { ++leaves; refs += n.x >> 2; }
+        s->facts.n_nodes = s->tree.nodes.size();
+        s->facts.per_leaf = leaves ? double(refs) / double(leaves) : 1.0;
+    }
     tick("accelerator");
     // the order of the pair blocks: a sequential walk over the tree's shape (1.8 s at 10 M triangles) on its own thread, beside everything up to the pair fill
     PairBlockOrder pbo;
     std::thread order_thread;
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{order_thread};
-    if (s->accel_kind == RT_ACCEL_KDTREE) order_thread = std::thread([&] { pair_blocks_order(s->tree.nodes, pbo); });
+    if (s->facts.accel_kind == RT_ACCEL_KDTREE) order_thread = std::thread([&] { pair_blocks_order(s->tree.nodes, pbo); });
     // ... and so do the leaf entries (four passes over the leaf lists by all host threads: 1.3 s at 10 M triangles) while this thread fills the per-triangle records
     // and uploads the tree.  Scenes of a few thousand references (C2's 14 triangles: cache resident, bound by instruction issue -- the entry form costs it 2.8 %,
     // profiles/r06_dedup_scan.txt) get runs of consecutive records per leaf; everything larger shares one record per primitive.
@@ -312,7 +319,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     const bool copies = knob("PBRT_HIP_LEAF_COPIES") != nullptr;
     std::thread layout_thread;
     Joiner joiner2{layout_thread};
-    if (s->accel_kind == RT_ACCEL_KDTREE) layout_thread = std::thread([&] {
+    if (s->facts.accel_kind == RT_ACCEL_KDTREE) layout_thread = std::thread([&] {
         try { ll_status = leaf_cursor_layout(s->tree.nodes, s->tree.leaf_refs, d->n_tris, copies, runs, ll) ? 1 : -1; } catch (...) { ll_status = -2; }
     });
     // triangles -> 48-byte records
@@ -338,7 +345,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     // expressions (this file is compiled -ffp-contract=off for the host too; sqrt and divide are IEEE on both sides)
     std::vector<float4> shade(size_t(2) * d->n_tris);
     if (n_quadric_slots != d->n_quadrics || (d->n_quadrics && !d->quadrics)) return fail(RT_EINVAL, "rt_scene_create: quadric slots do not match n_quadrics");
-    s->has_ext = s->has_ext || d->n_quadrics > 0;
+    s->facts.has_ext = s->facts.has_ext || d->n_quadrics > 0;
     std::vector<DevTriShading> dshading; std::vector<int> shading_idx;
     if (d->tri_shading) {
         if (d->n_shading && !d->shading) return fail(RT_EINVAL, "rt_scene_create: tri_shading without shading records");
@@ -362,7 +369,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
                 s->tex_uv_host.insert(s->tex_uv_host.end(), r.uv, r.uv + 6);
             }
             if (r.flags & (RT_SHADING_N | RT_SHADING_S)) {
-                smooth = true; s->has_ext = true;
+                smooth = true; s->facts.has_ext = true;
                 DevTriShading o; std::memset(&o, 0, sizeof o);
                 o.flags = r.flags; o.xform = r.xform;
                 std::memcpy(o.uv, r.uv, sizeof o.uv); std::memcpy(o.dpdu, dpdu, sizeof o.dpdu);
@@ -414,7 +421,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     if ((rc = upload(s, s->tree.leaf_refs.data(), s->tree.leaf_refs.size(), &s->dev.leaf_refs))) return rc;
     s->dev.nodes = nodes_dev;
     s->dev.tnodes = nodes_dev;
-    if (s->accel_kind == RT_ACCEL_KDTREE) {
+    if (s->facts.accel_kind == RT_ACCEL_KDTREE) {
         tick("node / leaf-list upload");
         layout_thread.join();
         if (ll_status == -2) return fail(RT_ENOMEM, "rt_scene_create: out of host memory while laying out the leaf entries");
@@ -458,7 +465,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         const RtMaterial &m = d->materials[i];
         if (m.type < RT_MAT_MATTE || m.type > RT_MAT_TRANSLUCENT) return fail(RT_EINVAL, "rt_scene_create: unknown material type");
         rt_material_resolve(&m, &mats[i]);                                        // include/pbrt_hip_texture.h: what the EXT kernels do per hit for a textured material
-        if (m.type >= RT_MAT_PLASTIC) s->has_ext = true;                           // plastic, uber, shinymetal, translucent: their lobes exist only in the EXT kernels
+        if (m.type >= RT_MAT_PLASTIC) s->facts.has_ext = true;                           // plastic, uber, shinymetal, translucent: their lobes exist only in the EXT kernels
     }
     s->materials_host = mats;                                                      // rt_scene_set_textures / rt_render: the records move when room for resolved ones is added
     if ((rc = upload(s, mats.data(), mats.size(), &s->dev.materials))) return rc;
@@ -466,9 +473,10 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
     // lights + emitter triangles with ShapeSet area CDF (shape.h:122-135)
     std::vector<float> ltris(size_t(d->n_light_tris) * 16, 0.f);
     std::vector<DevLight> lights(d->n_lights);
+    s->facts.n_lights = d->n_lights; s->facts.light_samples.assign(d->n_lights, 1);
     for (uint32_t i = 0; i < d->n_lights; ++i) {
         const RtLight &L = d->lights[i]; DevLight &o = lights[i];
-        o.type = L.type; o.n_samples = L.n_samples < 1 ? 1 : L.n_samples;
+        o.type = L.type; o.n_samples = s->facts.light_samples[i] = L.n_samples < 1 ? 1 : L.n_samples;     // (the host keeps them for plan_requests)
         for (int c = 0; c < 3; ++c) { o.color[c] = L.color[c]; o.pos[c] = L.pos[c]; }
         o.first_tri = L.first_tri; o.n_tris = L.n_tris; o.reverse_orientation = L.reverse_orientation;
         o.flip_normal = L.flip_normal; o.area = 0.f;
@@ -484,7 +492,7 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         o.quadric = L.quadric_plus1 - 1;
         if (L.quadric_plus1 < 0 || uint32_t(L.quadric_plus1) > d->n_quadrics) return fail(RT_EINVAL, "rt_scene_create: light refers to a quadric out of range");
         if (L.type < RT_LIGHT_POINT || L.type > RT_LIGHT_INFINITE) return fail(RT_EINVAL, "rt_scene_create: unknown light type");
-        if (L.type == RT_LIGHT_INFINITE) { s->has_ext = true; ++s->n_infinite; }      // the light's code exists only in the EXT kernels
+        if (L.type == RT_LIGHT_INFINITE) { s->facts.has_ext = true; ++s->n_infinite; }      // the light's code exists only in the EXT kernels
         if (L.type != RT_LIGHT_AREA) continue;
         if (size_t(L.first_tri) + L.n_tris > d->n_light_tris) return fail(RT_EINVAL, "rt_scene_create: light triangle range out of bounds");
         float area = 0.f; std::vector<float> areas;
@@ -515,17 +523,24 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         s->n_drawing_lights = 0;
         for (uint32_t i = 0; i < d->n_lights; ++i) {       // ShapeSet::Sample (shape.h:115-121) draws one RandomFloat() when the emitter has several triangles
             const int draws = (d->lights[i].type == RT_LIGHT_AREA && d->lights[i].quadric_plus1 == 0 && d->lights[i].n_tris > 1) ? 1 : 0;
-            if (i == 0) s->light_draws = draws; else if (draws != s->light_draws) s->light_draws = -1;
+            if (i == 0) s->facts.light_draws = draws; else if (draws != s->facts.light_draws) s->facts.light_draws = -1;
             flags[i] = unsigned(draws); s->n_drawing_lights += unsigned(draws);
         }
         if ((rc = upload(s, flags.data(), flags.size(), &s->light_draw_flags))) return rc;      // (read by the recurrence of a "weighted" frame with lights of mixed RNG use)
     }
 
     s->dev.n_tris = d->n_tris; s->dev.n_lights = d->n_lights; s->dev.n_infinite = int(s->n_infinite);
-    s->dev.accel_kind = s->accel_kind;
+    s->dev.accel_kind = s->facts.accel_kind;
     for (int a = 0; a < 3; ++a) { s->dev.nvox[a] = s->gridacc.nvox[a]; s->dev.gwidth[a] = s->gridacc.width[a]; s->dev.ginv_width[a] = s->gridacc.inv_width[a]; }
     std::memcpy(s->dev.bounds, s->tree.bounds, sizeof s->dev.bounds);
     s->dev.cam = d->camera; s->dev.vol = d->volume; s->volume = d->volume;
+    {   // the rest of what the frame planners read
+        plan::SceneFacts &f = s->facts;
+        f.medium = d->volume.present != 0;
+        f.lens_radius = d->camera.lens_radius; f.camera_type = d->camera.type;
+        std::memcpy(f.bounds, s->dev.bounds, sizeof f.bounds);
+        for (int a = 0; a < 3; ++a) { f.vol_p0[a] = d->volume.p0[a]; f.vol_p1[a] = d->volume.p1[a]; f.cam_pos[a] = d->camera.camera_to_world[4 * a + 3]; }   // CameraToWorld(0,0,0)
+    }
 
     // persistent launch geometry: as many resident blocks as the kernel's registers/LDS admit
     hipDeviceProp_t prop;
@@ -603,7 +618,7 @@ int rt_scene_get_stream(RtScene *s, void **hip_stream_out) {
 int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
     if (!s || !r) return fail(RT_EINVAL, "rt_scene_set_density: null argument");
     if (s->rendered) return fail(RT_ESTATE, "rt_scene_set_density: the scene has rendered a frame already");
-    if (s->density_kind != RT_DENSITY_NONE) return fail(RT_ESTATE, "rt_scene_set_density: the scene has a density region already");
+    if (s->facts.density_kind != RT_DENSITY_NONE) return fail(RT_ESTATE, "rt_scene_set_density: the scene has a density region already");
     if (!s->volume.present) return fail(RT_EINVAL, "rt_scene_set_density: the scene has no medium (RtSceneDesc.volume.present == 0)");
     if (r->kind != RT_DENSITY_EXPONENTIAL && r->kind != RT_DENSITY_GRID) return fail(RT_EINVAL, "rt_scene_set_density: unknown density kind");
     // the volume's world bound, WorldToVolume.GetInverse()(extent) (exponential.cpp:38, volumegrid.cpp:36): its corners through the inverse, in double
@@ -640,9 +655,9 @@ int rt_scene_set_density(RtScene *s, const RtDensityRegion *r) {
     d.dens_n[0] = r->nx; d.dens_n[1] = r->ny; d.dens_n[2] = r->nz; d.dens_grid = grid;
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
-    std::memcpy(s->vol_world, wb, sizeof wb);
-    s->density_kind = r->kind;
-    s->has_ext = true;                                                          // the density code exists only in the EXT kernels
+    std::memcpy(s->facts.vol_world, wb, sizeof wb);
+    s->facts.density_kind = r->kind;
+    s->facts.has_ext = true;                                                          // the density code exists only in the EXT kernels
     return RT_OK;
 }
 
@@ -750,7 +765,7 @@ int rt_scene_set_textures(RtScene *s, const RtTexture *nodes, uint32_t n_nodes, 
         if (n_textured) { if ((rc = upload_tex_uv(s))) return rc; }             // the per-vertex uvs of the meshes that have them (copies the scene record too)
         HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
         s->has_textures = true;
-        s->has_ext = true;                                                      // the evaluator exists only in the EXT kernels
+        s->facts.has_ext = true;                                                      // the evaluator exists only in the EXT kernels
         return RT_OK;
     });
 }
@@ -791,7 +806,7 @@ extern "C" {
 
 int rt_scene_accel_info(const RtScene *s, RtAccelInfo *info) {
     if (!s || !info) return fail(RT_EINVAL, "null argument");
-    fill_info(s->tree, s->gridacc, s->accel_kind, s->n_tris, info);
+    fill_info(s->tree, s->gridacc, s->facts.accel_kind, s->n_tris, info);
     return RT_OK;
 }
 

@@ -45,3 +45,43 @@ def test_light_loop_exit_keeps_every_flavour_bit_identical(pkg, scenes, integ):
     # every further light is in the loop: it changes the film
     for ns in (1, 4):
         assert not np.array_equal(films[(1, ns)], films[(2, ns)]) and not np.array_equal(films[(2, ns)], films[(3, ns)]), (integ, ns)
+
+
+@pytest.mark.gpu
+def test_the_scene_keeps_its_lights_sample_counts_on_the_host(pkg, scenes):
+    """DirectLighting "all" lays out three sample requests per light from the lights' sample counts.  The scene keeps them on the host from the loop that
+    fills the uploaded records (SceneFacts::light_samples, rt_frame_plan.h): a frame reads nothing back.  Seen from outside: the counts set the shadow
+    rays of a frame, a light of 65536 samples is refused by "all" with the request table's message before anything is launched, and "one", which asks
+    for one sample whatever the light says, renders the same scene."""
+    need_gpu(pkg)
+    rays = {}
+    for ns in (1, 3, 65536):
+        kw = dict(xres=8, yres=8, xsamples=1, ysamples=1, jitter=False, keyed=True, count=True, world_kwargs=dict(light_nsamples=ns))
+        ps = pkg.ParsedScene(text=scenes.cornell_scene(**kw, **INTEGRATORS["direct_all"]))
+        assert ps.valid and ps.errors == 0 and ps.lights()[0]["nsamples"] == ns
+        ds = pkg.DeviceScene(ps)
+        try:
+            if ns == 65536:
+                with pytest.raises(pkg.RtError, match="more than 65535 samples per light"):
+                    ds.render()
+                assert ds.counters()["camera_rays"] == 0                   # nothing was launched
+            else:
+                ds.render()
+                rays[ns] = ds.counters()
+                assert rays[ns]["camera_rays"] == ps.n_camera_samples and rays[ns]["bad_samples"] == 0
+        finally:
+            ds.close()
+        ps.close()
+        if ns == 65536:
+            ps = pkg.ParsedScene(text=scenes.cornell_scene(**kw, **INTEGRATORS["direct_one"]))
+            ds = pkg.DeviceScene(ps)
+            try:
+                ds.render()
+                assert ds.counters()["camera_rays"] == ps.n_camera_samples
+            finally:
+                ds.close()
+            ps.close()
+    # matte surfaces only: a camera ray has at most one shading point, and an estimate casts at most one shadow ray -- one sample per light cannot
+    # cast more shadow rays than there are camera rays, three samples do (most points see the light) and cannot cast more than three times as many
+    n = rays[1]["camera_rays"]
+    assert n == rays[3]["camera_rays"] and 0 < rays[1]["any_rays"] <= n < rays[3]["any_rays"] <= 3 * n, rays

@@ -5,6 +5,7 @@ fixtures of tests/golden/rays/) and the float64 forms, with field selection, mis
 No test feeds a non-finite ray: that guard is tested on the host (tests/test_rays_host.py)."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -96,16 +97,31 @@ def test_same_hits_and_counts_as_the_host_entry_points(pkg, label):
 
 
 # ---------------------------------------------------------------------------------------------- 2. camera rays
+CAMERA_SAMPLERS = {"stratified": '"integer xsamples" [2] "integer ysamples" [2] "bool jitter" ["true"]',
+                   "lowdiscrepancy": '"integer pixelsamples" [3]',          # rounded up to 4
+                   "random": '"integer xsamples" [2] "integer ysamples" [2]'}
+
+
 def camera_scenes():
     out = {"perspective (probe_cornell)": as_whitted(load_golden("probe_cornell")["scene"])}
     for name in A.PROBES:
         out[name] = as_whitted(np.load(os.path.join(GOLDEN, "analytic", name + ".npz"))["scene"])
+    # the two integrators whose sample requests live in a device table (DirectLighting "all": per light; bidirectional: its BidirTable), under each
+    # sampler: a camera ray must not depend on them, nor wait for them
+    probe = str(load_golden("probe_cornell")["scene"])
+    for integ, line in (("directlighting all", 'SurfaceIntegrator "directlighting" "string strategy" ["all"]'), ("bidirectional", 'SurfaceIntegrator "bidirectional"')):
+        for sampler, params in CAMERA_SAMPLERS.items():
+            text = re.sub(r'^SurfaceIntegrator "probe".*$', line, probe, flags=re.M)
+            text = re.sub(r'^Sampler "keyed".*$', 'Sampler "%s" "integer seed" [0] %s' % (sampler, params), text, flags=re.M)
+            assert text.count(line) == 1 and text.count('Sampler "%s"' % sampler) == 1
+            out["%s, %s (probe_cornell)" % (integ, sampler)] = text
     return out
 
 
 @pytest.mark.parametrize("label", list(camera_scenes()))
 def test_camera_rays_device_equals_camera_rays(pkg, label):
-    """perspective, orthographic (screen window), environment and thin-lens frames: the whole frame and a window that starts inside it"""
+    """perspective, orthographic (screen window), environment and thin-lens frames, and DirectLighting "all" and bidirectional frames under the three
+    samplers: the whole frame and a window that starts inside it"""
     need_gpu(pkg)
     ps, ds = open_scene(pkg, camera_scenes()[label])
     n = ps.n_camera_samples
