@@ -397,6 +397,34 @@ int rt_hit_geometry_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_h
 /* Camera::GenerateRay (core/camera.h:33-34; perspective.cpp:51-82, orthographic.cpp:48-79, environment.cpp:47-61) as rt_camera_rays, into
  * dev_rays[count]: the rays of camera samples first .. first + count - 1, bit for bit those of rt_camera_rays */
 int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays);
+/* Scene::Li (core/scene.cpp:120-126: surfaceIntegrator->Li, then volumeIntegrator->Transmittance and volumeIntegrator->Li) for n rays in device
+ * memory.  dev_out[n][4] = L.r, L.g, L.b, alpha (16-byte aligned, like dev_rays).
+ *  - Sample set.  Li takes a Sample (scene.cpp:58).  Ray i is evaluated with the sample set of camera sample first + i of the frame `rd` describes:
+ *    its keyed RNG stream, its Sample::oneD / twoD values under the frame's sampler (sampling.cpp:41-70), the frame's integrator and its
+ *    parameters.  first + i is the index rt_samples_read and rt_camera_rays_device use on one shard: the scanline index pixel * spp + s.  Only
+ *    the camera ray (scene.cpp:44-45) is replaced by the caller's.
+ *  - The ray is taken as given: o, d, mint, maxt.  d must be of unit length -- the integrators use -d as wo (whitted.cpp:69, directlighting.cpp:100,
+ *    path.cpp:98) as Camera::GenerateRay hands them normalised directions -- and the library does not renormalise, so that a camera ray comes
+ *    back out bit for bit.  There are no ray differentials (scene.cpp:46-53): the textures that would read them are refused at scene create.
+ *  - Defining property.  With dev_rays as rt_camera_rays_device(s, rd, first, n, ...) wrote them, dev_out[i] is floats 0..3 of record first + i
+ *    that rt_render of that frame leaves for rt_samples_read, bit for bit -- the radiance check of scene.cpp:60-74 included: a NaN radiance, a
+ *    luminance below -1e-5 or an infinite one becomes 0 (and counts as a bad sample).
+ *  - Asynchronous on the scene's stream, no host copy and no wait, as the calls above.  The workspace is the per-thread scratch frames use (it
+ *    does not depend on n) and grows -- waiting for the stream -- only when the query recurses deeper than any frame or query before it; a
+ *    DirectLighting "all" query uploads its per-light sample requests when they differ from the last frame's, as rt_render does.
+ *  - It is not a frame: neither the film nor the sample buffer is touched, rt_last_render_stats, rt_last_render_ms, rt_samples_read and
+ *    rt_film_* report the last rt_render as before the call, and a later rt_render gives the film it gave before.
+ *  - Counters.  With rt_set_counting on, the counting twin runs and rt_counters advances by what rt_render adds for those samples
+ *    (camera_rays by n less the unusable rays).  stack_overflows belongs to the kernel form: it agrees where the frame ran the megakernel.
+ *  - An unusable ray (rt::ray_usable, above) yields (0, 0, 0, 0) and traces nothing -- an infinite light's Le (infinite.cpp:84-95) would
+ *    take its direction -- and counts nothing; the other rays of the call are unaffected.  maxt = +inf and mint > maxt are ordinary rays.
+ *  - Accepted: Whitted, DirectLighting "all" and "one", Path; with or without a medium; kd-tree or grid; each sampler; shard_count == 1.
+ *    Refused with RT_EINVAL before any launch (rt_last_error says which): DirectLighting "weighted" (its recurrence spans the frame,
+ *    transport.cpp:71-122), the bidirectional and the debug integrator, shard_count != 1, first + n beyond the frame's camera samples, a NULL
+ *    or misaligned pointer with n > 0, and what rt_render refuses of the description.  n == 0 is RT_OK and launches nothing.
+ *  - Always the megakernel with the full shading set (every material, quadric and light) at natural register allocation: a query is
+ *    somewhat slower than the frame's own kernel where that is a high-occupancy or fixed-frame one. */
+int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays, uint64_t first, uint32_t n, float *dev_out);
 /* The stream the scene's calls are queued on: its own (non-blocking) one, or what rt_scene_set_stream was given */
 int rt_scene_get_stream(RtScene *s, void **hip_stream_out);
 

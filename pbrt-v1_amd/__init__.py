@@ -33,7 +33,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 
 
-HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
+HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_mega_rw.hip", "rt_mega_rd.hip", "rt_mega_rp.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
              "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
@@ -317,7 +317,7 @@ def hip_lib():
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
                      "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
-                     "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream"):
+                     "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -335,6 +335,7 @@ def hip_lib():
         L.rt_trace_any_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
         L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.rt_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_scene_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.rt_film_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
         L.rt_film_clear.argtypes = [C.c_void_p]
@@ -1099,6 +1100,26 @@ class DeviceScene:
             if mine is not None:
                 cur.wait_stream(mine)
         return occ
+
+    def radiance(self, rays, first: int = 0):
+        """Scene::Li for rays in device memory (rt_radiance_device): a float32 [n, 4] torch tensor (L.r, L.g, L.b, alpha) on the scene's device.
+        rays: contiguous float32 [n, 8] torch tensor on that device, directions of unit length.  Ray i is evaluated with the sample set of camera
+        sample first + i of the parsed frame (its RNG stream, sampler values, integrator): for the frame's own rays (camera_rays_device(first, n))
+        the result is samples()[first:first + n, :4] of a render() bit for bit.  Neither the film nor the sample buffer is touched."""
+        import torch
+        self._check_ray_tensor(torch, rays, getattr(self, "_device", None))
+        if first < 0:
+            raise ValueError("radiance: first must not be negative")
+        n, dev = int(rays.shape[0]), rays.device
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        if n:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_radiance_device(self._s, self.parsed.render_desc, C.c_void_p(rays.data_ptr()), int(first), n, C.c_void_p(out.data_ptr())))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return out
 
     def camera_rays_device(self, first: int, count: int):
         """rt_camera_rays_device: the rays of camera samples first .. first + count - 1 of the parsed frame as a float32 [count, 8] torch tensor on

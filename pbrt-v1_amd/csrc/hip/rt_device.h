@@ -171,6 +171,11 @@ struct DevFrame {
 #ifdef RT_TAIL_PROBE
     unsigned long long *probe;      // -DRT_TAIL_PROBE builds (tools/build_variant.py): per megakernel wave {start, work list found empty, end} in 10 ns ticks + samples taken
 #endif
+    // a radiance query (rt_radiance_device; read only by the kernels of flavour::Rays, appended so that no other field moved): work item w of
+    // [0, total_work) is camera sample q_first + w of the frame, its ray is q_rays[2 * w], [2 * w + 1] (one RtRay) and its {L.rgb, alpha} goes to q_out[w]
+    const float4 *q_rays;
+    float4 *q_out;
+    unsigned q_first;
 };
 
 // Explicit address spaces.  Pointers that live inside DevScene/DevFrame are loaded from memory, so the compiler cannot

@@ -31,6 +31,7 @@ struct Any {
     static constexpr bool no_env_camera = false;     // RtCamera::type is perspective or orthographic (still a run-time value between those two)
     static constexpr bool tile_order = false;        // single shard with DevFrame::mega_tile > 0: tile_order_to_sample hands out the work, fewer than 2^32 samples
     static constexpr bool all_n1 = false;            // every DimReq of the frame has n == 1 (one_d, two_d, light_dims)
+    static constexpr bool caller_rays = false;       // the ray-source axis: the camera (false), or the caller's RtRay array (DevFrame::q_rays; Rays below)
 };
 // the frames of qualifies()
 struct Frame {
@@ -39,6 +40,13 @@ struct Frame {
     static constexpr bool no_env_camera = RT_FIXED_CAMERA != 0;
     static constexpr bool tile_order = RT_FIXED_TILE_ORDER != 0;
     static constexpr bool all_n1 = RT_FIXED_N1 != 0;
+    static constexpr bool caller_rays = false;
+};
+// A radiance query (rt_radiance_device): nothing else known at compile time, and the rays are the caller's.  Work item w of [0, DevFrame::total_work) is
+// camera sample DevFrame::q_first + w of the frame in scanline order (no tile order, nothing falls off an extent); setup_sample sets the sample set up
+// as for that camera sample and loads DevFrame::q_rays[w] in place of camera_ray; the end of the sample stores {L, alpha} at DevFrame::q_out[w].
+struct Rays : Any {
+    static constexpr bool caller_rays = true;
 };
 
 // what the host knows of a frame and its scene when it picks the kernel (render_mega, rt_kernels.hip)

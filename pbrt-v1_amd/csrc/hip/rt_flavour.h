@@ -2,7 +2,7 @@
 // entry of its table that serves the request, flavour(k), the template arguments of entry k, and N, the table's size.  The translation units build
 // their tables from flavour(k) (RT_FLAVOUR_TABLE below), rt_host.h sizes the resident grids by N and rt_kernels.hip picks entries with index():
 // a table's order, its size and the host's choice cannot disagree.  (A ninth family, flavour::Fixed -- the twins of six Mega entries compiled for a
-// fixed frame -- lives in rt_fixed_frame.h with the traits it is built from.)  No HIP header: tests/flavour_host_test.cpp checks the rules with a host compiler.
+// fixed frame -- lives in rt_fixed_frame.h with the traits it is built from; flavour::Rays below, the radiance query, is built from fixed::Rays of that header.)  No HIP header: tests/flavour_host_test.cpp checks the rules with a host compiler.
 #pragma once
 #include "../../../include/pbrt_hip.h"
 #include <array>
@@ -77,6 +77,20 @@ struct Debug {
     static constexpr int index(const Request &r) { return ((r.vol ? 2 : 0) + (r.grid ? 1 : 0)) * 2 + (r.count ? 1 : 0); }
     static constexpr Flavour flavour(int k) { return Flavour{(k & 1) != 0, (k >> 1) & 1, (k & 4) != 0, true, (k & 4) != 0 ? RT_MIN_WAVES : RT_HIGH_OCC_WAVES, false}; }
 };
+// rt::render_kernel_fixed<..., fixed::Rays> per integrator (rt_mega_r{w,d,p}.hip): the radiance query for caller-supplied rays (rt_radiance_device).  A
+// caller's scene may hold any material, quadric or light and a query is not the headline: as Bidir and Debug, one flavour per (VOL, ACCEL, counting), all
+// with the EXT shading set at natural allocation -- the code of Mega's entries 12..15 (timed) and 1, 3, 5, 7 (counting) with another ray source.  No
+// high-occupancy and no fixed-frame twins.  The path integrator's counting kernel on a grid is held to 3 waves as its Mega twin is (rt_render_kernel.h)
+struct Rays {
+    static constexpr int N = 8;
+    static constexpr int index(const Request &r) { return ((r.vol ? 2 : 0) + (r.grid ? 1 : 0)) * 2 + (r.count ? 1 : 0); }
+    static constexpr Flavour flavour(int k, int integ) {
+        const bool count = (k & 1) != 0, grid = ((k >> 1) & 1) != 0, vol = (k & 4) != 0;
+        return Flavour{count, grid ? 1 : 0, vol, true, (count && integ == RT_INTEGRATOR_PATH && grid && !vol && RT_MIN_WAVES < 3) ? 3 : RT_MIN_WAVES, false};
+    }
+    // the entry of Mega's table whose shading code entry k carries
+    static constexpr int generic(int k) { Request r = flavour(k, 0).request(); r.ext = true; return Mega::index(r); }
+};
 // rt::pipe_shade_kernel per integrator (rt_pipe_{w,d,p}.hip): the triple per VOL
 struct Shade {
     static constexpr int N = 6;
@@ -110,6 +124,7 @@ template <class Family, class... Integ> constexpr bool round_trips(Integ... inte
 static_assert(round_trips<Mega>(RT_INTEGRATOR_WHITTED) && round_trips<Mega>(RT_INTEGRATOR_DIRECT) && round_trips<Mega>(RT_INTEGRATOR_PATH), "Mega: index(flavour(k)) != k");
 static_assert(round_trips<Weighted>() && round_trips<Bidir>(), "Weighted / Bidir: index(flavour(k)) != k");
 static_assert(round_trips<Debug>(), "Debug: index(flavour(k)) != k");
+static_assert(round_trips<Rays>(RT_INTEGRATOR_WHITTED) && round_trips<Rays>(RT_INTEGRATOR_DIRECT) && round_trips<Rays>(RT_INTEGRATOR_PATH), "Rays: index(flavour(k)) != k");
 static_assert(round_trips<Shade>() && round_trips<Vertex>() && round_trips<March>() && round_trips<Trace>(), "pipeline: index(flavour(k)) != k");
 
 // A family's table: one value per entry, in the order of flavour(k) -- the kernels of a translation unit, the resident grids of a scene (rt_host.h)

@@ -1,6 +1,6 @@
 // rt_frame_plan.h -- what the host decides for a frame before anything touches the device: the work extent (plan_extent), the sample-request tables
 // that are the keyed RNG's address map (plan_requests), the scheduling policy with its knobs (plan_schedule) and the bounds of the medium's marches
-// (plan_march).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
+// (plan_march); and what turns a frame's schedule into that of a radiance query over caller-supplied rays (plan_query).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
 // allocation beyond std::vector, no I/O, no getenv; a refusal comes back as a code and a message.  make_frame (rt_kernels.hip) binds the results
 // to a DevFrame.  No HIP header: tests/frame_plan_host_test.cpp checks the rules with a host compiler.
 #pragma once
@@ -308,6 +308,31 @@ inline Refusal plan_march(const RtRenderDesc &rd, const SceneFacts &sf, March &m
         if (vol_nmax > 65536) return refuse(RT_EINVAL, "rt_render: stepsize too small for the medium (more than 65536 march steps)");
     }
     m.vol_nmax = vol_nmax;
+    return Refusal{};
+}
+
+// ---------------------------------------------------------------------------------------------- 5. a radiance query (rt_radiance_device)
+// Rays first .. first + n - 1 of the caller stand in for the camera rays of camera samples first .. first + n - 1 of the frame `rd` describes, in
+// scanline order (pixel * spp + s: the order of rt_samples_read and rt_camera_rays_device on one shard).  The sample requests are the frame's
+// (plan_requests: they are the sample set); the schedule is the frame's turned into a query's: the work extent is the n rays, always the
+// megakernel (flavour::Rays: natural allocation, no fixed twin), no tile order -- the rays' coherence is the caller's business.
+struct QueryRange { unsigned long long first = 0; unsigned n = 0; };
+inline Refusal plan_query(const RtRenderDesc &rd, const QueryRange &q, Schedule &sc) {
+    if (rd.integrator == RT_INTEGRATOR_BIDIRECTIONAL) return refuse(RT_EINVAL, "rt_radiance_device: the bidirectional integrator is not supported (its light subpaths belong to no single ray)");
+    if (rd.integrator == RT_INTEGRATOR_DEBUG) return refuse(RT_EINVAL, "rt_radiance_device: the debug integrator is not supported (it computes no radiance; rt_hit_geometry_device returns its quantities)");
+    if (rd.integrator < RT_INTEGRATOR_WHITTED || rd.integrator > RT_INTEGRATOR_PATH) return refuse(RT_EINVAL, "unknown integrator");
+    if (rd.integrator == RT_INTEGRATOR_DIRECT && rd.strategy == RT_STRATEGY_WEIGHTED)
+        return refuse(RT_EINVAL, "rt_radiance_device: strategy \"weighted\" is not supported (its recurrence spans the whole frame in the sampler's order, transport.cpp:71-122)");
+    if (rd.integrator == RT_INTEGRATOR_DIRECT && (rd.strategy < RT_STRATEGY_ALL || rd.strategy > RT_STRATEGY_WEIGHTED)) return refuse(RT_EINVAL, "rt_radiance_device: unknown direct lighting strategy");
+    if (rd.max_depth < 0) return refuse(RT_EINVAL, "rt_radiance_device: negative maxdepth");
+    Extent &e = sc.extent;
+    if (e.shard_count != 1) return refuse(RT_EINVAL, "rt_radiance_device: shard_count != 1 (a query addresses the camera samples of the whole frame: one shard only)");
+    const unsigned long long samples = e.total_pixels * (unsigned long long)e.spp;           // (< 2^32: plan_extent)
+    if (q.first > samples || q.n > samples - q.first) return refuse(RT_EINVAL, "rt_radiance_device: first + n is beyond the frame's camera samples");
+    e.tile_w = e.tile_h = e.tiles_x = 0; e.tile_pixels = 1;
+    e.total_work = q.n;
+    sc.pipeline = 0; sc.by_vertex = false; sc.fixed_frame = false; sc.mega_tile = 0;
+    sc.high_occupancy = 0;                                   // (the natural-allocation kernels carry the pooled-leaf scratch: trav_mode 3 stays where the frame has it)
     return Refusal{};
 }
 

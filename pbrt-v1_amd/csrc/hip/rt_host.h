@@ -46,6 +46,7 @@ using namespace rt;
 namespace rt {
 extern const flavour::Table<RenderKernelFn, flavour::Mega> g_render_kernels_whitted, g_render_kernels_direct, g_render_kernels_path;
 extern const flavour::Table<RenderKernelFn, flavour::Fixed> g_render_kernels_fixed;        // the fixed-frame twins of six Mega entries (rt_fixed_frame.h), all integrators in one table
+extern const flavour::Table<RenderKernelFn, flavour::Rays> g_radiance_kernels_whitted, g_radiance_kernels_direct, g_radiance_kernels_path;   // rt_radiance_device (rt_mega_r{w,d,p}.hip)
 extern const flavour::Table<RenderKernelFn, flavour::Weighted> g_render_kernels_weighted;
 extern const flavour::Table<RenderKernelFn, flavour::Bidir> g_render_kernels_bidir;
 extern const flavour::Table<RenderKernelFn, flavour::Debug> g_render_kernels_debug;
@@ -56,11 +57,13 @@ extern const flavour::Table<PipeMarchFn, flavour::March> g_pipe_march;
 }  // namespace rt
 // ... by RtRenderDesc::integrator
 static const flavour::Table<RenderKernelFn, flavour::Mega> *const g_render_kernels[RT_INTEGRATOR_PATH + 1] = {&g_render_kernels_whitted, &g_render_kernels_direct, &g_render_kernels_path};
+static const flavour::Table<RenderKernelFn, flavour::Rays> *const g_radiance_kernels[RT_INTEGRATOR_PATH + 1] = {&g_radiance_kernels_whitted, &g_radiance_kernels_direct, &g_radiance_kernels_path};
 static const flavour::Table<PipeShadeFn, flavour::Shade> *const g_pipe_shade[RT_INTEGRATOR_PATH + 1] = {&g_pipe_shade_whitted, &g_pipe_shade_direct, &g_pipe_shade_path};
 // The persistent families are launched with as many blocks as stay resident (scene_create): a grid per table entry
 struct ResidentGrids {
     flavour::Table<unsigned, flavour::Mega> mega[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Fixed> fixed;
+    flavour::Table<unsigned, flavour::Rays> rays[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Weighted> weighted;
     flavour::Table<unsigned, flavour::Bidir> bidir;
     flavour::Table<unsigned, flavour::Debug> debug;
@@ -131,6 +134,9 @@ struct RtScene {
     DevBuf<DevMaterial> mat_buf;
     int spill_depth = 0;
     bool have_timing = false;
+    // rt_last_render_stats / rt_last_render_ms read the events of the last timed launch once and keep what they read: hipEventElapsedTime forms a time anew at
+    // every call and two reads of the same events differ in the last digits; a frame's stats stay the same bits until the next timed launch
+    bool stats_cached = false; RtRenderStats stats_cache{};
     uint32_t n_tris = 0;
     // queue pipeline (rt_pipeline.h)
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
@@ -143,6 +149,10 @@ struct RtScene {
     // rt_trace_*_device (rt_rays.hip): the two ray planes the trace kernel reads, and the hit plane of an any-hit call (a closest-hit call
     // writes the caller's RtHit array); each grows only when a call brings more rays than any before it
     DevBuf<float4> ray_planes, any_hits;
+    // rt_radiance_device (rt_kernels.hip): the query's own descriptor, so that the last frame's stays what rt_render left.  Everything else a query needs
+    // is the scratch frames use (frames, vol_buf, the material pool: per resident thread, grown only when a query recurses deeper than anything before
+    // it); nothing is sized by the number of rays
+    DevBuf<DevFrame> query_frame;
 };
 #define RT_PIPE_QN 4096          // ring of per-iteration queue counters
 #define RT_PIPE_TIMED 256        // iterations whose trace launch is bracketed by events

@@ -15,6 +15,7 @@
 #include "rt_shade.h"
 #include "rt_texture.h"
 #include "rt_fixed_frame.h"
+#include "rt_ray_guard.h"
 
 namespace rt {
 
@@ -163,6 +164,20 @@ RT_DEV void sample_write(const DevFrame &fr, const Lane &ln, V3 Ls, float alpha,
     rec[RT_SAMPLE_XY] = make_float4(ln.image_x, ln.image_y, 0.f, 0.f);
 #endif
 }
+// ... and of a radiance query (fixed::Rays): the same check, then one float4 {L, alpha} at the work item's place in the caller's array (written once,
+// not read by this launch: non-temporal).  Neither the sample buffer nor the film sees it.
+RT_DEV void query_store(const DevFrame &fr, uint32_t w, float r, float g, float b, float alpha) {
+    typedef float nt_f4 __attribute__((ext_vector_type(4)));
+    const nt_f4 r0 = {r, g, b, alpha};
+    __builtin_nontemporal_store(r0, (nt_f4 RT_G *)(RT_GPTR(float4, fr.q_out) + w));
+}
+RT_DEV void query_write(const DevFrame &fr, const Lane &ln, V3 Ls, float alpha, unsigned &bad) {
+    const float y = lum_y(Ls);
+    if (Ls.x != Ls.x || Ls.y != Ls.y || Ls.z != Ls.z) { Ls = mk3(0.f); ++bad; }
+    else if (y < -1e-5) { Ls = mk3(0.f); ++bad; }
+    else if (isinf(y)) { Ls = mk3(0.f); ++bad; }
+    query_store(fr, ln.work - fr.q_first, Ls.x, Ls.y, Ls.z, alpha);
+}
 
 // ---- camera sample -> camera ray -----------------------------------------------------------------------
 // StratifiedSampler (samplers/stratified.cpp:51-131, sampling.cpp:72-97): image position of sample s of
@@ -283,8 +298,10 @@ RT_DEV void tile_order_to_sample(const DevFrame &fr, unsigned w, unsigned &pixel
     pixel = (ty * T + qy) * W + tx * T + qx;
 }
 
+// `item` (fixed::Rays only): the work item, whose ray is the caller's.  The sample set -- ln.sample_index, ln.rng, ln.dim_base, the pixel == 0 rule -- is set up
+// the same way whoever supplies the ray; false when the caller's ray is one rt::ray_usable refuses (the sample then traces nothing and is {0, 0, 0, 0})
 template <class FX = fixed::Any>
-RT_DEV void setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned long long pixel, int s, Ray &ray) {
+RT_DEV bool setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned long long pixel, int s, Ray &ray, unsigned item = 0u) {
     const int w = fr.x_end - fr.x_start;
     int px, py;
     if (FX::tile_order || fr.total_pixels <= 0xffffffffull) { const unsigned row = fastdiv(unsigned(pixel), fr.div.width); px = fr.x_start + int(unsigned(pixel) - row * unsigned(w)); py = fr.y_start + int(row); }
@@ -320,10 +337,18 @@ RT_DEV void setup_sample(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
         }
     }
     ln.rng.ctr = ln.dim_base + ((FX::sampler != RT_SAMPLER_STRATIFIED && fr.sampler == RT_SAMPLER_LOWDISCREPANCY) ? 0u : fr.lhs_total);
-    ray = camera_ray<FX>(sc.cam, ln.image_x, ln.image_y, lu, lv);
-    // scene.cpp:47-53 generates the differential's offset rays with ++ / -- on sample->imageX / imageY: Film::AddSample later sees
-    // (x + 1) - 1 in float arithmetic, not x (found by the reference-side binding test, tests/test_boundary.py)
-    ln.image_x = (ln.image_x + 1.f) - 1.f; ln.image_y = (ln.image_y + 1.f) - 1.f;
+    if constexpr (FX::caller_rays) {
+        // one RtRay = two 16-byte loads: o.xyz d.x | d.yz mint maxt, taken as given (d is not renormalised: a camera ray comes back out bit for bit)
+        const float4 a = RT_GPTR(const float4, fr.q_rays)[size_t(2) * item], b = RT_GPTR(const float4, fr.q_rays)[size_t(2) * item + 1];
+        ray.o = mk3(a.x, a.y, a.z); ray.d = mk3(a.w, b.x, b.y); ray.mint = b.z; ray.maxt = b.w;
+        return ray_usable(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
+    } else {
+        ray = camera_ray<FX>(sc.cam, ln.image_x, ln.image_y, lu, lv);
+        // scene.cpp:47-53 generates the differential's offset rays with ++ / -- on sample->imageX / imageY: Film::AddSample later sees
+        // (x + 1) - 1 in float arithmetic, not x (found by the reference-side binding test, tests/test_boundary.py)
+        ln.image_x = (ln.image_x + 1.f) - 1.f; ln.image_y = (ln.image_y + 1.f) - 1.f;
+        return true;
+    }
 }
 
 // ---- recursion frames (whitted / directlighting) ---------------------------------------------------------
@@ -1066,7 +1091,11 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         ln.stage = frame_pop<EXT>(fr, ln, gtid, ln.L);
         return;
     }
-    if constexpr (STAGE == ST_FINISH) {
+    if constexpr (STAGE == ST_FINISH && FX::caller_rays) {
+        query_write(fr, ln, ln.L, ln.alpha, *c_bad);
+        ln.stage = ST_FETCH;
+        return;
+    } else if constexpr (STAGE == ST_FINISH) {
         if (WEIGHTED && fr.weighted_phase == 1) RT_GPTR(unsigned, fr.wt_base)[ln.work] = ln.ord;       // (ord started at 0: the sample's shading points)
         if (!WEIGHTED || fr.weighted_phase == 3) sample_write(fr, ln, ln.L, ln.alpha, *c_bad);
         ln.stage = ST_FETCH;

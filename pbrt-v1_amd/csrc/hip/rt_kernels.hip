@@ -412,11 +412,12 @@ static int camera_frame(const RtRenderDesc *rd, DevFrame &fr) {
 
 // Build the per-frame device descriptor: what rt_frame_plan.h plans for the frame (work extent, sample requests, schedule; `sc` keeps the host-side
 // choices), bound to the scene's device memory.
-static int make_frame(RtScene *s, const RtRenderDesc *rd, const plan::FrameKnobs &kn, DevFrame &fr, plan::Schedule &sc, bool need_film) {
+static int make_frame(RtScene *s, const RtRenderDesc *rd, const plan::FrameKnobs &kn, DevFrame &fr, plan::Schedule &sc, bool need_film, const plan::QueryRange *query = nullptr) {
     plan::Extent ext; plan::Requests rq;
     if (plan::Refusal r = plan::plan_extent(*rd, ext)) return fail(r.code, r.msg);
     if (plan::Refusal r = plan::plan_requests(*rd, s->facts, ext.spp, rq)) return fail(r.code, r.msg);
     sc = plan::plan_schedule(*rd, s->facts, ext, rq, kn);
+    if (query) { if (plan::Refusal r = plan::plan_query(*rd, *query, sc)) return fail(r.code, r.msg); }      // rt_radiance_device: the frame's sample set, the caller's rays as the work
     bind_extent(rd, sc.extent, sc.mega_tile, fr);
     fr.n1d = rq.n1d; fr.n2d = rq.n2d; fr.lhs_total = rq.lhs_total; fr.pixgen_draws = rq.pixgen_draws; fr.dims_max_n = rq.dims_max_n;
     std::memcpy(fr.one_d, rq.one_d, sizeof fr.one_d); std::memcpy(fr.two_d, rq.two_d, sizeof fr.two_d);
@@ -493,6 +494,7 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
     flavour::Request rq = request_of(s);
     rq.count = true;                                            // whatever rt_set_counting says
     const int k = flavour::Trace::index(rq);
+    s->stats_cached = false;
     HIPWARN(hipEventRecord(s->ev0, s->stream));
     hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
     HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream)); s->have_timing = true; s->last_pipeline = false; s->last_fixed = false;
@@ -574,6 +576,7 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (debug) { rc = upload_tex_uv(s); if (rc) return rc; }    // dg.u / dg.v of a mesh with "uv": on the device from the first debug frame on
     { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
     s->rendered = true;
+    s->stats_cached = false;                                   // (the launch functions record the events anew)
     s->last_fixed = false;                                     // (render_mega sets it)
     // ---- the frame, by one of the four launch functions
     rc = fr.pipeline ? render_pipeline(s, rd, fr, sc, kn) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr, sc);
@@ -605,6 +608,41 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
 #endif
     return RT_OK;
 }
+// Scene::Li for caller-supplied rays in device memory (include/pbrt_hip.h): the frame's plan with the n rays as its work (plan_query), bound like a
+// frame, and one launch of the flavour::Rays entry -- the megakernel's radiance estimate with the caller's array as ray source and result sink.
+// Nothing of the last rt_render is touched: no film, no sample buffer, no events, no last_* state; the descriptor is the query's own (query_frame).
+int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays, uint64_t first, uint32_t n, float *dev_out) {
+    static const std::string fn = "rt_radiance_device";
+    if (!s) return fail(RT_EINVAL, fn + ": null scene");
+    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
+    if (n > 0 && !dev_rays) return fail(RT_EINVAL, fn + ": null ray pointer");
+    if (n > 0 && !dev_out) return fail(RT_EINVAL, fn + ": null output pointer");
+    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_rays) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_rays is not 16-byte aligned");
+    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_out) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_out is not 16-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    const plan::FrameKnobs kn = frame_knobs();
+    const plan::QueryRange q{first, n};
+    DevFrame fr; plan::Schedule sc;
+    int rc = make_frame(s, rd, kn, fr, sc, false, &q); if (rc) return rc;
+    {
+        plan::March m;
+        if (plan::Refusal r = plan::plan_march(*rd, s->facts, m)) return fail(r.code, r.msg);
+        fr.vol_nmax = m.vol_nmax; fr.dens_cap = m.dens_cap;
+    }
+    if (n == 0) return RT_OK;
+    fr.q_rays = reinterpret_cast<const float4 *>(dev_rays); fr.q_out = reinterpret_cast<float4 *>(dev_out); fr.q_first = unsigned(first);
+    fr.samples = nullptr; fr.accum = nullptr; fr.filter_table = nullptr;          // (a query has no film)
+    if ((rc = bind_scratch(s, rd, fr, s->n_threads))) return rc;
+    const int k = flavour::Rays::index(request_of(s, rd, &fr));
+    const unsigned grid = s->grids.rays[rd->integrator][k];
+    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
+    HIPCHK(hipMemcpyAsync(s->query_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
+    hipLaunchKernelGGL((*g_radiance_kernels[rd->integrator])[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->query_frame);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
 int rt_sync(RtScene *s) {
     if (!s) return fail(RT_EINVAL, "null scene");
     HIPCHK(hipSetDevice(s->device));
@@ -633,22 +671,8 @@ int rt_set_counting(RtScene *s, int enabled) {
     s->facts.counting = enabled != 0;
     return RT_OK;
 }
-int rt_last_render_ms(RtScene *s, float *total_ms, float *kernel_ms) {
-    if (!s || !s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipEventSynchronize(s->ev2));
-    float k = 0.f, t = 0.f;
-    HIPCHK(hipEventElapsedTime(&k, s->ev0, s->ev1));
-    HIPCHK(hipEventElapsedTime(&t, s->ev0, s->ev2));
-    if (total_ms) *total_ms = t;        // render kernel(s) + film gather
-    if (kernel_ms) *kernel_ms = k;      // rt::render_kernel alone, or the whole shade / trace loop of the queue pipeline
-    return RT_OK;
-}
-// Timing of the last rt_render by kernel: {whole frame, render part (megakernel or shade+trace loop), trace kernel launches summed,
-// film gather} in ms, the number of pipeline iterations (0: megakernel) and how many of them were timed.
-int rt_last_render_stats(RtScene *s, RtRenderStats *out) {
-    if (!s || !out) return fail(RT_EINVAL, "null argument");
-    if (!s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
+// Timing of the last timed launch by kernel, read from its events (rt_last_render_stats below keeps what this reads)
+static int read_render_stats(RtScene *s, RtRenderStats *out) {
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipEventSynchronize(s->ev2));
     std::memset(out, 0, sizeof *out);
@@ -675,6 +699,27 @@ int rt_last_render_stats(RtScene *s, RtRenderStats *out) {
         hipEvent_t seq[6] = {s->ev0, s->wt_ev[0], s->wt_ev[1], s->wt_ev[2], s->wt_ev[3], s->ev1};
         for (int i = 0; i < 5; ++i) HIPCHK(hipEventElapsedTime(&out->weighted_ms[i], seq[i], seq[i + 1]));
     }
+    return RT_OK;
+}
+// Timing of the last rt_render by kernel: {whole frame, render part (megakernel or shade+trace loop), trace kernel launches summed,
+// film gather} in ms, the number of pipeline iterations (0: megakernel) and how many of them were timed.  The events are read once per timed launch:
+// every later call returns the same bits (RtScene::stats_cache), whatever was queued on the stream in between (rt_radiance_device records no event).
+int rt_last_render_stats(RtScene *s, RtRenderStats *out) {
+    if (!s || !out) return fail(RT_EINVAL, "null argument");
+    if (!s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
+    if (!s->stats_cached) {
+        if (int rc = read_render_stats(s, &s->stats_cache)) return rc;
+        s->stats_cached = true;
+    }
+    *out = s->stats_cache;
+    return RT_OK;
+}
+int rt_last_render_ms(RtScene *s, float *total_ms, float *kernel_ms) {
+    if (!s || !s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
+    RtRenderStats st;
+    if (int rc = rt_last_render_stats(s, &st)) return rc;
+    if (total_ms) *total_ms = st.total_ms;        // render kernel(s) + film gather
+    if (kernel_ms) *kernel_ms = st.render_ms;     // rt::render_kernel alone, or the whole shade / trace loop of the queue pipeline
     return RT_OK;
 }
 

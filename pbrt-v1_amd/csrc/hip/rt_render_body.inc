@@ -94,10 +94,28 @@
                     {
                         unsigned long long pixel; int s;
                         bool ok;
-                        if (FX::tile_order || fr.mega_tile > 0) { unsigned px; tile_order_to_sample(fr, unsigned(w), px, s); pixel = px; ok = true; }      // (single shard)
+                        if constexpr (FX::caller_rays) {                  // a query: item w is camera sample q_first + w in scanline order, whatever the ray (one shard, fewer than 2^32 samples)
+                            const unsigned n = fr.q_first + unsigned(w), px = fastdiv(n, fr.div.spp);
+                            pixel = px; s = int(n - px * unsigned(fr.spp)); ok = true;
+                        }
+                        else if (FX::tile_order || fr.mega_tile > 0) { unsigned px; tile_order_to_sample(fr, unsigned(w), px, s); pixel = px; ok = true; }      // (single shard)
                         else ok = work_to_sample(fr, w, pixel, s);
                         if (ok) {
                             Ray ray;
+                            if constexpr (FX::caller_rays) {
+                                ln.work = fr.q_first + uint32_t(w);
+                                // a ray the guard refuses (rt_ray_guard.h) traces nothing -- an infinite light's Le would take its direction -- and counts
+                                // nothing: its result is zero, and the lane asks for work again
+                                if (!setup_sample<FX>(sc, fr, ln, pixel, s, ray, unsigned(w))) query_store(fr, unsigned(w), 0.f, 0.f, 0.f, 0.f);
+                                else {
+                                    ln.L = mk3(0.f); ln.thr = mk3(1.f); ln.alpha = 0.f; ln.depth = 0; ln.fsp = 0;
+                                    ln.specular = false;
+                                    if (COUNT) ++c_cam;
+                                    accel_begin<ACCEL>(ln.tv, sc, ray, false);
+                                    if (VOL) vol_store_ray(fr, 0, gtid, ray);
+                                    ln.has_ray = true; ln.stage = ST_VERTEX;
+                                }
+                            } else {
                             setup_sample<FX>(sc, fr, ln, pixel, s, ray);
                             ln.work = (FX::tile_order || fr.mega_tile > 0) ? uint32_t(pixel * unsigned(fr.spp) + unsigned(s)) : uint32_t(w);
                             if (INTEG == RT_INTEG_DIRECT_WEIGHTED) ln.ord = fr.weighted_phase == 1 ? 0u : RT_GPTR(const unsigned, fr.wt_base)[ln.work];
@@ -108,6 +126,7 @@
                             if (VOL) vol_store_ray(fr, 0, gtid, ray);
                             ln.has_ray = true; ln.stage = ST_VERTEX;
                             if (BYV) ln.vf = BV_B | BV_CUR_B;                 // the camera ray is the "continuation" that leads to the first vertex
+                            }
                         }
                     }
                 }

@@ -576,13 +576,21 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         for (unsigned &n : g.debug) n = std::min(n, others);
         mx = others;
     }
+    {   // the radiance-query kernels carry the code of Mega's EXT entries: they share the scratch every frame shares and never take a larger grid
+        const unsigned others = mx;
+        for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) {
+            if ((rc = resident(*g_radiance_kernels[i], g.rays[i]))) return rc;
+            for (unsigned &n : g.rays[i]) n = std::min(n, others);
+        }
+        mx = others;
+    }
     if ((rc = resident(g_pipe_trace, g.trace, trace_per_cu)) || (rc = resident(g_pipe_march, g.march))) return rc;
     s->n_threads = mx * RT_BLOCK;                               // ... of all: the spill area is shared
     s->spill_depth = s->tree.max_depth > RT_TRACE_STACK ? s->tree.max_depth - RT_TRACE_STACK + 1 : 1;     // RT_TRACE_STACK <= RT_STACK_LDS
     if ((rc = s->work_counter.grow(64))) return rc;             // 8 band counters, one 64-byte line each (the pipeline uses the first)
     if ((rc = s->counters.grow(64))) return rc;                 // 8 RtCounters, 16 RT_PROFILE, 2 x 16 RT_PROFILE_STAGES
     HIPCHK(hipMemsetAsync(s->counters, 0, 64 * sizeof(unsigned long long), s->stream));
-    if ((rc = s->filter_dev.grow(256)) || (rc = s->dev_scene.grow(1)) || (rc = s->dev_frame.grow(1))) return rc;
+    if ((rc = s->filter_dev.grow(256)) || (rc = s->dev_scene.grow(1)) || (rc = s->dev_frame.grow(1)) || (rc = s->query_frame.grow(1))) return rc;
     HIPCHK(hipMemcpy(s->dev_scene, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice));
     HIPCHK(hipEventCreate(&s->ev2.p));
     if ((rc = s->spill.grow(size_t(s->spill_depth) * s->n_threads * 2))) return rc;        // uint4 entries in the pair form, uint2 otherwise
