@@ -481,6 +481,8 @@ typedef struct RtRenderStats {
     float weighted_ms[5];
     int32_t fixed_frame;       /* megakernel: 1 when the frame ran a kernel compiled for its sampler, camera and work order (stratified, n == 1 requests, no lens,
                                 * no environment camera, one shard; same film bit for bit), 0 when it ran the generic kernel */
+    int32_t fixed_scene;       /* ... and non-zero when that kernel was compiled for the scene as well, a bit per axis: 1 the scene's one light, 2 no material with a
+                                * specular lobe (same film bit for bit again); 0 otherwise */
 } RtRenderStats;
 /* ImageFilm::WriteImage's normalisation (image.cpp:157-203) of ANY 5-plane accumulator in device memory (planes of n floats each), e.g. the
  * rows of the film a rank owns after a reduce-scatter; rgb[n][3] and alpha[n] stay on the device.  Asynchronous on the scene's stream. */

@@ -184,15 +184,22 @@ struct DevFrame {
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RT_G __attribute__((address_space(1)))
 #define RT_L __attribute__((address_space(3)))
+// ... and the constant address space, for data no kernel writes (a scene's light records and emitter triangles, a frame's request table): a load from a
+// wave-uniform address there is a scalar load whatever the kernel has stored meanwhile, where the same load through RT_G stays a vector load once
+// the compiler has seen a store it cannot tell apart.  Only the scene twins (fixed::Scene::one_light, rt_fixed_frame.h) read through it.
+#define RT_K __attribute__((address_space(4)))
 #else
 #define RT_G
 #define RT_L
+#define RT_K
 #endif
 typedef const DevMaterial RT_G &MatRef;
 typedef const DevLight RT_G &LightRef;
 #define RT_MAT(sc, i) (*((const DevMaterial RT_G *)(sc).materials + (i)))
 #define RT_LIGHT(sc, i) (*((const DevLight RT_G *)(sc).lights + (i)))
 #define RT_GPTR(T, p) ((T RT_G *)(p))
+#define RT_LIGHT_K(sc) (*((const DevLight RT_K *)(sc).lights))           // the record of a scene's only light
+#define RT_KPTR(T, p) ((T RT_K *)(p))
 
 // Sample-buffer layout (round 3).  Work item w of a shard is sample s = w % spp of the shard's local pixel lp = w / spp (local pixels
 // follow the shard's tiles in order, so on one rank lp is the pixel's scanline index).  64 consecutive local pixels form a chunk stored

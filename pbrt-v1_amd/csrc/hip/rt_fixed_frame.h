@@ -3,7 +3,9 @@
 // wait, a compare and a branch each, and the code of every alternative in every instantiation).  A traits type as their trailing template parameter turns
 // those selections into constants: fixed::Any (the default) is the code as it always was, fixed::Frame the twin for the frames qualifies() admits.  What a
 // fixed kernel still computes are the expressions the generic kernel runs for such a frame, so the films are bit-identical.  The family of the fixed
-// kernels (flavour::Fixed, rt_mega_f.hip) is declared here too.  No HIP header: tests/fixed_frame_host_test.cpp checks the rules with a host compiler.
+// kernels (flavour::Fixed, rt_mega_f.hip) is declared here too, and so are the traits of the scene (fixed::Scene: its one light, its all-matte material
+// table) with the family of their kernels (flavour::FixedScene, rt_mega_fs{d,p}.hip).  No HIP header: tests/fixed_frame_host_test.cpp and
+// tests/fixed_scene_host_test.cpp check the rules with a host compiler.
 #pragma once
 #include "rt_flavour.h"
 
@@ -19,6 +21,13 @@
 #endif
 #ifndef RT_FIXED_TILE_ORDER
 #define RT_FIXED_TILE_ORDER 1
+#endif
+// ... and the two axes of the scene (fixed::Scene below; measurements: profiles/fixed_scene_kernels.txt); scene_qualifies() stays as strict as it is
+#ifndef RT_FIXED_ONE_LIGHT
+#define RT_FIXED_ONE_LIGHT 1
+#endif
+#ifndef RT_FIXED_NO_SPECULAR
+#define RT_FIXED_NO_SPECULAR 1
 #endif
 
 namespace rt {
@@ -74,6 +83,35 @@ constexpr bool qualifies(const Facts &f) {
            !f.counting && !f.ext && !f.vol && f.high_occ;
 }
 
+// ---- the scene.  The stage bodies also ask, in every pass, what the SCENE fixed when it was loaded: which light (a per-lane index into the light
+// records, their triangles and their sample requests, although a scene with one light has one address for all 64 lanes), and whether the material at
+// hand has a specular lobe (three draws and a bsdf_sample_f per direction of the Whitted / DirectLighting recursion, which an all-matte table answers
+// with "no lobe" every time).  A second traits type, the parameter after FX, turns these into constants the same way: fixed::AnyScene (the default) is
+// the code as it was, fixed::Scene<...> the twin for the scenes scene_qualifies() admits.  The two axes are independent.
+struct AnyScene {
+    static constexpr bool one_light = false;         // DevScene::n_lights == 1: the light index is 0 wherever a light, its triangles or its sample requests are read
+    static constexpr bool no_specular = false;       // no material has a specular lobe: no recursion frame is ever pushed, PathIntegrator's specularBounce stays false
+    static constexpr bool accel_known = false;       // launch_ray takes the accelerator from the kernel's ACCEL, not from DevScene::accel_kind
+};
+template <bool ONE_LIGHT, bool NO_SPECULAR> struct Scene {
+    static constexpr bool accel_known = true;
+    static constexpr bool one_light = ONE_LIGHT && RT_FIXED_ONE_LIGHT != 0;
+    static constexpr bool no_specular = NO_SPECULAR && RT_FIXED_NO_SPECULAR != 0;
+};
+enum { SCENE_ONE_LIGHT = 1, SCENE_NO_SPECULAR = 2 };      // a bit per axis: Schedule::fixed_scene, RtRenderStats::fixed_scene
+// what the host knows of the scene's lights and materials (plan::SceneFacts::n_lights, ::specular_materials)
+struct SceneFacts {
+    unsigned n_lights;       // DevScene::n_lights
+    bool specular;           // some material is not matte (mirror, glass: the materials of a scene without EXT code), whether or not its lobes are black
+};
+// The axes of the scene twin a frame takes, or 0: the frame takes a fixed-frame kernel of DirectLighting or Path (the integrators that have scene twins),
+// and the scene has one light -- every twin is compiled for that, with or without "no specular lobe" (flavour::FixedScene)
+constexpr int scene_qualifies(const Facts &f, const SceneFacts &s) {
+    if (!qualifies(f) || (f.integrator != RT_INTEGRATOR_DIRECT && f.integrator != RT_INTEGRATOR_PATH)) return 0;
+    if (s.n_lights != 1u) return 0;
+    return SCENE_ONE_LIGHT | (s.specular ? 0 : SCENE_NO_SPECULAR);
+}
+
 }  // namespace fixed
 
 namespace flavour {
@@ -98,5 +136,33 @@ constexpr bool fixed_round_trips() {
     return true;
 }
 static_assert(fixed_round_trips(), "Fixed: index(request(k)) != k, or entry k is not the twin of a Mega entry");
+
+// rt::render_kernel_scene<..., fixed::Frame, fixed::Scene<...>> (rt_mega_fs{d,p}.hip): the scene twins of Fixed's DirectLighting and Path entries, a table
+// per integrator: entry 2 * grid + (no specular lobe).  Every entry is compiled for one light.
+struct FixedScene {
+    static constexpr int N = 4;
+    static constexpr bool has(int integ) { return integ == RT_INTEGRATOR_DIRECT || integ == RT_INTEGRATOR_PATH; }
+    static constexpr bool has_axes(int axes) { return axes == fixed::SCENE_ONE_LIGHT || axes == (fixed::SCENE_ONE_LIGHT | fixed::SCENE_NO_SPECULAR); }
+    static constexpr int index(const Request &r, int axes) { return (r.grid ? 2 : 0) + ((axes & fixed::SCENE_NO_SPECULAR) ? 1 : 0); }
+    static constexpr int axes(int k) { return fixed::SCENE_ONE_LIGHT | ((k & 1) ? fixed::SCENE_NO_SPECULAR : 0); }
+    static constexpr Flavour flavour(int k) { return Flavour{false, k >> 1, false, false, RT_HIGH_OCC_WAVES, true}; }
+    static constexpr Request request(int k, int integ) { Request r = flavour(k).request(); r.integ = integ; return r; }
+    // ... and the entry of Fixed's table it is the twin of
+    static constexpr int fixed_twin(int k, int integ) { return Fixed::index(request(k, integ)); }
+};
+constexpr bool fixed_scene_round_trips() {
+    for (int integ = RT_INTEGRATOR_WHITTED; integ <= RT_INTEGRATOR_PATH; ++integ) {
+        if (!FixedScene::has(integ)) continue;
+        for (int k = 0; k < FixedScene::N; ++k) {
+            if (FixedScene::index(FixedScene::request(k, integ), FixedScene::axes(k)) != k || !FixedScene::has_axes(FixedScene::axes(k))) return false;
+            const int t = FixedScene::fixed_twin(k, integ);
+            const Flavour g = Fixed::flavour(t), f = FixedScene::flavour(k);
+            if (Fixed::integrator(t) != integ) return false;
+            if (g.count != f.count || g.accel != f.accel || g.vol != f.vol || g.ext != f.ext || g.waves != f.waves || g.high_occ != f.high_occ) return false;
+        }
+    }
+    return true;
+}
+static_assert(fixed_scene_round_trips(), "FixedScene: index(request(k), axes(k)) != k, or entry k is not the twin of a Fixed entry");
 }  // namespace flavour
 }  // namespace rt

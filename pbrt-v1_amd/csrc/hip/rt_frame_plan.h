@@ -52,7 +52,9 @@ struct SceneFacts {
     bool counting = true;                // rt_set_counting
     bool medium = false;                 // RtVolume::present
     unsigned n_lights = 0;
-    std::vector<int> light_samples;      // [n_lights] DevLight::n_samples, as uploaded (>= 1)
+    bool specular_materials = false;     // some material is not matte (mirror, glass; the EXT materials set has_ext): fixed::SceneFacts::specular
+    bool scene_twins = true;             // the scene's frames may take a kernel compiled for its light and materials; scene_create clears it for PBRT_HIP_FIXED_SCENE=0
+    std::vector<int> light_samples;     // [n_lights] DevLight::n_samples, as uploaded (>= 1)
     int light_draws = 0;                 // RandomFloat()s one EstimateDirect draws: the same for every light (0 / 1), or -1 when the lights differ
     float lens_radius = 0.f; int camera_type = RT_CAMERA_PERSPECTIVE;
     float bounds[6] = {0, 0, 0, 0, 0, 0};            // the accelerator's bound (min, max)
@@ -199,6 +201,7 @@ struct Schedule {
     int dbg_x = -1000000, dbg_y = -1000000;
     Extent extent;                       // the caller's, or reset to scanline order for a one-shard megakernel frame
     bool fixed_frame = false;            // render_mega launches the twin compiled for a fixed frame (rt_fixed_frame.h)
+    int fixed_scene = 0;                 // ... and, non-zero, that kernel's twin compiled for the scene too: the axes it fixes (fixed::SCENE_*)
     bool by_vertex = false;              // render_pipeline shades once per path vertex (rt_pipe_vertex.h)
 };
 inline Schedule plan_schedule(const RtRenderDesc &rd, const SceneFacts &sf, const Extent &ext, const Requests &rq, const FrameKnobs &kn) {
@@ -261,9 +264,14 @@ inline Schedule plan_schedule(const RtRenderDesc &rd, const SceneFacts &sf, cons
     if (sc.trav_mode != 3 || sc.high_occupancy) sc.trav_mode = 2;  // (the high-occupancy kernels carry no pooled-leaf scratch)
     // A frame whose sampler, camera, work order and sample requests are what fixed::Frame states takes the twin compiled for them (rt_fixed_frame.h);
     // PBRT_HIP_FIXED_FRAME=0 keeps it on the generic kernel (the films are the same bits: tests/test_gpu_fixed_frame.py)
-    sc.fixed_frame = fixed::qualifies(fixed::Facts{rd.integrator, rd.sampler, weighted, sf.lens_radius, sf.camera_type, ext.shard_count, sc.mega_tile, rq.dims_max_n,
-                                                   sf.counting, sf.has_ext, sf.medium, sc.high_occupancy != 0});
+    const fixed::Facts facts{rd.integrator, rd.sampler, weighted, sf.lens_radius, sf.camera_type, ext.shard_count, sc.mega_tile, rq.dims_max_n,
+                             sf.counting, sf.has_ext, sf.medium, sc.high_occupancy != 0};
+    sc.fixed_frame = fixed::qualifies(facts);
     if (kn.fixed_frame) sc.fixed_frame = sc.fixed_frame && *kn.fixed_frame != 0;
+    // ... and where the scene has one light (and, a second axis, no material with a specular lobe) the twin compiled for that too;
+    // a scene created under PBRT_HIP_FIXED_SCENE=0 (a scene fact, read with the scene's other knobs: it can only turn the twin off) keeps its frames on
+    // the fixed-frame kernel (the same bits again: tests/test_gpu_fixed_scene.py)
+    sc.fixed_scene = sc.fixed_frame && sf.scene_twins ? fixed::scene_qualifies(facts, fixed::SceneFacts{sf.n_lights, sf.specular_materials}) : 0;
     // PathIntegrator without a medium in the queue pipeline: one shade pass per path vertex, all of a vertex's rays in one trace launch (rt_pipe_vertex.h)
     sc.by_vertex = sc.pipeline && rd.integrator == RT_INTEGRATOR_PATH && !sf.medium;
     if (kn.pipe_vertex) sc.by_vertex = sc.by_vertex && *kn.pipe_vertex != 0;
@@ -331,7 +339,7 @@ inline Refusal plan_query(const RtRenderDesc &rd, const QueryRange &q, Schedule 
     if (q.first > samples || q.n > samples - q.first) return refuse(RT_EINVAL, "rt_radiance_device: first + n is beyond the frame's camera samples");
     e.tile_w = e.tile_h = e.tiles_x = 0; e.tile_pixels = 1;
     e.total_work = q.n;
-    sc.pipeline = 0; sc.by_vertex = false; sc.fixed_frame = false; sc.mega_tile = 0;
+    sc.pipeline = 0; sc.by_vertex = false; sc.fixed_frame = false; sc.fixed_scene = 0; sc.mega_tile = 0;
     sc.high_occupancy = 0;                                   // (the natural-allocation kernels carry the pooled-leaf scratch: trav_mode 3 stays where the frame has it)
     return Refusal{};
 }

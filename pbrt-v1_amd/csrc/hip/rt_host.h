@@ -46,6 +46,7 @@ using namespace rt;
 namespace rt {
 extern const flavour::Table<RenderKernelFn, flavour::Mega> g_render_kernels_whitted, g_render_kernels_direct, g_render_kernels_path;
 extern const flavour::Table<RenderKernelFn, flavour::Fixed> g_render_kernels_fixed;        // the fixed-frame twins of six Mega entries (rt_fixed_frame.h), all integrators in one table
+extern const flavour::Table<RenderKernelFn, flavour::FixedScene> g_render_kernels_fixed_scene_direct, g_render_kernels_fixed_scene_path;   // their scene twins (rt_mega_fs{d,p}.hip)
 extern const flavour::Table<RenderKernelFn, flavour::Rays> g_radiance_kernels_whitted, g_radiance_kernels_direct, g_radiance_kernels_path;   // rt_radiance_device (rt_mega_r{w,d,p}.hip)
 extern const flavour::Table<RenderKernelFn, flavour::Weighted> g_render_kernels_weighted;
 extern const flavour::Table<RenderKernelFn, flavour::Bidir> g_render_kernels_bidir;
@@ -57,12 +58,14 @@ extern const flavour::Table<PipeMarchFn, flavour::March> g_pipe_march;
 }  // namespace rt
 // ... by RtRenderDesc::integrator
 static const flavour::Table<RenderKernelFn, flavour::Mega> *const g_render_kernels[RT_INTEGRATOR_PATH + 1] = {&g_render_kernels_whitted, &g_render_kernels_direct, &g_render_kernels_path};
+static const flavour::Table<RenderKernelFn, flavour::FixedScene> *const g_render_kernels_fixed_scene[RT_INTEGRATOR_PATH + 1] = {nullptr, &g_render_kernels_fixed_scene_direct, &g_render_kernels_fixed_scene_path};   // (flavour::FixedScene::has)
 static const flavour::Table<RenderKernelFn, flavour::Rays> *const g_radiance_kernels[RT_INTEGRATOR_PATH + 1] = {&g_radiance_kernels_whitted, &g_radiance_kernels_direct, &g_radiance_kernels_path};
 static const flavour::Table<PipeShadeFn, flavour::Shade> *const g_pipe_shade[RT_INTEGRATOR_PATH + 1] = {&g_pipe_shade_whitted, &g_pipe_shade_direct, &g_pipe_shade_path};
 // The persistent families are launched with as many blocks as stay resident (scene_create): a grid per table entry
 struct ResidentGrids {
     flavour::Table<unsigned, flavour::Mega> mega[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Fixed> fixed;
+    flavour::Table<unsigned, flavour::FixedScene> fixed_scene[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Rays> rays[RT_INTEGRATOR_PATH + 1];
     flavour::Table<unsigned, flavour::Weighted> weighted;
     flavour::Table<unsigned, flavour::Bidir> bidir;
@@ -142,6 +145,7 @@ struct RtScene {
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
     Pinned<unsigned> h_qcount;                          // page-locked mirror of q_count (termination test)
     bool last_fixed = false;                            // the last frame ran a fixed-frame kernel (rt_fixed_frame.h)
+    int last_fixed_scene = 0;                           // ... a scene twin of one: the axes it fixes (fixed::SCENE_*)
     bool last_pipeline = false, last_marches = false; int pipe_iters = 0, pipe_timed = 0; unsigned pipe_slots = 0;
     DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;

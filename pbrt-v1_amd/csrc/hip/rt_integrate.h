@@ -396,10 +396,13 @@ RT_DEV void all_lights_done(Lane &ln) {
 }
 
 // DEFER (queue pipeline, rt_pipeline.h): the ray is only recorded; the trace kernel starts the traversal
-template <bool DEFER = false>
+// ACCEL: the kernel's accelerator where it hands it down (the scene twins, fixed::Scene::accel_known), or -1: DevScene::accel_kind decides
+template <bool DEFER = false, int ACCEL = -1>
 RT_DEV void launch_ray(Lane &ln, const DevScene &sc, V3 o, V3 d, float mint, float maxt, bool any, int next_stage) {
     Ray r; r.o = o; r.d = d; r.mint = mint; r.maxt = maxt;
     if (DEFER) { ln.tv.o = o; ln.tv.d = d; ln.tv.mint = mint; ln.tv.maxt = maxt; ln.tv.any = any; ln.tv.hit_prim = -1; ln.tv.b1 = 0.f; ln.tv.b2 = 0.f; }
+    else if constexpr (ACCEL == RT_ACCEL_GRID) grid_begin(ln.tv, sc, r, any);
+    else if constexpr (ACCEL >= 0) trav_begin(ln.tv, sc, r, any);
     else if (sc.accel_kind == RT_ACCEL_GRID) grid_begin(ln.tv, sc, r, any); else trav_begin(ln.tv, sc, r, any);
     ln.has_ray = true;
     ln.stage = next_stage;
@@ -516,9 +519,22 @@ RT_DEV V3 scene_transmittance(const DevScene &sc, const DevFrame &fr, Lane &ln, 
 // BSDF-sampling half; returns with either a MIS ray in flight (ST_MIS_DONE) or ST_ED_DONE.
 // GEOM_N: EstimateDirect's normal argument is the geometric normal (the bidirectional integrator, bidirectional.cpp:119) instead of bsdf->dgShading.nn;
 // the BSDF keeps its own frame either way
-template <bool EXT, bool DEFER = false, bool GEOM_N = false>
+// SX (rt_fixed_frame.h): the record of light i -- with one light record 0 for every lane, a wave-uniform address read through the constant address space
+// (rt_device.h RT_K: scalar loads, here and in the light's triangles), wherever a light is read
+template <class SX>
+RT_DEV decltype(auto) light_of(const DevScene &sc, int i) {
+    if constexpr (SX::one_light) return (RT_LIGHT_K(sc));
+    else return (RT_LIGHT(sc, i));
+}
+// ... and request k (light sample, BSDF sample, BSDF component) of light li in DirectLighting "all"'s table (DevFrame::light_dims; li < n_lights)
+template <class SX>
+RT_DEV DimReq light_dim(const DevFrame &fr, int li, int k) {
+    if constexpr (SX::one_light) { const DimReq r = RT_KPTR(const DimReq, fr.light_dims)[k]; return r; }
+    else { const DimReq r = (RT_GPTR(const DimReq, fr.light_dims) + 3 * li)[k]; return r; }
+}
+template <bool EXT, bool DEFER = false, bool GEOM_N = false, class SX = fixed::AnyScene, int ACCEL = -1>
 RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
-    LightRef Lt = RT_LIGHT(sc, ln.cur_light);
+    const auto &Lt = light_of<SX>(sc, ln.cur_light);
     ln.stage = ST_ED_DONE;
     if (light_is_delta<EXT>(Lt)) return;                                        // IsDeltaLight()
     MatRef m = RT_MAT(sc, ln.v.mat);
@@ -526,15 +542,15 @@ RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
     V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, ln.bs1, ln.bs2, ln.bcs, bsdfPdf, BX_ALL & ~BX_SPECULAR, sampled);
     if (!is_black(f) && bsdfPdf > 0.f) {
         float lightPdf;
-        if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(GEOM_N ? ln.v.ng : ln.v.nn, wi) : area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
-        else lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);            // (the other kernels' statement, as it was)
+        if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(GEOM_N ? ln.v.ng : ln.v.nn, wi) : area_light_pdf<EXT, SX::one_light>(sc, Lt, ln.v.p, wi);
+        else lightPdf = area_light_pdf<EXT, SX::one_light>(sc, Lt, ln.v.p, wi);            // (the other kernels' statement, as it was)
         if (lightPdf > 0.f) {
             float fw = 1 * bsdfPdf, gw = 1 * lightPdf;                            // PowerHeuristic mc.h:55-59
             float weight = (fw * fw) / (fw * fw + gw * gw);
             // Li is Lemit iff the closest hit is this emitter seen from its front side -- the infinite light's L iff the ray hits nothing
             // (light->Le(ray), transport.cpp:184-185); decided after the trace
             ln.pend = div_s(((f * mat_color(Lt.color)) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn)) * weight, bsdfPdf);
-            launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_MIS_DONE);
+            launch_ray<DEFER, ACCEL>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_MIS_DONE);
         }
     }
 }
@@ -550,11 +566,11 @@ RT_DEV size_t weighted_record(const DevFrame &fr, const Lane &ln, int nLights) {
 }
 
 // light-sampling half
-template <bool EXT, bool DEFER = false, bool GEOM_N = false>
+template <bool EXT, bool DEFER = false, bool GEOM_N = false, class SX = fixed::AnyScene, int ACCEL = -1>
 RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float ls1, float ls2) {
     ln.cur_light = light;
     ln.Ld = mk3(0.f);
-    LightRef Lt = RT_LIGHT(sc, light);
+    const auto &Lt = light_of<SX>(sc, light);
     MatRef m = RT_MAT(sc, ln.v.mat);
     V3 wi, Li, sd; float lightPdf, smax;
     if (light_is_delta<EXT>(Lt)) {                                              // point.cpp:61-66, spot.cpp:80-84, distant.cpp:63-67
@@ -567,17 +583,17 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
             sd = wi; smax = RT_INF;
         } else {                                                                // area.cpp:58-68
             V3 ns;
-            V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
+            V3 ps = area_sample_point<EXT, SX::one_light>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
             wi = normalize3(ps - ln.v.p);
-            lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+            lightPdf = area_light_pdf<EXT, SX::one_light>(sc, Lt, ln.v.p, wi);
             Li = area_L(Lt, ns, -wi);
             sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
         }
     } else {                                                                    // area.cpp:58-68
         V3 ns;
-        V3 ps = area_sample_point<EXT>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
+        V3 ps = area_sample_point<EXT, SX::one_light>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
         wi = normalize3(ps - ln.v.p);
-        lightPdf = area_light_pdf<EXT>(sc, Lt, ln.v.p, wi);
+        lightPdf = area_light_pdf<EXT, SX::one_light>(sc, Lt, ln.v.p, wi);
         Li = area_L(Lt, ns, -wi);
         sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
     }
@@ -592,7 +608,7 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
                 ln.pend = div_s(((f * Li) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn)) * weight, lightPdf);
             }
             // VisibilityTester::SetSegment / SetRay light.h:78-83
-            launch_ray<DEFER>(ln, sc, ln.v.p, sd, RT_RAY_EPSILON, smax, true, ST_SHADOW_DONE);
+            launch_ray<DEFER, ACCEL>(ln, sc, ln.v.p, sd, RT_RAY_EPSILON, smax, true, ST_SHADOW_DONE);
             return;
         }
     }
@@ -761,7 +777,7 @@ RT_DEV void debug_vertex(const DevScene &sc, const DevFrame &fr, Lane &ln, unsig
 }
 
 // The body of ONE stage.  Returns when the lane has a ray in flight or has changed stage.
-template <bool COUNT, int INTEG_, bool VOL, bool EXT, int STAGE, bool DEFER = false, bool PARK = false, class FX = fixed::Any>
+template <bool COUNT, int INTEG_, bool VOL, bool EXT, int STAGE, bool DEFER = false, bool PARK = false, class FX = fixed::Any, class SX = fixed::AnyScene, int ACCEL = -1>
 RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid,
                        unsigned *c_closest, unsigned *c_any, unsigned *c_bad) {
     // RT_INTEG_DIRECT_WEIGHTED: DirectLighting with strategy "weighted", a kernel family of its own so that the all / one kernels keep their code
@@ -793,8 +809,8 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
 #endif
             if (ln.depth == 0) { ln.alpha = 1.f; if (VOL) vol_ray_ptr(fr, 0, gtid)[7 * size_t(fr.n_threads)] = ln.tv.maxt; }   // r.maxt = ray.maxt
             else if (VOL) ln.thr = ln.thr * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);           // path.cpp:89
-            if ((ln.depth == 0 || ln.specular) && ln.v.light >= 0)              // path.cpp:91-92
-                ln.L = ln.L + ln.thr * area_L(RT_LIGHT(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);   // isect.Le: dg.nn, the geometric normal
+            if ((ln.depth == 0 || (!SX::no_specular && ln.specular)) && ln.v.light >= 0)              // path.cpp:91-92
+                ln.L = ln.L + ln.thr * area_L(light_of<SX>(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);   // isect.Le: dg.nn, the geometric normal
         } else {
             if (!hit) {                                                         // whitted.cpp:52-59, directlighting.cpp:186-191
                 ln.L = mk3(0.f);
@@ -812,14 +828,14 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             if (ln.depth == 0) ln.alpha = 1.f;
             if (VOL) vol_ray_ptr(fr, ln.fsp, gtid)[7 * size_t(fr.n_threads)] = ln.tv.maxt;       // the hit shortens this level's ray
             ln.L = mk3(0.f);
-            if (ln.v.light >= 0) ln.L = ln.L + area_L(RT_LIGHT(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);
+            if (ln.v.light >= 0) ln.L = ln.L + area_L(light_of<SX>(sc, ln.v.light), vertex_ng<EXT>(ln.v), ln.v.wo);
         }
         ln.li = 0; ln.lj = 0; ln.L_all = mk3(0.f); ln.Ld_light = mk3(0.f);
         ln.stage = ST_DIRECT_NEXT;
         return;
     }
     if constexpr (STAGE == ST_DIRECT_NEXT) {
-        const int nLights = int(sc.n_lights);
+        const int nLights = SX::one_light ? 1 : int(sc.n_lights);
         if constexpr (WEIGHTED) {
             // WeightedSampleOneLight transport.cpp:71-122, sample offsets of directlighting.cpp:54-64 -- see rt_weighted.h for the three passes
             if (nLights == 0) { ln.stage = ST_SPECULAR; return; }                                   // directlighting.cpp:106
@@ -867,20 +883,19 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
                 ls1 = ln.rng.next_float(); ls2 = ln.rng.next_float();           // transport.cpp:141-145
                 ln.bs1 = ln.rng.next_float(); ln.bs2 = ln.rng.next_float(); ln.bcs = ln.rng.next_float();
             }
-            int lightNum = min(int(floorf(un * nLights)), nLights - 1);
-            estimate_direct_begin<EXT, DEFER>(sc, ln, lightNum, ls1, ls2);
+            int lightNum = SX::one_light ? 0 : min(int(floorf(un * nLights)), nLights - 1);     // (un is in [0, 1): one light is light 0; its draw still moves the counter)
+            estimate_direct_begin<EXT, DEFER, false, SX, ACCEL>(sc, ln, lightNum, ls1, ls2);
             return;
         }
         if (INTEG == RT_INTEGRATOR_DIRECT) {
             // UniformSampleAllLights transport.cpp:31-50 with the dimensions of directlighting.cpp:46-53
             if (ln.li >= nLights) { all_lights_done(ln); return; }
-            const DimReq RT_G *ld = RT_GPTR(const DimReq, fr.light_dims) + 3 * ln.li;
-            const DimReq rl = ld[0], rb = ld[1], rc = ld[2];
+            const DimReq rl = light_dim<SX>(fr, ln.li, 0), rb = light_dim<SX>(fr, ln.li, 1), rc = light_dim<SX>(fr, ln.li, 2);
             if (ln.lj == 0) ln.Ld_light = mk3(0.f);
             const float ls1 = dim_value<FX>(fr, ln, rl, ln.lj, 0), ls2 = dim_value<FX>(fr, ln, rl, ln.lj, 1);
             ln.bs1 = dim_value<FX>(fr, ln, rb, ln.lj, 0); ln.bs2 = dim_value<FX>(fr, ln, rb, ln.lj, 1);
             ln.bcs = dim_value<FX>(fr, ln, rc, ln.lj, 0);
-            estimate_direct_begin<EXT, DEFER>(sc, ln, ln.li, ls1, ls2);
+            estimate_direct_begin<EXT, DEFER, false, SX, ACCEL>(sc, ln, SX::one_light ? 0 : ln.li, ls1, ls2);
             return;
         }
         // Whitted: one sample per light, unweighted (whitted.cpp:73-81)
@@ -938,7 +953,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         return;
     }
     if constexpr (STAGE == ST_ED_BSDF) {
-        estimate_direct_bsdf<EXT, DEFER>(sc, ln);
+        estimate_direct_bsdf<EXT, DEFER, false, SX, ACCEL>(sc, ln);
         return;
     }
     if constexpr (STAGE == ST_MIS_DONE) {
@@ -946,7 +961,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         if (ln.tv.hit_prim >= 0) {                                              // transport.cpp:180-184
             V3 nh; int light;
             prim_normal_light<EXT>(sc, ln.tv, nh, light);
-            if (light == ln.cur_light) {
+            if (light == (SX::one_light ? 0 : ln.cur_light)) {
                 if (dot3(nh, -ln.tv.d) > 0)                                    // isect.Le(-wi) non-black; transport.cpp:188-190
                     ln.Ld = ln.Ld + ln.pend * scene_transmittance<VOL, EXT>(sc, fr, ln, ln.tv.o, ln.tv.d, ln.tv.mint, ln.tv.maxt);
             }
@@ -959,7 +974,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         return;
     }
     if constexpr (STAGE == ST_ED_DONE) {
-        const int nLights = int(sc.n_lights);
+        const int nLights = SX::one_light ? 1 : int(sc.n_lights);
         if constexpr (WEIGHTED) {
             if (fr.weighted_phase == 2) {                                       // survey: what L.y() would be had this light been the chosen one
                 const unsigned at = fr.wt_mixed ? __float_as_uint(ln.wt_w) : 1u + 2u * unsigned(ln.li);
@@ -987,7 +1002,13 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             ln.stage = ST_SPECULAR;
         } else {
             ln.Ld_light = ln.Ld_light + ln.Ld;
-            const int ns = FX::all_n1 ? 1 : int(RT_GPTR(const DimReq, fr.light_dims)[3 * ln.li].n);
+            if constexpr (SX::one_light && FX::all_n1) {                        // one light, one sample (li == 0, lj == 0): this is the loop's only round
+                ln.L_all = ln.L_all + ln.Ld_light * (1.f / float(1));
+                ln.lj = 0; ln.li = 1;
+                all_lights_done(ln);
+                return;
+            }
+            const int ns = FX::all_n1 ? 1 : SX::one_light ? int(RT_KPTR(const DimReq, fr.light_dims)[0].n) : int(RT_GPTR(const DimReq, fr.light_dims)[3 * ln.li].n);
             if (++ln.lj >= ns) {
                 ln.L_all = ln.L_all + ln.Ld_light * (1.f / float(ns));           // L += Ld / nSamples
                 ln.lj = 0; ++ln.li;
@@ -1010,7 +1031,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         V3 wi; float pdf; int flags;
         V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, bs1, bs2, bcs, pdf, BX_ALL, flags);
         if (is_black(f) || pdf == 0.f) { ln.stage = ST_RETURN; return; }
-        ln.specular = (flags & BX_SPECULAR) != 0;
+        ln.specular = !SX::no_specular && (flags & BX_SPECULAR) != 0;
         ln.thr = ln.thr * div_s(f * absdot3(wi, ln.v.nn), pdf);
         if (k > 3) {
             if (ln.rng.next_float() > .5f) { ln.stage = ST_RETURN; return; }
@@ -1018,7 +1039,22 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         }
         if (k == fr.max_depth) { ln.stage = ST_RETURN; return; }
         ++ln.depth;
-        launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
+        launch_ray<DEFER, ACCEL>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
+        return;
+    }
+    // SX::no_specular: no material has a specular lobe, bsdf_sample_f answers "no lobe" (f black, pdf 0) to both requests below and nothing is pushed --
+    // what is left of the two stages are the three draws each makes for its arguments, where the generic code makes them
+    if constexpr (STAGE == ST_SPECULAR && SX::no_specular) {
+        if (!(ln.depth < fr.max_depth)) { ln.stage = ST_RETURN; return; }
+        ln.rng.ctr += 3u;
+        ln.stage = ST_SPEC_TRANS;
+        return;
+    } else if constexpr (STAGE == ST_SPEC_TRANS && SX::no_specular) {
+        ln.rng.ctr += 3u;
+        ln.stage = ST_RETURN;
+        return;
+    } else if constexpr (STAGE == ST_POP && SX::no_specular && !VOL) {          // fsp == 0: no frame is ever pushed
+        ln.stage = ST_FINISH;
         return;
     }
     if constexpr (STAGE == ST_SPECULAR) {                                                         // whitted.cpp:82-109
@@ -1032,7 +1068,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         if (!is_black(f) && ad > 0.f) {
             frame_push<EXT>(fr, ln, gtid, f, ad, ST_SPEC_TRANS);
             ++ln.depth;
-            launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
+            launch_ray<DEFER, ACCEL>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
             if (VOL) { Ray cr; cr.o = ln.v.p; cr.d = wi; cr.mint = RT_RAY_EPSILON; cr.maxt = RT_INF; vol_store_ray(fr, ln.fsp, gtid, cr); }
             return;
         }
@@ -1049,7 +1085,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
         if (!is_black(f) && ad > 0.f) {
             frame_push<EXT>(fr, ln, gtid, f, ad, ST_RETURN);
             ++ln.depth;
-            launch_ray<DEFER>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
+            launch_ray<DEFER, ACCEL>(ln, sc, ln.v.p, wi, RT_RAY_EPSILON, RT_INF, false, ST_VERTEX);
             if (VOL) { Ray cr; cr.o = ln.v.p; cr.d = wi; cr.mint = RT_RAY_EPSILON; cr.maxt = RT_INF; vol_store_ray(fr, ln.fsp, gtid, cr); }
             return;
         }
@@ -1120,7 +1156,7 @@ enum { BV_S = 1u, BV_M = 2u, BV_B = 4u, BV_ED = 8u,            // the vertex has
        BV_CUR_S = 64u, BV_CUR_M = 128u, BV_CUR_B = 256u,        // the ray in flight
        BV_S_CLEAR = 512u, BV_M_LIT = 1024u };                   // results: the shadow ray was unoccluded; the MIS ray hit the sampled emitter from its front
 // what the ray that has just ended says (transport.cpp:152-156, :180-190)
-template <bool COUNT, bool EXT>
+template <bool COUNT, bool EXT, class SX = fixed::AnyScene>
 RT_DEV void byv_ray_result(const DevScene &sc, Lane &ln, unsigned *c_closest, unsigned *c_any) {
     if (ln.vf & BV_CUR_S) {
         if (COUNT) ++*c_any;
@@ -1130,28 +1166,28 @@ RT_DEV void byv_ray_result(const DevScene &sc, Lane &ln, unsigned *c_closest, un
         if (ln.tv.hit_prim >= 0) {
             V3 nh; int light;
             prim_normal_light<EXT>(sc, ln.tv, nh, light);
-            if (light == ln.cur_light && dot3(nh, -ln.tv.d) > 0) ln.vf |= BV_M_LIT;
+            if (light == (SX::one_light ? 0 : ln.cur_light) && dot3(nh, -ln.tv.d) > 0) ln.vf |= BV_M_LIT;
         }
     }
     ln.vf &= ~(BV_CUR_S | BV_CUR_M | BV_CUR_B);
 }
 // inside the traversal loop: the lane's ray has ended and its vertex has another one waiting
-template <bool COUNT, int ACCEL, bool EXT>
+template <bool COUNT, int ACCEL, bool EXT, class SX = fixed::AnyScene>
 RT_DEV void byv_ray_advance(const DevScene &sc, Lane &ln, unsigned *c_closest, unsigned *c_any) {
-    byv_ray_result<COUNT, EXT>(sc, ln, c_closest, c_any);
+    byv_ray_result<COUNT, EXT, SX>(sc, ln, c_closest, c_any);
     Ray r; r.o = ln.tv.o; r.mint = RT_RAY_EPSILON; r.maxt = RT_INF;
     if (ln.vf & BV_QM) { r.d = ln.dM; ln.vf = (ln.vf & ~BV_QM) | BV_CUR_M; }
     else { r.d = ln.dB; ln.vf = (ln.vf & ~BV_QB) | BV_CUR_B; }
     if (ACCEL == RT_ACCEL_GRID) grid_begin(ln.tv, sc, r, false); else trav_begin(ln.tv, sc, r, false);
 }
 // one pass: every lane without a ray finishes its previous vertex and runs its next one up to its rays (or ends the path: ST_FETCH)
-template <bool COUNT, int ACCEL, bool EXT, class FX = fixed::Any>
+template <bool COUNT, int ACCEL, bool EXT, class FX = fixed::Any, class SX = fixed::AnyScene>
 RT_DEV void advance_pass_byv(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid, unsigned *c_closest, unsigned *c_any, unsigned *c_bad) {
     constexpr int INTEG = RT_INTEGRATOR_PATH;
-#define RT_BV_BODY(S) stage_body<COUNT, INTEG, false, EXT, S, true, false, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
-    const int nLights = int(sc.n_lights);
+#define RT_BV_BODY(S) stage_body<COUNT, INTEG, false, EXT, S, true, false, FX, SX>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
+    const int nLights = SX::one_light ? 1 : int(sc.n_lights);
     if (!ln.has_ray && (ln.stage == ST_VERTEX || ln.stage == ST_ED_DONE)) {
-        byv_ray_result<COUNT, EXT>(sc, ln, c_closest, c_any);          // the vertex's last ray (the earlier ones were read when the next ray started)
+        byv_ray_result<COUNT, EXT, SX>(sc, ln, c_closest, c_any);         // the vertex's last ray (the earlier ones were read when the next ray started)
         if (ln.vf & BV_ED) {                                            // the two halves of EstimateDirect, then path.cpp:99-110
             V3 Ld = mk3(0.f);                                           // transport.cpp:127
             if (ln.vf & BV_S_CLEAR) Ld = Ld + ln.pendS * mk3(1.f);      // Transmittance = 1 (no medium)
@@ -1217,16 +1253,16 @@ RT_DEV bool stage_in_phase(int stage, int phase) {
 }
 // PARK (queue pipeline with a medium): only the head of a ray march is run here (march_begin) -- the lane then sits in ST_VOL_STEP without a ray
 // and its steps are run by rt::pipe_march_kernel (rt_pipe_march.h), which hands it back in ST_POP.
-template <bool COUNT, int INTEG_, bool VOL, bool EXT, bool DEFER = false, bool PARK = false, class FX = fixed::Any>
+template <bool COUNT, int INTEG_, bool VOL, bool EXT, bool DEFER = false, bool PARK = false, class FX = fixed::Any, class SX = fixed::AnyScene, int ACCEL = -1>
 RT_DEV void advance_pass(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigned gtid,
                          unsigned *c_closest, unsigned *c_any, unsigned *c_bad, int phase) {
     constexpr int INTEG = INTEG_ == RT_INTEG_DIRECT_WEIGHTED ? int(RT_INTEGRATOR_DIRECT) : INTEG_;
 #ifdef RT_PROFILE_STAGES
 #define RT_RUN(S) { const unsigned long long m_ = __ballot(!ln.has_ray && ln.stage == S); if (m_) { const unsigned long long t_ = __builtin_readcyclecounter(); \
-        if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad); \
+        if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX, SX, ACCEL>(sc, fr, ln, gtid, c_closest, c_any, c_bad); \
         if (__lane_id() == 0) { atomicAdd(fr.counters + 24 + 2 * S, __builtin_readcyclecounter() - t_); atomicAdd(fr.counters + 24 + 2 * S + 1, (unsigned long long)__popcll(m_) | (1ull << 40)); } } }
 #else
-#define RT_RUN(S) if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
+#define RT_RUN(S) if (!ln.has_ray && ln.stage == S) stage_body<COUNT, INTEG_, VOL, EXT, S, DEFER, PARK, FX, SX, ACCEL>(sc, fr, ln, gtid, c_closest, c_any, c_bad)
 #endif
     if constexpr (INTEG_ == RT_INTEGRATOR_DEBUG) {            // one camera ray per sample: its hit data, then Scene::Li's medium and the sample record
         RT_RUN(ST_VERTEX);

@@ -215,10 +215,14 @@ static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const p
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
     const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
     const bool fixed_frame = sc.fixed_frame;      // the twin compiled for a fixed frame (rt_fixed_frame.h), where plan_schedule found that the frame qualifies
-    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : fixed_frame ? flavour::Fixed::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
-    const unsigned grid = debug ? s->grids.debug[k] : fixed_frame ? s->grids.fixed[k] : s->grids.mega[rd->integrator][k];
-    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : fixed_frame ? g_render_kernels_fixed[k] : (*g_render_kernels[rd->integrator])[k];
-    s->last_fixed = fixed_frame;
+    // ... and that kernel's twin compiled for the scene's one light (and all-matte material table) as well, where the schedule names its axes
+    const int scene_axes = fixed_frame && !debug && flavour::FixedScene::has(rd->integrator) && flavour::FixedScene::has_axes(sc.fixed_scene) ? sc.fixed_scene : 0;
+    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : scene_axes ? flavour::FixedScene::index(request_of(s, rd, &fr), scene_axes)
+                : fixed_frame ? flavour::Fixed::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
+    const unsigned grid = debug ? s->grids.debug[k] : scene_axes ? s->grids.fixed_scene[rd->integrator][k] : fixed_frame ? s->grids.fixed[k] : s->grids.mega[rd->integrator][k];
+    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : scene_axes ? (*g_render_kernels_fixed_scene[rd->integrator])[k]
+                                : fixed_frame ? g_render_kernels_fixed[k] : (*g_render_kernels[rd->integrator])[k];
+    s->last_fixed = fixed_frame; s->last_fixed_scene = scene_axes;
     if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
 #ifdef RT_TAIL_PROBE
     static unsigned long long *probe = nullptr;
@@ -694,6 +698,7 @@ static int read_render_stats(RtScene *s, RtRenderStats *out) {
     } else out->trace_ms = out->render_ms;
     out->bands = s->last_pipeline ? 0 : 1;
     out->fixed_frame = s->last_fixed ? 1 : 0;
+    out->fixed_scene = s->last_fixed ? s->last_fixed_scene : 0;
     if (s->last_weighted) {
         out->weighted_points = s->wt_points;
         hipEvent_t seq[6] = {s->ev0, s->wt_ev[0], s->wt_ev[1], s->wt_ev[2], s->wt_ev[3], s->ev1};

@@ -1,0 +1,4 @@
+// rt_mega_fsd.hip -- the scene twins of the fixed-frame kernels (rt_fixed_frame.h, flavour::FixedScene) for integrator 1 (1 directlighting, 2 path)
+#define RT_TU_INTEG 1
+#define RT_TU_TABLE g_render_kernels_fixed_scene_direct
+#include "rt_mega_fs_tu.inc"

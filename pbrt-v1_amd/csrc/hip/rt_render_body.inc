@@ -1,5 +1,5 @@
 // rt_render_body.inc -- the body of rt::render_kernel and rt::render_kernel_fixed (rt_render_kernel.h includes it into both): needs the template
-// arguments COUNT, INTEG, ACCEL, VOL, MINW, EXT, the traits FX (rt_fixed_frame.h) and the parameters scp, frp in scope.
+// arguments COUNT, INTEG, ACCEL, VOL, MINW, EXT, the traits FX and SX (rt_fixed_frame.h: the frame's, the scene's) and the parameters scp, frp in scope.
     __shared__ uint2 lds_stack[RT_STACK_LDS * RT_BLOCK];
     constexpr bool POOL = MINW < RT_HIGH_OCC_WAVES;                       // the pooled-leaf scratch (19 KB) is only carried by the kernels that use it
     constexpr int PN = POOL ? RT_BLOCK : 64;
@@ -49,8 +49,8 @@
         // ---- shade / regenerate: run every lane that is not waiting on a ray until it is (or is out of work)
         do {
             RT_PF(++pf_inner;)
-            if constexpr (BYV) advance_pass_byv<COUNT, ACCEL, EXT, FX>(sc, fr, ln, gtid, &c_closest, &c_any, &c_bad);
-            else advance_pass<COUNT, INTEG, VOL, EXT, false, false, FX>(sc, fr, ln, gtid, &c_closest, &c_any, &c_bad, phase);
+            if constexpr (BYV) advance_pass_byv<COUNT, ACCEL, EXT, FX, SX>(sc, fr, ln, gtid, &c_closest, &c_any, &c_bad);
+            else advance_pass<COUNT, INTEG, VOL, EXT, false, false, FX, SX, SX::accel_known ? ACCEL : -1>(sc, fr, ln, gtid, &c_closest, &c_any, &c_bad, phase);
             const unsigned long long want = phase == 0 ? 0ull : __ballot(!ln.has_ray && ln.stage == ST_FETCH);
             if (want) {                                                   // work fetch from the wave's private chunk of the sample list
                 // One device-scope counter serves ~6-8 ns per atomic whoever asks (measured through the trace kernel's refill rate,
@@ -143,7 +143,7 @@
         for (;;) {
             if constexpr (BYV) {                                          // a lane whose ray has ended starts its vertex's next ray here, without a shading pass
                 const bool next = ln.has_ray && !ln.tv.active && (ln.vf & (BV_QM | BV_QB)) != 0u;
-                if (__any(next)) { if (next) byv_ray_advance<COUNT, ACCEL, EXT>(sc, ln, &c_closest, &c_any); }       // (always at once: a lane left waiting here counts as "idle" for the exit test below)
+                if (__any(next)) { if (next) byv_ray_advance<COUNT, ACCEL, EXT, SX>(sc, ln, &c_closest, &c_any); }       // (always at once: a lane left waiting here counts as "idle" for the exit test below)
             }
             const bool act = ln.has_ray && ln.tv.active;
             const unsigned long long am = __ballot(act);

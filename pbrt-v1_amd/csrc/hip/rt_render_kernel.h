@@ -53,11 +53,19 @@ template <bool COUNT, int INTEG, int ACCEL, bool VOL, int MINW, bool EXT>
 __global__ __launch_bounds__(RT_BLOCK, (EXT && COUNT && INTEG == RT_INTEGRATOR_PATH && ACCEL == RT_ACCEL_GRID && !VOL && MINW < 3) ? 3 : MINW) void render_kernel(const DevScene *__restrict__ scp,
                                                                        const DevFrame *__restrict__ frp) {
     using FX = fixed::Any;
+    using SX = fixed::AnyScene;
 #include "rt_render_body.inc"
 }
 // the twin of render_kernel<COUNT, INTEG, ACCEL, VOL, MINW, EXT> for the frames FX describes (flavour::Fixed, rt_mega_f.hip)
 template <bool COUNT, int INTEG, int ACCEL, bool VOL, int MINW, bool EXT, class FX>
 __global__ __launch_bounds__(RT_BLOCK, MINW) void render_kernel_fixed(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp) {
+    using SX = fixed::AnyScene;
+#include "rt_render_body.inc"
+}
+// ... and the twin of render_kernel_fixed<..., FX> for the scenes SX describes (flavour::FixedScene, rt_mega_fs{d,p}.hip): a kernel of its own name, so that
+// the fixed-frame kernels keep theirs
+template <bool COUNT, int INTEG, int ACCEL, bool VOL, int MINW, bool EXT, class FX, class SX>
+__global__ __launch_bounds__(RT_BLOCK, MINW) void render_kernel_scene(const DevScene *__restrict__ scp, const DevFrame *__restrict__ frp) {
 #include "rt_render_body.inc"
 }
 

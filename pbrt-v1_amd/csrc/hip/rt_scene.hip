@@ -466,8 +466,10 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         if (m.type < RT_MAT_MATTE || m.type > RT_MAT_TRANSLUCENT) return fail(RT_EINVAL, "rt_scene_create: unknown material type");
         rt_material_resolve(&m, &mats[i]);                                        // include/pbrt_hip_texture.h: what the EXT kernels do per hit for a textured material
         if (m.type >= RT_MAT_PLASTIC) s->facts.has_ext = true;                           // plastic, uber, shinymetal, translucent: their lobes exist only in the EXT kernels
+        if (m.type != RT_MAT_MATTE) s->facts.specular_materials = true;                  // mirror, glass (and the EXT materials): fixed::Scene's "no specular lobe" does not hold
     }
-    s->materials_host = mats;                                                      // rt_scene_set_textures / rt_render: the records move when room for resolved ones is added
+    if (const char *e = knob("PBRT_HIP_FIXED_SCENE")) s->facts.scene_twins = std::atoi(e) != 0;   // 0: this scene's frames take no scene twin (rt_fixed_frame.h); no value forces one
+    s->materials_host = mats;                                                     // rt_scene_set_textures / rt_render: the records move when room for resolved ones is added
     if ((rc = upload(s, mats.data(), mats.size(), &s->dev.materials))) return rc;
 
     // lights + emitter triangles with ShapeSet area CDF (shape.h:122-135)
@@ -565,6 +567,11 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         const unsigned others = mx;
         if ((rc = resident(g_render_kernels_fixed, g.fixed))) return rc;
         for (int k = 0; k < flavour::Fixed::N; ++k) g.fixed[k] = std::min(g.fixed[k], g.mega[flavour::Fixed::integrator(k)][flavour::Fixed::generic(k)]);
+        for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) {        // ... and a scene twin never a larger one than its fixed-frame twin's
+            if (!flavour::FixedScene::has(i)) { g.fixed_scene[i].fill(0u); continue; }
+            if ((rc = resident(*g_render_kernels_fixed_scene[i], g.fixed_scene[i]))) return rc;
+            for (int k = 0; k < flavour::FixedScene::N; ++k) g.fixed_scene[i][k] = std::min(g.fixed_scene[i][k], g.fixed[flavour::FixedScene::fixed_twin(k, i)]);
+        }
         mx = others;
     }
     if ((rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir))) return rc;

@@ -488,21 +488,30 @@ RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, fl
 }
 
 // ---- lights ------------------------------------------------------------------------------
+// K (here and below): the light is the scene's only one (fixed::Scene::one_light) -- its record and its triangles are read through the constant address
+// space (rt_device.h RT_K: scalar loads); the light's record comes as LT, a DevLight in whichever address space the caller read it from
+template <bool K = false>
 RT_DEV void light_tri(const DevScene &sc, unsigned k, V3 &p1, V3 &p2, V3 &p3) {
+    if constexpr (K) {
+        const float RT_K *t = RT_KPTR(const float, sc.light_tris) + size_t(k) * 16;
+        p1 = mk3(t[0], t[1], t[2]); p2 = mk3(t[3], t[4], t[5]); p3 = mk3(t[6], t[7], t[8]);
+    } else {
     const float RT_G *t = RT_GPTR(const float, sc.light_tris) + size_t(k) * 16;
     p1 = mk3(t[0], t[1], t[2]); p2 = mk3(t[3], t[4], t[5]); p3 = mk3(t[6], t[7], t[8]);
+    }
 }
 
 // ---- delta lights: {Point,Spot,Distant}Light::Sample_L(p, &wi, &visibility) (point.cpp:55-60, spot.cpp:61-79,
 // distant.cpp:57-62).  Returns the incident radiance; `sd`, `smax` = the visibility ray's direction and maxt
 // (SetSegment: p -> light position, maxt 1 - eps; SetRay: p along wi, unbounded; light.h:78-83).
 // (IsDeltaLight(): the area light says no, and -- in the EXT kernels, the only ones a scene with one runs -- the infinite light, infinite.cpp:45)
-template <bool EXT> RT_DEV bool light_is_infinite(LightRef Lt) { return EXT && Lt.type == RT_LIGHT_INFINITE; }
-template <bool EXT> RT_DEV bool light_is_delta(LightRef Lt) {
+template <bool EXT, class LT> RT_DEV bool light_is_infinite(const LT &Lt) { return EXT && Lt.type == RT_LIGHT_INFINITE; }
+template <bool EXT, class LT> RT_DEV bool light_is_delta(const LT &Lt) {
     if constexpr (EXT) return Lt.type != RT_LIGHT_AREA && Lt.type != RT_LIGHT_INFINITE;
     else return Lt.type != RT_LIGHT_AREA;
 }
-RT_DEV V3 delta_light_sample(LightRef Lt, V3 p, V3 &wi, V3 &sd, float &smax) {
+template <class LT>
+RT_DEV V3 delta_light_sample(const LT &Lt, V3 p, V3 &wi, V3 &sd, float &smax) {
     if (Lt.type == RT_LIGHT_DISTANT) {
         wi = mk3(Lt.dir[0], Lt.dir[1], Lt.dir[2]);
         sd = wi; smax = RT_INF;
@@ -641,17 +650,22 @@ RT_DEV float quadric_light_pdf(const DevScene &sc, unsigned qi, V3 p, V3 wi) {  
 
 // Shape::Pdf(p, wi) shape.h:96-107 evaluated on the emitter's own triangles:
 // ShapeSet::Intersect (shape.h:150-156) keeps the LAST triangle hit, the ray's maxt is never shortened.
-template <bool EXT>
-RT_DEV float area_light_pdf(const DevScene &sc, LightRef L, V3 p, V3 wi) {
+template <bool EXT, bool K = false, class LT>
+RT_DEV float area_light_pdf(const DevScene &sc, const LT &L, V3 p, V3 wi) {
     if (EXT && L.quadric >= 0) return quadric_light_pdf(sc, unsigned(L.quadric), p, wi);
     bool any = false; float thit = 0.f; V3 nl = mk3(0.f);
     for (unsigned k = 0; k < L.n_tris; ++k) {
-        V3 p1, p2, p3; light_tri(sc, L.first_tri + k, p1, p2, p3);
+        V3 p1, p2, p3; light_tri<K>(sc, L.first_tri + k, p1, p2, p3);
         float t, b1, b2;
         if (tri_test(p1, p2 - p1, p3 - p1, p, wi, RT_RAY_EPSILON, RT_INF, t, b1, b2)) {
             any = true; thit = t;
+            if constexpr (K) {
+                const float RT_K *ltr = RT_KPTR(const float, sc.light_tris) + size_t(L.first_tri + k) * 16;
+                nl = mk3(ltr[12], ltr[13], ltr[14]);
+            } else {
             const float RT_G *ltr = RT_GPTR(const float, sc.light_tris) + size_t(L.first_tri + k) * 16;
             nl = mk3(ltr[12], ltr[13], ltr[14]);             // tri_frame() of the emitter triangle, precomputed
+            }
         }
     }
     if (!any) return 0.f;
@@ -664,20 +678,23 @@ RT_DEV float area_light_pdf(const DevScene &sc, LightRef L, V3 p, V3 wi) {
 }
 
 // AreaLight::L light.h:93-96
-RT_DEV V3 area_L(LightRef L, V3 n, V3 w) { return dot3(n, w) > 0 ? mat_color(L.color) : mk3(0.f); }
+template <class LT> RT_DEV V3 area_L(const LT &L, V3 n, V3 w) { return dot3(n, w) > 0 ? mat_color(L.color) : mk3(0.f); }
 
 // shape->Sample(p,u1,u2,&ns): ShapeSet::Sample shape.h:115-121 (one extra RandomFloat when the emitter has
 // more than one triangle) + Triangle::Sample trianglemesh.cpp:336-349 + UniformSampleTriangle mc.cpp:136-141
-template <bool EXT, class RNG>
-RT_DEV V3 area_sample_point(const DevScene &sc, LightRef L, V3 pref, float u1, float u2, RNG &rng, V3 &ns) {
+template <bool EXT, bool K = false, class LT, class RNG>
+RT_DEV V3 area_sample_point(const DevScene &sc, const LT &L, V3 pref, float u1, float u2, RNG &rng, V3 &ns) {
     if (EXT && L.quadric >= 0) return quadric_sample(sc, unsigned(L.quadric), L.reverse_orientation != 0, pref, u1, u2, ns);
     unsigned k = 0;
     if (L.n_tris > 1) {
         float ls = rng.next_float();
-        for (k = 0; k < L.n_tris - 1; ++k)
+        for (k = 0; k < L.n_tris - 1; ++k) {
+            if constexpr (K) { if (ls < RT_KPTR(const float, sc.light_tris)[size_t(L.first_tri + k) * 16 + 10]) break; }
+            else
             if (ls < RT_GPTR(const float, sc.light_tris)[size_t(L.first_tri + k) * 16 + 10]) break;
+        }
     }
-    V3 p1, p2, p3; light_tri(sc, L.first_tri + k, p1, p2, p3);
+    V3 p1, p2, p3; light_tri<K>(sc, L.first_tri + k, p1, p2, p3);
     float su1 = sqrtf(u1);
     float b1 = 1.f - su1, b2 = u2 * su1;
     V3 ps = b1 * p1 + b2 * p2 + (1.f - b1 - b2) * p3;
