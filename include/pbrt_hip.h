@@ -425,6 +425,35 @@ int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, ui
  *  - Always the megakernel with the full shading set (every material, quadric and light) at natural register allocation: a query is
  *    somewhat slower than the frame's own kernel where that is a high-occupancy or fixed-frame one. */
 int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays, uint64_t first, uint32_t n, float *dev_out);
+/* Sample::imageX, imageY of camera samples first .. first + count - 1 of the frame `rd` describes into dev_xy[count][2] (8-byte aligned): floats 4
+ * and 5 of the records rt_samples_read returns after rt_render of that frame, bit for bit.  The numbering is that of rt_camera_rays_device and
+ * rt_radiance_device (the scanline index pixel * spp + s on one shard); only the sampler, film and extent fields of `rd` are read.  Asynchronous on
+ * the scene's stream, no allocation, no copy, no wait.  Refused with RT_EINVAL before any launch: a null scene or description, a null or misaligned
+ * pointer with count > 0, shard_count != 1, first + count beyond the frame's camera samples.  count == 0 is RT_OK and launches nothing. */
+int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, float *dev_xy);
+/* Film::AddSample (scene.cpp:76 -> film/image.cpp:103-142) for n radiances in device memory: the third stage of Scene::Render's loop, behind
+ * rt_camera_rays_device and rt_radiance_device.  dev_L[n][4] = L.r, L.g, L.b, alpha (16-byte aligned; the layout rt_radiance_device writes).
+ *  - For i = 0 .. n-1 the bound film receives what Scene::Render would hand it for camera sample first + i of the frame `rd` describes if its
+ *    radiance were dev_L[i]: first the radiance check of scene.cpp:60-74 -- a NaN component, a luminance below -1e-5 or an infinite one turns L
+ *    into 0; the sample is still added, its weight and alpha * weight count, and with rt_set_counting on it counts as a bad sample -- then
+ *    ImageFilm::AddSample at the sample's own imageX, imageY (rt_sample_positions_device), with the filter table, widths and crop window of `rd`.
+ *  - Order.  Per film pixel the contributions are added on top of what the film holds, in ascending sample index: sample-pixel rows, then
+ *    columns, then sample in pixel -- the order of a frame's own gather.  So the whole frame in one call gives the film of rt_render bit for
+ *    bit, and so does every partition of [0, N) into contiguous chunks added in ascending order (a caller never needs the whole frame's
+ *    radiances at once).  Chunks added in another order give a deterministic film that may differ from it in the last bit.
+ *  - Only the sampler, film, filter, extent and shard fields of `rd` are read; the radiances need not come from an integrator of the library.
+ *  - Asynchronous on the scene's stream.  The 1 KB filter table is uploaded as rt_render uploads it; otherwise no host copy and no wait, except
+ *    that the call's staging buffer (8 bytes per sample of the range: sized by the chunk, not by the frame) grows when n exceeds the largest n
+ *    added so far on the scene, which waits for the stream before the old block goes.
+ *  - It is not a frame: rt_samples_read, rt_last_render_stats, rt_last_render_ms and the traversal counters report the last rt_render as
+ *    before the call.  Only the film changed, and bad_samples where counting is on.
+ *  - A sample pixel further from the crop window than the filter reaches (floor(width + .5) pixels) adds to no film pixel; its radiance is
+ *    still checked and counted.
+ *  - Refused before any launch (rt_last_error names the function and the reason): a null scene or description, a null or misaligned pointer with
+ *    n > 0, shard_count != 1, first + n beyond the frame's camera samples, filter widths that are not positive, film coordinates beyond 32767
+ *    (RT_EINVAL); no film bound (RT_ESTATE) or a film of another size than the crop window of `rd` (RT_EINVAL), as rt_render.  n == 0 is RT_OK
+ *    and launches nothing. */
+int rt_film_add_device(RtScene *s, const RtRenderDesc *rd, const float *dev_L, uint64_t first, uint32_t n);
 /* The stream the scene's calls are queued on: its own (non-blocking) one, or what rt_scene_set_stream was given */
 int rt_scene_get_stream(RtScene *s, void **hip_stream_out);
 

@@ -34,7 +34,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse",
 
 
 HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_mega_fsd.hip", "rt_mega_fsp.hip", "rt_mega_rw.hip", "rt_mega_rd.hip", "rt_mega_rp.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
-             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
+             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
 def _include_closure(path, seen=None):
@@ -317,7 +317,8 @@ def hip_lib():
                      "rt_kdtree_build", "rt_kdtree_info", "rt_kdtree_copy", "rt_kdtree_destroy",
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
                      "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
-                     "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device"):
+                     "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device",
+                     "rt_sample_positions_device", "rt_film_add_device"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -336,6 +337,8 @@ def hip_lib():
         L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
         L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.rt_sample_positions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.rt_film_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.rt_scene_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.rt_film_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
         L.rt_film_clear.argtypes = [C.c_void_p]
@@ -1141,6 +1144,57 @@ class DeviceScene:
             if mine is not None:
                 cur.wait_stream(mine)
         return rays
+
+    def sample_positions_device(self, first: int, count: int):
+        """rt_sample_positions_device: Sample::imageX, imageY of camera samples first .. first + count - 1 of the parsed frame as a float32
+        [count, 2] torch tensor on the scene's device (bit for bit samples()[first:first + count, 4:6] of a render())."""
+        import torch
+        if first < 0 or count < 0:
+            raise ValueError("sample_positions_device: first and count must not be negative")
+        if not torch.cuda.is_available():
+            raise RtError("torch sees no HIP device.  torch carries a HIP runtime of its own and the first one a process loads serves both: "
+                          "import torch before this package loads libpbrt_hip.so (before the first DeviceScene), as bench.py does")
+        d = getattr(self, "_device", -1)
+        dev = torch.device("cuda", d if d is not None and d >= 0 else torch.cuda.current_device())
+        xy = torch.empty((int(count), 2), dtype=torch.float32, device=dev)
+        if count:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_sample_positions_device(self._s, self.parsed.render_desc, int(first), int(count), C.c_void_p(xy.data_ptr())))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return xy
+
+    def add_samples(self, L, first: int = 0):
+        """Film::AddSample for radiances in device memory (rt_film_add_device).  L: contiguous float32 [n, 4] torch tensor (L.r, L.g, L.b, alpha:
+        what radiance() returns) on the scene's device; row i is added to the bound film as camera sample first + i of the parsed frame, on top
+        of what the film holds.  clear_film(); add_samples(radiance(camera_rays_device(0, N))) is the film of render() bit for bit, and so is the
+        same in contiguous chunks added in ascending order."""
+        import torch
+        if not isinstance(L, torch.Tensor):
+            raise ValueError("L: a torch tensor is needed, got %s" % type(L).__name__)
+        if L.dtype != torch.float32:
+            raise ValueError("L: dtype float32 is needed, got %s" % L.dtype)
+        if L.dim() != 2 or L.shape[1] != 4:
+            raise ValueError("L: shape [n, 4] (L.r, L.g, L.b, alpha) is needed, got %s" % (tuple(L.shape),))
+        if not L.is_contiguous():
+            raise ValueError("L: a contiguous tensor is needed")
+        if not L.is_cuda:
+            raise ValueError("L: a tensor in device memory is needed, got one on %s" % L.device)
+        device = getattr(self, "_device", None)
+        if device is not None and device >= 0 and L.device.index != device:
+            raise ValueError("L: the tensor is on %s, the scene on device %d" % (L.device, device))
+        if first < 0:
+            raise ValueError("add_samples: first must not be negative")
+        n, dev = int(L.shape[0]), L.device
+        if n:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_film_add_device(self._s, self.parsed.render_desc, C.c_void_p(L.data_ptr()), int(first), n))
+            if mine is not None:
+                cur.wait_stream(mine)
 
     def close(self):
         if self._s:

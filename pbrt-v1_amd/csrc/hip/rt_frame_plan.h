@@ -1,6 +1,6 @@
 // rt_frame_plan.h -- what the host decides for a frame before anything touches the device: the work extent (plan_extent), the sample-request tables
 // that are the keyed RNG's address map (plan_requests), the scheduling policy with its knobs (plan_schedule) and the bounds of the medium's marches
-// (plan_march); and what turns a frame's schedule into that of a radiance query over caller-supplied rays (plan_query).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
+// (plan_march); what turns a frame's schedule into that of a radiance query over caller-supplied rays (plan_query); and what a range of caller-supplied radiances needs of the film (plan_film_add).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
 // allocation beyond std::vector, no I/O, no getenv; a refusal comes back as a code and a message.  make_frame (rt_kernels.hip) binds the results
 // to a DevFrame.  No HIP header: tests/frame_plan_host_test.cpp checks the rules with a host compiler.
 #pragma once
@@ -341,6 +341,48 @@ inline Refusal plan_query(const RtRenderDesc &rd, const QueryRange &q, Schedule 
     e.total_work = q.n;
     sc.pipeline = 0; sc.by_vertex = false; sc.fixed_frame = false; sc.fixed_scene = 0; sc.mega_tile = 0;
     sc.high_occupancy = 0;                                   // (the natural-allocation kernels carry the pooled-leaf scratch: trav_mode 3 stays where the frame has it)
+    return Refusal{};
+}
+
+// ---------------------------------------------------------------------------------------------- 6. a film add (rt_film_add_device)
+// Radiances first .. first + n - 1 of the caller stand in for those of camera samples first .. first + n - 1 of the frame `rd` describes, in the
+// scanline order of plan_query; the film receives them as Scene::Render would hand them to Film::AddSample.  Only the sampler, film, filter, extent
+// and shard fields of `rd` are read.  The plan: the refusals that need no device (film_w x film_h: the bound film, 0 x 0 when none is bound), the
+// sample pixels and sample rows the range touches, the film rows a gather for it has to visit -- the sample rows widened by the filter's reach
+// floor(width + .5) (a sample of sample pixel sy lies in [sy, sy + 1]: |y - sy| <= width + .5 for every film row y it can reach) and clipped to the
+// crop window -- and the size of the call's staging buffer: one image position (two floats) per sample of the range.
+struct FilmAdd {
+    int spp = 0;
+    int reach_x = 0, reach_y = 0;                    // floor(filter width + .5)
+    unsigned long long pixel0 = 0, pixel1 = 0;       // sample pixels [pixel0, pixel1] of the sample extent in scanline order, the partial ones at both ends included
+    int srow0 = 0, srow1 = -1;                       // sample rows [srow0, srow1], absolute (y_start + pixel / width)
+    int row0 = 0, row_end = 0;                       // film rows [row0, row_end) relative to the crop window's first row; empty when the range reaches none
+    size_t staging_floats = 0;
+};
+inline Refusal plan_film_add(const RtRenderDesc &rd, const QueryRange &q, int film_w, int film_h, FilmAdd &p) {
+    p = FilmAdd{};
+    Extent e;
+    if (Refusal r = plan_extent(rd, e)) return r;
+    if (e.shard_count != 1) return refuse(RT_EINVAL, "rt_film_add_device: shard_count != 1 (the radiances are addressed as the camera samples of the whole frame: one shard only)");
+    const unsigned long long samples = e.total_pixels * (unsigned long long)e.spp;           // (< 2^32: plan_extent)
+    if (q.first > samples || q.n > samples - q.first) return refuse(RT_EINVAL, "rt_film_add_device: first + n is beyond the frame's camera samples");
+    if (!(rd.filter_x_width > 0.f) || !(rd.filter_y_width > 0.f)) return refuse(RT_EINVAL, "rt_film_add_device: filter widths must be positive");
+    if (rd.x_pixel_start + (long long)rd.x_pixel_count > 32767 || rd.y_pixel_start + (long long)rd.y_pixel_count > 32767 || rd.x_pixel_start < -32768 || rd.y_pixel_start < -32768)
+        return refuse(RT_EINVAL, "rt_film_add_device: film coordinates beyond 32767 (the gather packs sample footprints as int16)");
+    if (rd.x_pixel_count < 1 || rd.y_pixel_count < 1) return refuse(RT_EINVAL, "rt_film_add_device: empty crop window");
+    if (film_w == 0 && film_h == 0) return refuse(RT_ESTATE, "rt_film_add_device: no film bound (call rt_film_bind first)");
+    if (rd.x_pixel_count != film_w || rd.y_pixel_count != film_h) return refuse(RT_EINVAL, "rt_film_add_device: film size does not match the bound film");
+    p.spp = e.spp;
+    // (a reach beyond the film's own coordinates reaches nothing more: clamped so that the sums below stay small)
+    p.reach_x = int(std::min(std::floor(rd.filter_x_width + 0.5f), 65536.f)); p.reach_y = int(std::min(std::floor(rd.filter_y_width + 0.5f), 65536.f));
+    if (q.n == 0) return Refusal{};
+    const unsigned long long width = (unsigned long long)(rd.x_end - rd.x_start);
+    p.pixel0 = q.first / unsigned(e.spp); p.pixel1 = (q.first + q.n - 1) / unsigned(e.spp);
+    p.srow0 = rd.y_start + int(p.pixel0 / width); p.srow1 = rd.y_start + int(p.pixel1 / width);
+    const long long lo = (long long)p.srow0 - p.reach_y - rd.y_pixel_start, hi = (long long)p.srow1 + p.reach_y - rd.y_pixel_start + 1;
+    p.row0 = int(std::max(lo, 0ll)); p.row_end = int(std::min(hi, (long long)rd.y_pixel_count));
+    if (p.row_end <= p.row0) p.row0 = p.row_end = 0;
+    p.staging_floats = size_t(q.n) * 2;
     return Refusal{};
 }
 

@@ -1,7 +1,8 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
 // the owners of its device memory, events and stream, the kernel tables and their resident grids (rt_flavour.h).  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
 // rt_kernels.hip renders (make_frame binds what rt_frame_plan.h plans, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
-// memory (rt_trace_*_device, rt_hit_geometry_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
+// memory (rt_trace_*_device, rt_hit_geometry_device), rt_film_add.hip adds caller-supplied radiances in device memory to the film (the kernels of rt_film_add_device /
+// rt_sample_positions_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
 #include "rt_flavour.h"
 #include "rt_render_kernel.h"
@@ -157,6 +158,9 @@ struct RtScene {
     // is the scratch frames use (frames, vol_buf, the material pool: per resident thread, grown only when a query recurses deeper than anything before
     // it); nothing is sized by the number of rays
     DevBuf<DevFrame> query_frame;
+    // rt_film_add_device (rt_kernels.hip): the image positions of the call's samples, two floats each -- the call's own staging, sized by the largest
+    // range added so far; the sample buffer above stays the last frame's
+    DevBuf<float> add_xy;
 };
 #define RT_PIPE_QN 4096          // ring of per-iteration queue counters
 #define RT_PIPE_TIMED 256        // iterations whose trace launch is bracketed by events
@@ -203,3 +207,9 @@ template <class F> static inline int guarded(const char *what, F &&f) {
 struct FilmGather { int which = 0, grx = 0, gry = 0, cols = 0, rows = 0, slot_ncs = 0; size_t slot_lds = 0, col_bytes = 0; };
 int film_gather_plan(RtScene *s, const rt::DevFrame &fr, FilmGather &g);
 int film_gather_launch(RtScene *s, const rt::DevFrame &fr, const FilmGather &g, const rt::DevFrame *dfr, int row0, int row_end);
+
+// ---- a film add (rt_film_add.hip): the image positions of camera samples [first, first + count) of the frame bound to `fr` (with dev_L: its bad
+// radiances counted), and ImageFilm::AddSample for such a range over the film rows plan::plan_film_add found, both on the scene's stream
+int sample_positions_launch(RtScene *s, const rt::DevFrame &fr, unsigned long long first, unsigned count, float *dev_xy, const float *dev_L);
+int film_add_form(const rt::plan::FilmAdd &p, bool &packed);       // which of the gather's two forms (PBRT_HIP_FILM_ADD forces one), before any launch
+int film_add_launch(RtScene *s, const RtRenderDesc &rd, const rt::plan::FilmAdd &p, bool packed, unsigned long long first, unsigned n, const float *dev_L, const float *dev_xy);

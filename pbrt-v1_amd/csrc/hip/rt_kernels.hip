@@ -647,6 +647,42 @@ int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
+// Sample::imageX / imageY of camera samples first .. first + count - 1 into the caller's DEVICE buffer (include/pbrt_hip.h): the frame of
+// rt_camera_rays_device, the sampler without the camera (rt_film_add.hip).
+int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, float *dev_xy) {
+    static const std::string fn = "rt_sample_positions_device";
+    if (!s) return fail(RT_EINVAL, fn + ": null scene");
+    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
+    if (count > 0 && !dev_xy) return fail(RT_EINVAL, fn + ": null output pointer");
+    if (count > 0 && (reinterpret_cast<uintptr_t>(dev_xy) & 7u) != 0) return fail(RT_EINVAL, fn + ": dev_xy is not 8-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    DevFrame fr; int rc = camera_frame(rd, fr); if (rc) return rc;
+    if (fr.shard_count != 1) return fail(RT_EINVAL, fn + ": shard_count != 1 (the positions are addressed as the camera samples of the whole frame: one shard only)");
+    const unsigned long long samples = fr.total_pixels * (unsigned long long)fr.spp;
+    if (first > samples || count > samples - first) return fail(RT_EINVAL, fn + ": first + count is beyond the frame's camera samples");
+    return sample_positions_launch(s, fr, first, count, dev_xy, nullptr);
+}
+// Film::AddSample for radiances in device memory (include/pbrt_hip.h): binds what plan::plan_film_add plans -- the range's image positions into the
+// call's own staging buffer (with the scene counting: the bad radiances counted on the way), then the gather over the film rows the range reaches.
+// Nothing of the last rt_render but the film is touched: no sample buffer, no events, no last_* state.
+int rt_film_add_device(RtScene *s, const RtRenderDesc *rd, const float *dev_L, uint64_t first, uint32_t n) {
+    static const std::string fn = "rt_film_add_device";
+    if (!s) return fail(RT_EINVAL, fn + ": null scene");
+    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
+    if (n > 0 && !dev_L) return fail(RT_EINVAL, fn + ": null radiance pointer");
+    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_L) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_L is not 16-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    plan::FilmAdd p;
+    if (plan::Refusal r = plan::plan_film_add(*rd, plan::QueryRange{first, n}, s->accum ? s->film_w : 0, s->accum ? s->film_h : 0, p)) return fail(r.code, r.msg);
+    if (n == 0) return RT_OK;
+    bool packed; int rc = film_add_form(p, packed); if (rc) return rc;
+    DevFrame fr; rc = camera_frame(rd, fr); if (rc) return rc;
+    if ((rc = ensure(s, s->add_xy, p.staging_floats))) return rc;
+    { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
+    HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));      // as rt_render uploads it
+    if ((rc = sample_positions_launch(s, fr, first, n, s->add_xy, s->facts.counting ? dev_L : nullptr))) return rc;
+    return film_add_launch(s, *rd, p, packed, first, n, dev_L, s->add_xy);
+}
 int rt_sync(RtScene *s) {
     if (!s) return fail(RT_EINVAL, "null scene");
     HIPCHK(hipSetDevice(s->device));
