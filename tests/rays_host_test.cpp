@@ -1,6 +1,7 @@
 // rays_host_test.cpp -- rt_ray_guard.h on the host: rt::ray_usable, the predicate that decides which caller-supplied rays reach traversal
 // (rt_trace_closest_device / rt_trace_any_device lay an unusable ray out as an empty one).  Cases: NaN, +inf and -inf in each of the eight
-// components of an otherwise ordinary ray; a zero direction (+0 and -0); a denormal direction; maxt = +inf; mint > maxt; mint = -inf; and a
+// components of an otherwise ordinary ray; a zero direction (+0 and -0); a denormal direction; maxt = +inf; mint > maxt; mint = -inf; the extreme
+// records of the degenerate-ray classes of tests/edge_rays_cases.py (signed zeros next to an axis direction, scaled and denormal d); and a
 // few thousand seeded random finite rays.  The verdict is also held against <cmath>'s classification, and the empty ray an unusable one
 // becomes is checked to be usable and empty.  Stand-alone (tests/test_rays_host.py builds it under AddressSanitizer and
 // UndefinedBehaviorSanitizer); no GPU, no HIP header.
@@ -82,6 +83,39 @@ int main() {
         r[6] = -inf; r[7] = inf; check("mint = -inf", r, true);
         r[6] = std::numeric_limits<float>::max(); r[7] = -std::numeric_limits<float>::max(); check("mint > maxt at the ends of the range", r, true);
         r[0] = std::numeric_limits<float>::max(); r[1] = -std::numeric_limits<float>::max(); r[2] = denorm; check("o at the ends of the range", r, true);
+    }
+    {   // the extreme records of the degenerate-ray classes (tests/edge_rays_cases.py): all of them reach traversal
+        for (int axis = 0; axis < 3; ++axis)                             // class a: an axis-aligned direction, the two zeros in every combination of +0.f and -0.f
+            for (int m = 0; m < 8; ++m) {
+                float r[8] = {7.1f, 13.35f, 18.2f, 0.f, 0.f, 0.f, 0.f, 1000.f};
+                r[3 + axis] = (m & 4) ? -1.f : 1.f;
+                r[3 + (axis + 1) % 3] = (m & 1) ? -0.f : 0.f; r[3 + (axis + 2) % 3] = (m & 2) ? -0.f : 0.f;
+                check("axis-aligned direction, signed zeros", r, true);
+            }
+        for (int k = 0; k < 4; ++k) {                                    // class h: d scaled by 2^k with mint, maxt scaled by 2^-k ...
+            const int e[4] = {-60, -20, 20, 60};
+            float r[8]; std::memcpy(r, base, sizeof r);
+            for (int i = 3; i < 6; ++i) r[i] = std::ldexp(r[i], e[k]);
+            r[7] = std::ldexp(r[7], -e[k]);
+            check("scaled direction", r, true);
+        }
+        {   // ... and into the denormal range, every component, where 1 / d overflows; maxt = +inf
+            float r[8]; std::memcpy(r, base, sizeof r);
+            for (int i = 3; i < 6; ++i) r[i] = std::ldexp(r[i], -140);
+            r[7] = inf;
+            ++g_checked;
+            for (int i = 3; i < 6; ++i)
+                if (std::fpclassify(r[i]) != FP_SUBNORMAL || std::isfinite(1.f / r[i])) { ++g_failed; std::fprintf(stderr, "CHECK(denormal d) %g is not one\n", r[i]); }
+            check("denormal direction, maxt = +inf", r, true);
+            r[4] = -0.f; r[5] = 0.f;
+            check("denormal axis-aligned direction, signed zeros", r, true);
+        }
+        {   // class g: mint == maxt, and mint one step above maxt
+            float r[8]; std::memcpy(r, base, sizeof r);
+            r[6] = r[7] = 229.42726f; check("mint == maxt", r, true);
+            r[6] = std::nextafter(r[7], inf); check("mint = nextafter(maxt)", r, true);
+            r[6] = -500.f; r[7] = 1000.f; check("negative mint", r, true);
+        }
     }
     {   // what an unusable ray becomes
         const float e[8] = {RT_EMPTY_RAY_O, RT_EMPTY_RAY_D, RT_EMPTY_RAY_MINT, RT_EMPTY_RAY_MAXT};
