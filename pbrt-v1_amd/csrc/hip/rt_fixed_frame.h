@@ -58,7 +58,7 @@ struct Rays : Any {
     static constexpr bool caller_rays = true;
 };
 
-// what the host knows of a frame and its scene when it picks the kernel (render_mega, rt_kernels.hip)
+// what the host knows of a frame and its scene when it picks the kernel (plan_schedule and plan_launch, rt_frame_plan.h)
 struct Facts {
     int integrator;          // RtRenderDesc::integrator
     int sampler;             // DevFrame::sampler

@@ -1,6 +1,6 @@
 // rt_frame_plan.h -- what the host decides for a frame before anything touches the device: the work extent (plan_extent), the sample-request tables
 // that are the keyed RNG's address map (plan_requests), the scheduling policy with its knobs (plan_schedule) and the bounds of the medium's marches
-// (plan_march); what turns a frame's schedule into that of a radiance query over caller-supplied rays (plan_query); and what a range of caller-supplied radiances needs of the film (plan_film_add).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
+// (plan_march); what turns a frame's schedule into that of a radiance query over caller-supplied rays (plan_query); what a range of caller-supplied radiances needs of the film (plan_film_add); and which kernel of which family the frame or query launches (plan_launch).  Plain functions over plain structs: a render description, the SceneFacts an RtScene keeps of itself, the knobs as values.  No
 // allocation beyond std::vector, no I/O, no getenv; a refusal comes back as a code and a message.  make_frame (rt_kernels.hip) binds the results
 // to a DevFrame.  No HIP header: tests/frame_plan_host_test.cpp checks the rules with a host compiler.
 #pragma once
@@ -200,7 +200,7 @@ struct Schedule {
     int trav_mode = 2, exit_thresh = 0, high_occupancy = 0, leaf_min = 0, xcd_bands = 0, phase_sync = 0, pipeline = 0, mega_tile = 0;   // the DevFrame fields
     int dbg_x = -1000000, dbg_y = -1000000;
     Extent extent;                       // the caller's, or reset to scanline order for a one-shard megakernel frame
-    bool fixed_frame = false;            // render_mega launches the twin compiled for a fixed frame (rt_fixed_frame.h)
+    bool fixed_frame = false;            // plan_launch takes the twin compiled for a fixed frame (rt_fixed_frame.h)
     int fixed_scene = 0;                 // ... and, non-zero, that kernel's twin compiled for the scene too: the axes it fixes (fixed::SCENE_*)
     bool by_vertex = false;              // render_pipeline shades once per path vertex (rt_pipe_vertex.h)
 };
@@ -384,6 +384,34 @@ inline Refusal plan_film_add(const RtRenderDesc &rd, const QueryRange &q, int fi
     if (p.row_end <= p.row0) p.row0 = p.row_end = 0;
     p.staging_floats = size_t(q.n) * 2;
     return Refusal{};
+}
+
+// ---------------------------------------------------------------------------------------------- 7. the launch
+// What a frame asks of the kernel tables (rt_flavour.h: each family's index() turns it into the entry to launch).  rt_trace_* and the device-ray calls
+// have no frame: no integrator, no schedule
+inline flavour::Request request(const RtRenderDesc *rd, const SceneFacts &sf, const Schedule *sc) {
+    return flavour::Request{rd ? rd->integrator : 0, sf.accel_kind == RT_ACCEL_GRID, sf.medium, sf.counting, sf.has_ext, sc && sc->high_occupancy != 0};
+}
+// The family a frame (or a radiance query) runs and the entry k of that family's table; scene_axes: the axes a FixedScene entry fixes, else 0.
+// Pipeline has no one entry: render_pipeline picks its shade, trace and march kernels from the same request.
+struct Launch {
+    enum Family { Mega, Fixed, FixedScene, Debug, Weighted, Bidir, Rays, Pipeline } family = Mega;
+    int integ = 0, k = 0, scene_axes = 0;
+};
+inline Launch plan_launch(const RtRenderDesc &rd, const SceneFacts &sf, const Schedule &sc, bool query) {
+    const flavour::Request rq = request(&rd, sf, &sc);
+    const int integ = rd.integrator;
+    if (query) return Launch{Launch::Rays, integ, flavour::Rays::index(rq), 0};
+    if (sc.pipeline) return Launch{Launch::Pipeline, integ, 0, 0};
+    if (integ == RT_INTEGRATOR_BIDIRECTIONAL) return Launch{Launch::Bidir, integ, flavour::Bidir::index(rq), 0};
+    if (integ == RT_INTEGRATOR_DIRECT && rd.strategy == RT_STRATEGY_WEIGHTED) return Launch{Launch::Weighted, integ, flavour::Weighted::index(rq), 0};
+    if (integ == RT_INTEGRATOR_DEBUG) return Launch{Launch::Debug, integ, flavour::Debug::index(rq), 0};
+    // the twin compiled for a fixed frame (rt_fixed_frame.h), where plan_schedule found that the frame qualifies, and that kernel's twin compiled for the
+    // scene's one light (and all-matte material table) as well, where the schedule names its axes and the integrator has such twins
+    if (sc.fixed_frame && flavour::FixedScene::has(integ) && flavour::FixedScene::has_axes(sc.fixed_scene))
+        return Launch{Launch::FixedScene, integ, flavour::FixedScene::index(rq, sc.fixed_scene), sc.fixed_scene};
+    if (sc.fixed_frame) return Launch{Launch::Fixed, integ, flavour::Fixed::index(rq), 0};
+    return Launch{Launch::Mega, integ, flavour::Mega::index(rq), 0};
 }
 
 }  // namespace plan

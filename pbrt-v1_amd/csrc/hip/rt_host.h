@@ -1,6 +1,7 @@
 // rt_host.h -- what the host-side translation units of libpbrt_hip.so share: the scene object behind the opaque RtScene handle, error / knob helpers,
-// the owners of its device memory, events and stream, the kernel tables and their resident grids (rt_flavour.h).  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
-// rt_kernels.hip renders (make_frame binds what rt_frame_plan.h plans, the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
+// the owners of its device memory, events and stream, the kernel tables with their resident grids (rt_flavour.h; persistent_kernel is the one place that
+// turns a planned launch, rt_frame_plan.h plan::Launch, into a kernel and a grid), the record of the last timed launch (LastLaunch) and the refusals the device-pointer entry points share.  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
+// rt_kernels.hip renders (make_frame binds what rt_frame_plan.h plans, launch_persistent launches what plan_launch chose, the queue pipeline, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
 // memory (rt_trace_*_device, rt_hit_geometry_device), rt_film_add.hip adds caller-supplied radiances in device memory to the film (the kernels of rt_film_add_device /
 // rt_sample_positions_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
@@ -74,6 +75,62 @@ struct ResidentGrids {
     flavour::Table<unsigned, flavour::Trace> trace;
     flavour::Table<unsigned, flavour::March> march;
 };
+// The kernel and the grid of a planned launch (rt_frame_plan.h plan_launch): the one place that indexes the tables above for the persistent families.
+// The queue pipeline is no one kernel: render_pipeline picks its entries
+struct PersistentKernel { RenderKernelFn fn = nullptr; unsigned grid = 0; };
+static inline PersistentKernel persistent_kernel(const ResidentGrids &g, const plan::Launch &l) {
+    const int i = l.integ, k = l.k;
+    switch (l.family) {
+    case plan::Launch::Mega: return {(*g_render_kernels[i])[k], g.mega[i][k]};
+    case plan::Launch::Fixed: return {g_render_kernels_fixed[k], g.fixed[k]};
+    case plan::Launch::FixedScene: return {(*g_render_kernels_fixed_scene[i])[k], g.fixed_scene[i][k]};
+    case plan::Launch::Debug: return {g_render_kernels_debug[k], g.debug[k]};
+    case plan::Launch::Weighted: return {g_render_kernels_weighted[k], g.weighted[k]};
+    case plan::Launch::Bidir: return {g_render_kernels_bidir[k], g.bidir[k]};
+    case plan::Launch::Rays: return {(*g_radiance_kernels[i])[k], g.rays[i][k]};
+    case plan::Launch::Pipeline: break;
+    }
+    return {};
+}
+// A device's resident grids: every entry gets as many blocks as its registers / LDS keep resident (x CUs; the trace kernel at most what
+// PBRT_HIP_TRACE_BLOCKS_PER_CU says: occupancy experiments), then the rules that let every family share one scratch.  n_threads: the threads of the largest
+// grid of all -- what the per-thread scratch and the spill area are sized by
+static inline int size_resident_grids(int device, ResidentGrids &g, int &n_cus, unsigned &n_threads) {
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    n_cus = prop.multiProcessorCount;
+    unsigned trace_per_cu = ~0u;
+    if (const char *e = knob("PBRT_HIP_TRACE_BLOCKS_PER_CU")) trace_per_cu = unsigned(std::max(1, std::atoi(e)));
+    auto resident = [&](const auto &kernels, auto &grids, unsigned at_most = ~0u) -> int {
+        static_assert(sizeof kernels / sizeof kernels[0] == sizeof grids / sizeof grids[0], "a grid per table entry");
+        for (size_t k = 0; k < kernels.size(); ++k) {
+            int per_cu = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernels[k], RT_BLOCK, 0));
+            grids[k] = unsigned(prop.multiProcessorCount) * std::max(1u, std::min(unsigned(std::max(per_cu, 0)), at_most));
+        }
+        return RT_OK;
+    };
+    int rc;
+    for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) {
+        if ((rc = resident(*g_render_kernels[i], g.mega[i])) || (rc = resident(*g_radiance_kernels[i], g.rays[i]))) return rc;
+        if (!flavour::FixedScene::has(i)) g.fixed_scene[i].fill(0u);
+        else if ((rc = resident(*g_render_kernels_fixed_scene[i], g.fixed_scene[i]))) return rc;
+    }
+    if ((rc = resident(g_render_kernels_fixed, g.fixed)) || (rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir)) ||
+        (rc = resident(g_render_kernels_debug, g.debug)) || (rc = resident(g_pipe_trace, g.trace, trace_per_cu)) || (rc = resident(g_pipe_march, g.march))) return rc;
+    auto largest = [](const auto &grids, unsigned of = 0) { for (unsigned n : grids) of = std::max(of, n); return of; };
+    // a fixed-frame kernel never takes a larger grid than its generic twin's (it shares the twin's scratch), a scene twin never a larger one than its fixed-frame twin's
+    for (int k = 0; k < flavour::Fixed::N; ++k) g.fixed[k] = std::min(g.fixed[k], g.mega[flavour::Fixed::integrator(k)][flavour::Fixed::generic(k)]);
+    for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i)
+        for (int k = 0; flavour::FixedScene::has(i) && k < flavour::FixedScene::N; ++k) g.fixed_scene[i][k] = std::min(g.fixed_scene[i][k], g.fixed[flavour::FixedScene::fixed_twin(k, i)]);
+    unsigned grid = largest(g.bidir, largest(g.weighted));                // the largest of the megakernel families
+    for (const auto &mega : g.mega) grid = largest(mega, grid);
+    // the debug and the radiance-query kernels (fewer registers than any of those; the code of Mega's EXT entries) never take a larger grid than the largest of the others
+    for (unsigned &n : g.debug) n = std::min(n, grid);
+    for (auto &rays : g.rays) for (unsigned &n : rays) n = std::min(n, grid);
+    n_threads = largest(g.march, largest(g.trace, grid)) * RT_BLOCK;
+    return RT_OK;
+}
 
 // ---- owners (rt_devbuf.h).  A device block is a DevBuf<T>; the same template with another release function owns page-locked memory, an event and the
 // stream a scene created itself.  rt_kernels.hip defines the release functions, next to rt::dev_alloc / rt::dev_free.
@@ -87,6 +144,17 @@ using OwnedStream = rt::DevBuf<std::remove_pointer_t<hipStream_t>, rt::stream_fr
 struct PipePlanes {
     DevBuf<float4> state, ray_o, hit, q_o; DevBuf<unsigned> q_slot;
     template <class F> void each(F &&f) { f(state, size_t(RT_PIPE_VEC)); f(ray_o, size_t(2)); f(hit, size_t(3)); f(q_o, size_t(4)); f(q_slot, size_t(3)); }   // hit: [kind][slot] in the by-vertex form
+};
+
+// The last timed launch (rt_render, rt_trace_closest / rt_trace_any): what rt_last_render_stats reports next to the events' times.  A launch builds one
+// and assigns it to the scene whole once it is queued, so no field outlives its launch; a default one is "no timed launch yet".  The events are read once
+// per launch and kept (stats): hipEventElapsedTime forms a time anew at every call and two reads of the same events differ in the last digits.
+struct LastLaunch {
+    bool timed = false;                                 // ev0 .. ev2 hold a launch
+    bool pipeline = false, marches = false; int iterations = 0, timed_iterations = 0; unsigned slots = 0;     // the queue pipeline: iterations, those with events, slots
+    bool weighted = false; unsigned long long weighted_points = 0;     // DirectLighting "weighted": the frame's shading points
+    bool fixed = false; int fixed_scene = 0;            // a fixed-frame kernel (rt_fixed_frame.h); a scene twin of one: the axes it fixes (fixed::SCENE_*)
+    bool stats_read = false; RtRenderStats stats{};
 };
 
 // Members are destroyed in reverse order of declaration: every buffer, then the events, then the stream (rt_scene_destroy has synchronised it).
@@ -110,8 +178,8 @@ struct RtScene {
     DevBuf<unsigned long long> work_counter, counters;
     DevBuf<uint2> spill;
     DevBuf<float> frames;
-    unsigned grid = 0, n_threads = 0;
-    ResidentGrids grids{};             // grid: the largest of the megakernel families, n_threads: of all
+    unsigned n_threads = 0;
+    ResidentGrids grids{};             // size_resident_grids; n_threads: the threads of the largest grid
     DevBuf<DimReq> light_dims;         // DirectLighting "all": the per-light sample requests (plan_requests, rt_frame_plan.h; make_frame uploads them); the bidirectional integrator: its BidirTable
     std::vector<DimReq> light_dims_host;
     const unsigned *light_draw_flags = nullptr; unsigned n_drawing_lights = 0;
@@ -120,7 +188,6 @@ struct RtScene {
     DevBuf<unsigned> wt_base; DevBuf<float> wt_rec; DevBuf<float2> wt_pick;
     DevBuf<unsigned long long> wt_sums;                        // per-block sums of the point-count scan
     Pinned<unsigned long long> wt_total;                       // page-locked: the frame's shading points (weighted_scan_top_kernel)
-    unsigned long long wt_points = 0; bool last_weighted = false;
     DevBuf<DevScene> dev_scene; DevBuf<DevFrame> dev_frame;     // descriptors in HBM (read with scalar loads)
     DevBuf<float4> samples;                                    // per-shard sample buffer
     int samples_spp = 1;
@@ -137,17 +204,11 @@ struct RtScene {
     bool has_textures = false;
     DevBuf<DevMaterial> mat_buf;
     int spill_depth = 0;
-    bool have_timing = false;
-    // rt_last_render_stats / rt_last_render_ms read the events of the last timed launch once and keep what they read: hipEventElapsedTime forms a time anew at
-    // every call and two reads of the same events differ in the last digits; a frame's stats stay the same bits until the next timed launch
-    bool stats_cached = false; RtRenderStats stats_cache{};
+    LastLaunch last;
     uint32_t n_tris = 0;
     // queue pipeline (rt_pipeline.h)
     PipePlanes pool; DevBuf<unsigned> q_count; DevBuf<unsigned long long> wave_work; DevBuf<PipePool> dev_pool;
     Pinned<unsigned> h_qcount;                          // page-locked mirror of q_count (termination test)
-    bool last_fixed = false;                            // the last frame ran a fixed-frame kernel (rt_fixed_frame.h)
-    int last_fixed_scene = 0;                           // ... a scene twin of one: the axes it fixes (fixed::SCENE_*)
-    bool last_pipeline = false, last_marches = false; int pipe_iters = 0, pipe_timed = 0; unsigned pipe_slots = 0;
     DevBuf<float4> trace_buf;                            // rt_trace_*: rays (2 x float4) and hits, reused across calls
     int n_cus = 0;
     DevBuf<unsigned> trace_qc;
@@ -201,6 +262,19 @@ template <class F> static inline int guarded(const char *what, F &&f) {
     try { return f(); }
     catch (const std::bad_alloc &) { return rt::fail(RT_ENOMEM, std::string(what) + ": out of host memory"); }
     catch (const std::exception &e) { return rt::fail(RT_ESTATE, std::string(what) + ": " + e.what()); }
+}
+
+// ---- the refusals the entry points that take device pointers share (rt_kernels.hip, rt_rays.hip), before anything is launched.  `what` names a pointer in
+// the "null" text ("ray pointer"), `name` in the alignment text ("dev_rays")
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline int refuse_null(const std::string &fn, const void *p, const char *what) { return p ? RT_OK : fail(RT_EINVAL, fn + ": null " + what); }
+static inline int refuse_unaligned16(const std::string &fn, const void *p, const char *name) {
+    return aligned16(p) ? RT_OK : fail(RT_EINVAL, fn + ": " + name + " is not 16-byte aligned");
+}
+// an error some earlier asynchronous work left behind must not be taken for this launch's
+static inline int pending_error() {
+    const hipError_t pre = hipGetLastError();
+    return pre == hipSuccess ? RT_OK : fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre));
 }
 
 // ---- the film gather (rt_film.hip): which of the three kernels a frame takes, and its launch over film rows [row0, row_end) on the scene's stream

@@ -1,4 +1,4 @@
-// rt_kernels.hip -- the render path of libpbrt_hip.so's C ABI (include/pbrt_hip.h): make_frame (the binder of what rt_frame_plan.h plans), the megakernel / queue-pipeline dispatch, rt_render, rt_trace_*.
+// rt_kernels.hip -- the render path of libpbrt_hip.so's C ABI (include/pbrt_hip.h): make_frame (the binder of what rt_frame_plan.h plans), launch_persistent (the one launch of the kernel plan_launch chose), the queue pipeline, rt_render, rt_trace_*.
 // (Scene create: rt_scene.hip.  Film kernels and rt_film_*: rt_film.hip.  Shared host declarations: rt_host.h.  Which kernel instantiation: rt_flavour.h.)
 //
 // Kernels
@@ -85,15 +85,26 @@ static int bind_scratch(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, size_t
     return ensure_material_pool(s, fr, w.mat_levels, n);
 }
 
-// What a frame asks of the kernel tables (rt_flavour.h: each family's index() turns it into the entry to launch); rt_trace_* have no frame
-static flavour::Request request_of(const RtScene *s, const RtRenderDesc *rd = nullptr, const DevFrame *fr = nullptr) {
-    return flavour::Request{rd ? rd->integrator : 0, s->facts.accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->facts.counting, s->facts.has_ext, fr && fr->high_occupancy};
+// The kernel and resident grid of a planned launch (rt_host.h persistent_kernel); a variant the scene has no grid for is refused
+static int resident_kernel(const RtScene *s, const plan::Launch &ln, PersistentKernel &pk) {
+    pk = persistent_kernel(s->grids, ln);
+    return pk.grid ? RT_OK : fail(RT_ESTATE, "render kernel variant has no resident grid");
+}
+// One launch of a persistent kernel on the scene's stream: the descriptor to `dev_fr` (the frame's, or a query's own), the work counters zeroed, `staged`
+// (where the caller times from there: ev0 of a megakernel frame) recorded, the kernel over its resident grid
+static int launch_persistent(RtScene *s, const PersistentKernel &pk, const DevFrame &fr, DevFrame *dev_fr, hipEvent_t staged = nullptr) {
+    HIPCHK(hipMemcpyAsync(dev_fr, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
+    if (staged) HIPCHK(hipEventRecord(staged, s->stream));
+    hipLaunchKernelGGL(pk.fn, dim3(pk.grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)dev_fr);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
 }
 
 // The queue pipeline: alternate a shade kernel (pipe_shade_kernel, or pipe_vertex_kernel for a path without a medium) and pipe_trace_kernel
 // until a shade pass enqueues no ray.  The host learns the queue sizes RT_PIPE_BATCH iterations late (page-locked copy + fence event per
 // batch), so the GPU never waits for it; the iterations launched after the last productive one find every slot in ST_EXIT and return at once.
-static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Schedule &sc, const plan::FrameKnobs &kn) {
+static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Schedule &sc, const plan::FrameKnobs &kn, LastLaunch &ll) {
     const int integ = rd->integrator;
     const bool by_vertex = sc.by_vertex;          // PathIntegrator without a medium: one shade pass per path vertex (plan_schedule)
     // ---- pool size: 32 M slots with a medium, 8 M without, unless the frame is smaller or the per-slot scratch would not fit (a fine ray march: 3 floats per step)
@@ -132,7 +143,7 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, con
         for (auto &e : s->pipe_ev) HIPCHK(hipEventCreate(&e.p));
         for (auto &e : s->pipe_fence) HIPCHK(hipEventCreateWithFlags(&e.p, hipEventDisableTiming));
     }
-    const flavour::Request rq = request_of(s, rd, &fr);
+    const flavour::Request rq = plan::request(rd, s->facts, &sc);
     const PipeShadeFn shade = by_vertex ? g_pipe_vertex[flavour::Vertex::index(rq)] : (*g_pipe_shade[integ])[flavour::Shade::index(rq)];
     const int tk = flavour::Trace::index(rq);
     const PipeTraceFn trace = g_pipe_trace[tk];
@@ -189,53 +200,26 @@ static int render_pipeline(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, con
         ++batch;
         if (iter > max_iters) return fail(RT_ESTATE, "rt_render: the queue pipeline did not terminate");
     }
-    s->last_marches = marches;
-    s->pipe_slots = n_slots; s->pipe_iters = checked + 1; s->pipe_timed = std::min(s->pipe_iters, RT_PIPE_TIMED);
+    ll.pipeline = true; ll.marches = marches;
+    ll.slots = n_slots; ll.iterations = checked + 1; ll.timed_iterations = std::min(ll.iterations, RT_PIPE_TIMED);
     HIPCHK(hipEventRecord(s->ev1, s->stream));
     return RT_OK;
 }
 
-// The bidirectional integrator: rt::bidir_kernel (rt_bidir.h), with the eight path vertices of every thread in s->frames
-static int render_bidir(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+// One launch of the persistent kernel plan_launch chose: the megakernel rt::render_kernel of Whitted, DirectLighting "all" / "one", Path (generic, or a twin
+// compiled for a fixed frame and scene) and the debug integrator, or the bidirectional integrator's rt::bidir_kernel (rt_bidir.h: the eight path vertices
+// of every thread in s->frames)
+static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Launch &ln) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-    const int k = flavour::Bidir::index(request_of(s, rd, &fr));
-    const unsigned grid = s->grids.bidir[k];
-    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
-    HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-    HIPCHK(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(g_render_kernels_bidir[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev1, s->stream));
-    return RT_OK;
-}
-
-// The megakernel of Whitted, DirectLighting "all" / "one", Path and the debug integrator (a table of its own, flavour::Debug): one launch of rt::render_kernel
-static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Schedule &sc) {
-    int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-    const bool debug = rd->integrator == RT_INTEGRATOR_DEBUG;
-    const bool fixed_frame = sc.fixed_frame;      // the twin compiled for a fixed frame (rt_fixed_frame.h), where plan_schedule found that the frame qualifies
-    // ... and that kernel's twin compiled for the scene's one light (and all-matte material table) as well, where the schedule names its axes
-    const int scene_axes = fixed_frame && !debug && flavour::FixedScene::has(rd->integrator) && flavour::FixedScene::has_axes(sc.fixed_scene) ? sc.fixed_scene : 0;
-    const int k = debug ? flavour::Debug::index(request_of(s, rd, &fr)) : scene_axes ? flavour::FixedScene::index(request_of(s, rd, &fr), scene_axes)
-                : fixed_frame ? flavour::Fixed::index(request_of(s, rd, &fr)) : flavour::Mega::index(request_of(s, rd, &fr));
-    const unsigned grid = debug ? s->grids.debug[k] : scene_axes ? s->grids.fixed_scene[rd->integrator][k] : fixed_frame ? s->grids.fixed[k] : s->grids.mega[rd->integrator][k];
-    const RenderKernelFn kernel = debug ? g_render_kernels_debug[k] : scene_axes ? (*g_render_kernels_fixed_scene[rd->integrator])[k]
-                                : fixed_frame ? g_render_kernels_fixed[k] : (*g_render_kernels[rd->integrator])[k];
-    s->last_fixed = fixed_frame; s->last_fixed_scene = scene_axes;
-    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    PersistentKernel pk; if ((rc = resident_kernel(s, ln, pk))) return rc;
 #ifdef RT_TAIL_PROBE
     static unsigned long long *probe = nullptr;
-    const size_t n_waves = size_t(grid) * (RT_BLOCK / 64);
+    const size_t n_waves = size_t(pk.grid) * (RT_BLOCK / 64);
     if (!probe) HIPCHK(hipMalloc((void **)&probe, size_t(s->n_threads / 64 + 64) * 4 * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(probe, 0, n_waves * 4 * sizeof(unsigned long long), s->stream));
     fr.probe = probe;
 #endif
-    HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-    HIPCHK(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_persistent(s, pk, fr, s->dev_frame, s->ev0))) return rc;
     HIPCHK(hipEventRecord(s->ev1, s->stream));
 #ifdef RT_TAIL_PROBE
     {   // the launch's timeline: when the waves started, when each found the work list empty, when each ended (10 ns ticks of s_memrealtime)
@@ -266,25 +250,16 @@ static int render_mega(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const p
 
 // DirectLighting "weighted" (rt_weighted.h): count -> scan -> survey -> recurrence -> the frame.  ev0 .. ev1 bracket all of it (kernel_ms of a weighted frame
 // is the five together)
-static int render_weighted(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
+static int render_weighted(RtScene *s, const RtRenderDesc *rd, DevFrame &fr, const plan::Launch &ln, LastLaunch &ll) {
     int rc = bind_scratch(s, rd, fr, s->n_threads); if (rc) return rc;
-    const int k = flavour::Weighted::index(request_of(s, rd, &fr));
-    const unsigned grid = s->grids.weighted[k];
-    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
+    PersistentKernel pk; if ((rc = resident_kernel(s, ln, pk))) return rc;
     const int nL = int(s->dev.n_lights), R = 1 + 2 * nL;
     if (!s->wt_total) HIPCHK(hipHostMalloc((void **)&s->wt_total.p, sizeof(unsigned long long), hipHostMallocDefault));
     if ((rc = s->wt_sums.grow(RT_WSCAN_BLOCKS))) return rc;
     for (Event &e : s->wt_ev) if (!e) HIPCHK(hipEventCreate(&e.p));
     rc = ensure(s, s->wt_base, size_t(fr.total_work) + 1); if (rc) return rc;
     fr.wt_base = s->wt_base;
-    auto pass = [&](int phase) -> int {
-        fr.weighted_phase = phase;
-        HIPCHK(hipMemcpyAsync(s->dev_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-        hipLaunchKernelGGL(g_render_kernels_weighted[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->dev_frame);
-        HIPCHK(hipGetLastError());
-        return RT_OK;
-    };
+    auto pass = [&](int phase) -> int { fr.weighted_phase = phase; return launch_persistent(s, pk, fr, s->dev_frame); };
     HIPCHK(hipEventRecord(s->ev0, s->stream));
     if ((rc = pass(1))) return rc;
     HIPCHK(hipEventRecord(s->wt_ev[0], s->stream));
@@ -297,9 +272,9 @@ static int render_weighted(RtScene *s, const RtRenderDesc *rd, DevFrame &fr) {
     const unsigned long long n_points = *s->wt_total;
     // The one place where rt_render can fail AFTER it has launched work (the number of shading points is only known once the count pass has run;
     // pbrt_hip.h says so): the film and the sample buffer are untouched (the count pass writes neither), the scene is left without a last frame.
-    auto late_fail = [&](int code, const char *msg) { s->last_weighted = false; s->last_pipeline = false; s->have_timing = false; s->wt_points = 0; return fail(code, msg); };
+    auto late_fail = [&](int code, const char *msg) { s->last = LastLaunch{}; return fail(code, msg); };
     if (n_points >= 0xffffffffull) return late_fail(RT_EINVAL, "rt_render: strategy \"weighted\": more than 2^32 - 2 shading points in the frame");
-    s->wt_points = n_points;
+    ll.weighted = true; ll.weighted_points = n_points;
     const bool mixed = s->facts.light_draws < 0;
     const int nD = int(s->n_drawing_lights);
     size_t rec_floats = size_t(n_points) * size_t(R);
@@ -463,13 +438,13 @@ int rt_camera_rays(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t 
 }
 // The same into the caller's DEVICE buffer, asynchronous on the scene's stream: no allocation, no copy, no wait (rt_rays.hip traces such rays).
 int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays) {
-    if (!s) return fail(RT_EINVAL, "rt_camera_rays_device: null scene");
-    if (!rd) return fail(RT_EINVAL, "rt_camera_rays_device: null render description");
-    if (!dev_rays) return fail(RT_EINVAL, "rt_camera_rays_device: null ray pointer");
-    if ((reinterpret_cast<uintptr_t>(dev_rays) & 15u) != 0) return fail(RT_EINVAL, "rt_camera_rays_device: dev_rays is not 16-byte aligned");
-    if (count > (1u << 30)) return fail(RT_EINVAL, "rt_camera_rays_device: count = " + std::to_string(count) + " is above 2^30");
+    static const std::string fn = "rt_camera_rays_device";
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, rd, "render description")) || (rc = refuse_null(fn, dev_rays, "ray pointer")) ||
+        (rc = refuse_unaligned16(fn, dev_rays, "dev_rays"))) return rc;
+    if (count > (1u << 30)) return fail(RT_EINVAL, fn + ": count = " + std::to_string(count) + " is above 2^30");
     HIPCHK(hipSetDevice(s->device));
-    DevFrame fr; int rc = camera_frame(rd, fr); if (rc) return rc;
+    DevFrame fr; if ((rc = camera_frame(rd, fr))) return rc;
     if (count == 0) return RT_OK;
     hipLaunchKernelGGL(camera_kernel, dim3((count + 255) / 256), dim3(256), 0, s->stream, s->dev, fr, (unsigned long long)first, count, dev_rays);
     HIPCHK(hipGetLastError());
@@ -495,14 +470,15 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
     TraceJob job{};
     job.q_o = s->trace_buf; job.q_d = s->trace_buf + n; job.q_slot = nullptr; job.q_count = s->trace_qc; job.hit = s->trace_buf + 2 * size_t(n);
     job.n_slots = 0; job.spill = s->spill; job.n_threads = s->n_threads; job.counters = s->counters;
-    flavour::Request rq = request_of(s);
+    flavour::Request rq = plan::request(nullptr, s->facts, nullptr);
     rq.count = true;                                            // whatever rt_set_counting says
     const int k = flavour::Trace::index(rq);
-    s->stats_cached = false;
+    s->last = LastLaunch{};                                     // (the events are recorded anew)
     HIPWARN(hipEventRecord(s->ev0, s->stream));
     hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
-    HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream)); s->have_timing = true; s->last_pipeline = false; s->last_fixed = false;
+    HIPWARN(hipEventRecord(s->ev1, s->stream)); HIPWARN(hipEventRecord(s->ev2, s->stream));
     HIPCHK(hipGetLastError());
+    s->last.timed = true;                                       // one kernel between ev0 and ev1, nothing of a frame: every other field stays empty
     HIPCHK(hipMemcpyAsync(host.data(), s->trace_buf + 2 * size_t(n), size_t(n) * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     for (uint32_t i = 0; i < n; ++i) {
@@ -514,8 +490,9 @@ static int trace_common(RtScene *s, const RtRay *rays, uint32_t n, int any, RtHi
 }
 int rt_trace_closest(RtScene *s, const RtRay *rays, uint32_t n, RtHit *hits_out) { return trace_common(s, rays, n, 0, hits_out, nullptr); }
 int rt_trace_any(RtScene *s, const RtRay *rays, uint32_t n, uint8_t *occluded_out) { return trace_common(s, rays, n, 1, nullptr, occluded_out); }
-// Validate, bound the medium's marches, size the sample buffer, hand the frame to one of render_pipeline / render_bidir / render_weighted / render_mega,
-// then the film gather.  Which instantiation each of the four launches is rt_flavour.h's index() of request_of(s, rd, &fr).
+// Validate, bound the medium's marches, size the sample buffer, hand the frame to the launch function of the family plan_launch chose (render_pipeline,
+// render_weighted, or render_mega for every single-launch family), then the film gather.  From the moment the frame is accepted the scene has no last
+// launch (LastLaunch) until this one's events are all recorded: an error on the way leaves "no timed launch yet", never a mix of two frames.
 int rt_render(RtScene *s, const RtRenderDesc *rd) {
     if (!s || !rd) return fail(RT_EINVAL, "null argument");
     HIPCHK(hipSetDevice(s->device));
@@ -578,18 +555,21 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
     fr.samples = s->samples; s->samples_last = fr.total_work; s->samples_spp = fr.spp;
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));
     if (debug) { rc = upload_tex_uv(s); if (rc) return rc; }    // dg.u / dg.v of a mesh with "uv": on the device from the first debug frame on
-    { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
+    if ((rc = pending_error())) return rc;
     s->rendered = true;
-    s->stats_cached = false;                                   // (the launch functions record the events anew)
-    s->last_fixed = false;                                     // (render_mega sets it)
-    // ---- the frame, by one of the four launch functions
-    rc = fr.pipeline ? render_pipeline(s, rd, fr, sc, kn) : bidir ? render_bidir(s, rd, fr) : weighted ? render_weighted(s, rd, fr) : render_mega(s, rd, fr, sc);
+    s->last = LastLaunch{};                                    // (the launch functions record the events anew)
+    // ---- the frame, by the launch function of its family
+    const plan::Launch ln = plan::plan_launch(*rd, s->facts, sc, false);
+    LastLaunch ll;
+    ll.fixed = ln.family == plan::Launch::Fixed || ln.family == plan::Launch::FixedScene; ll.fixed_scene = ln.scene_axes;
+    if (ln.family == plan::Launch::Pipeline) rc = render_pipeline(s, rd, fr, sc, kn, ll);
+    else if (ln.family == plan::Launch::Weighted) rc = render_weighted(s, rd, fr, ln, ll);
+    else rc = render_mega(s, rd, fr, ln);
     if (rc) return rc;
-    s->last_pipeline = fr.pipeline != 0; s->last_weighted = weighted;
     // ---- film gather and events
     if (!skip_film) { rc = film_gather_launch(s, fr, fg, (const DevFrame *)s->dev_frame, 0, fr.y_pixel_count); if (rc) return rc; }
     HIPCHK(hipEventRecord(s->ev2, s->stream));
-    s->have_timing = true;
+    ll.timed = true; s->last = ll;
 #ifdef RT_PROFILE
     {   // -DRT_PROFILE builds: per-wave cycle split of the render kernel
         unsigned long long v[24];
@@ -614,20 +594,18 @@ int rt_render(RtScene *s, const RtRenderDesc *rd) {
 }
 // Scene::Li for caller-supplied rays in device memory (include/pbrt_hip.h): the frame's plan with the n rays as its work (plan_query), bound like a
 // frame, and one launch of the flavour::Rays entry -- the megakernel's radiance estimate with the caller's array as ray source and result sink.
-// Nothing of the last rt_render is touched: no film, no sample buffer, no events, no last_* state; the descriptor is the query's own (query_frame).
+// Nothing of the last rt_render is touched: no film, no sample buffer, no events, no LastLaunch; the descriptor is the query's own (query_frame).
 int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays, uint64_t first, uint32_t n, float *dev_out) {
     static const std::string fn = "rt_radiance_device";
-    if (!s) return fail(RT_EINVAL, fn + ": null scene");
-    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
-    if (n > 0 && !dev_rays) return fail(RT_EINVAL, fn + ": null ray pointer");
-    if (n > 0 && !dev_out) return fail(RT_EINVAL, fn + ": null output pointer");
-    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_rays) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_rays is not 16-byte aligned");
-    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_out) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_out is not 16-byte aligned");
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, rd, "render description"))) return rc;
+    if (n > 0 && ((rc = refuse_null(fn, dev_rays, "ray pointer")) || (rc = refuse_null(fn, dev_out, "output pointer")) ||
+                  (rc = refuse_unaligned16(fn, dev_rays, "dev_rays")) || (rc = refuse_unaligned16(fn, dev_out, "dev_out")))) return rc;
     HIPCHK(hipSetDevice(s->device));
     const plan::FrameKnobs kn = frame_knobs();
     const plan::QueryRange q{first, n};
     DevFrame fr; plan::Schedule sc;
-    int rc = make_frame(s, rd, kn, fr, sc, false, &q); if (rc) return rc;
+    if ((rc = make_frame(s, rd, kn, fr, sc, false, &q))) return rc;
     {
         plan::March m;
         if (plan::Refusal r = plan::plan_march(*rd, s->facts, m)) return fail(r.code, r.msg);
@@ -637,26 +615,19 @@ int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays
     fr.q_rays = reinterpret_cast<const float4 *>(dev_rays); fr.q_out = reinterpret_cast<float4 *>(dev_out); fr.q_first = unsigned(first);
     fr.samples = nullptr; fr.accum = nullptr; fr.filter_table = nullptr;          // (a query has no film)
     if ((rc = bind_scratch(s, rd, fr, s->n_threads))) return rc;
-    const int k = flavour::Rays::index(request_of(s, rd, &fr));
-    const unsigned grid = s->grids.rays[rd->integrator][k];
-    if (grid == 0) return fail(RT_ESTATE, "render kernel variant has no resident grid");
-    { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
-    HIPCHK(hipMemcpyAsync(s->query_frame, &fr, sizeof(DevFrame), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemsetAsync(s->work_counter, 0, 64 * sizeof(unsigned long long), s->stream));
-    hipLaunchKernelGGL((*g_radiance_kernels[rd->integrator])[k], dim3(grid), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, (const DevFrame *)s->query_frame);
-    HIPCHK(hipGetLastError());
-    return RT_OK;
+    PersistentKernel pk;
+    if ((rc = resident_kernel(s, plan::plan_launch(*rd, s->facts, sc, true), pk)) || (rc = pending_error())) return rc;
+    return launch_persistent(s, pk, fr, s->query_frame);
 }
 // Sample::imageX / imageY of camera samples first .. first + count - 1 into the caller's DEVICE buffer (include/pbrt_hip.h): the frame of
 // rt_camera_rays_device, the sampler without the camera (rt_film_add.hip).
 int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, float *dev_xy) {
     static const std::string fn = "rt_sample_positions_device";
-    if (!s) return fail(RT_EINVAL, fn + ": null scene");
-    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
-    if (count > 0 && !dev_xy) return fail(RT_EINVAL, fn + ": null output pointer");
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, rd, "render description")) || (count > 0 && (rc = refuse_null(fn, dev_xy, "output pointer")))) return rc;
     if (count > 0 && (reinterpret_cast<uintptr_t>(dev_xy) & 7u) != 0) return fail(RT_EINVAL, fn + ": dev_xy is not 8-byte aligned");
     HIPCHK(hipSetDevice(s->device));
-    DevFrame fr; int rc = camera_frame(rd, fr); if (rc) return rc;
+    DevFrame fr; if ((rc = camera_frame(rd, fr))) return rc;
     if (fr.shard_count != 1) return fail(RT_EINVAL, fn + ": shard_count != 1 (the positions are addressed as the camera samples of the whole frame: one shard only)");
     const unsigned long long samples = fr.total_pixels * (unsigned long long)fr.spp;
     if (first > samples || count > samples - first) return fail(RT_EINVAL, fn + ": first + count is beyond the frame's camera samples");
@@ -664,21 +635,19 @@ int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t firs
 }
 // Film::AddSample for radiances in device memory (include/pbrt_hip.h): binds what plan::plan_film_add plans -- the range's image positions into the
 // call's own staging buffer (with the scene counting: the bad radiances counted on the way), then the gather over the film rows the range reaches.
-// Nothing of the last rt_render but the film is touched: no sample buffer, no events, no last_* state.
+// Nothing of the last rt_render but the film is touched: no sample buffer, no events, no LastLaunch.
 int rt_film_add_device(RtScene *s, const RtRenderDesc *rd, const float *dev_L, uint64_t first, uint32_t n) {
     static const std::string fn = "rt_film_add_device";
-    if (!s) return fail(RT_EINVAL, fn + ": null scene");
-    if (!rd) return fail(RT_EINVAL, fn + ": null render description");
-    if (n > 0 && !dev_L) return fail(RT_EINVAL, fn + ": null radiance pointer");
-    if (n > 0 && (reinterpret_cast<uintptr_t>(dev_L) & 15u) != 0) return fail(RT_EINVAL, fn + ": dev_L is not 16-byte aligned");
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, rd, "render description"))) return rc;
+    if (n > 0 && ((rc = refuse_null(fn, dev_L, "radiance pointer")) || (rc = refuse_unaligned16(fn, dev_L, "dev_L")))) return rc;
     HIPCHK(hipSetDevice(s->device));
     plan::FilmAdd p;
     if (plan::Refusal r = plan::plan_film_add(*rd, plan::QueryRange{first, n}, s->accum ? s->film_w : 0, s->accum ? s->film_h : 0, p)) return fail(r.code, r.msg);
     if (n == 0) return RT_OK;
-    bool packed; int rc = film_add_form(p, packed); if (rc) return rc;
-    DevFrame fr; rc = camera_frame(rd, fr); if (rc) return rc;
-    if ((rc = ensure(s, s->add_xy, p.staging_floats))) return rc;
-    { hipError_t pre = hipGetLastError(); if (pre != hipSuccess) return fail(RT_EDEVICE, std::string("pending HIP error before launch: ") + hipGetErrorString(pre)); }
+    bool packed; if ((rc = film_add_form(p, packed))) return rc;
+    DevFrame fr; if ((rc = camera_frame(rd, fr))) return rc;
+    if ((rc = ensure(s, s->add_xy, p.staging_floats)) || (rc = pending_error())) return rc;
     HIPCHK(hipMemcpyAsync(s->filter_dev, rd->filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, s->stream));      // as rt_render uploads it
     if ((rc = sample_positions_launch(s, fr, first, n, s->add_xy, s->facts.counting ? dev_L : nullptr))) return rc;
     return film_add_launch(s, *rd, p, packed, first, n, dev_L, s->add_xy);
@@ -719,24 +688,25 @@ static int read_render_stats(RtScene *s, RtRenderStats *out) {
     HIPCHK(hipEventElapsedTime(&out->render_ms, s->ev0, s->ev1));
     HIPCHK(hipEventElapsedTime(&out->total_ms, s->ev0, s->ev2));
     out->gather_ms = out->total_ms - out->render_ms;
-    out->pipeline = s->last_pipeline ? 1 : 0;
-    if (s->last_pipeline) {
-        out->iterations = s->pipe_iters; out->timed_iterations = s->pipe_timed;
+    const LastLaunch &l = s->last;
+    out->pipeline = l.pipeline ? 1 : 0;
+    if (l.pipeline) {
+        out->iterations = l.iterations; out->timed_iterations = l.timed_iterations;
         float sum = 0.f;
         float sum2 = 0.f, sum3 = 0.f;
-        for (int i = 0; i < s->pipe_timed; ++i) {
+        for (int i = 0; i < l.timed_iterations; ++i) {
             float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, s->pipe_ev[6 * i], s->pipe_ev[6 * i + 1])); sum += ms;
             HIPCHK(hipEventElapsedTime(&ms, s->pipe_ev[6 * i + 2], s->pipe_ev[6 * i + 3])); sum2 += ms;
-            if (s->last_marches) { HIPCHK(hipEventElapsedTime(&ms, s->pipe_ev[6 * i + 4], s->pipe_ev[6 * i + 5])); sum3 += ms; }
+            if (l.marches) { HIPCHK(hipEventElapsedTime(&ms, s->pipe_ev[6 * i + 4], s->pipe_ev[6 * i + 5])); sum3 += ms; }
         }
         out->trace_ms = sum; out->shade_ms = sum2; out->march_ms = sum3;
-        out->slots = s->pipe_slots;
+        out->slots = l.slots;
     } else out->trace_ms = out->render_ms;
-    out->bands = s->last_pipeline ? 0 : 1;
-    out->fixed_frame = s->last_fixed ? 1 : 0;
-    out->fixed_scene = s->last_fixed ? s->last_fixed_scene : 0;
-    if (s->last_weighted) {
-        out->weighted_points = s->wt_points;
+    out->bands = l.pipeline ? 0 : 1;
+    out->fixed_frame = l.fixed ? 1 : 0;
+    out->fixed_scene = l.fixed_scene;
+    if (l.weighted) {
+        out->weighted_points = l.weighted_points;
         hipEvent_t seq[6] = {s->ev0, s->wt_ev[0], s->wt_ev[1], s->wt_ev[2], s->wt_ev[3], s->ev1};
         for (int i = 0; i < 5; ++i) HIPCHK(hipEventElapsedTime(&out->weighted_ms[i], seq[i], seq[i + 1]));
     }
@@ -744,19 +714,19 @@ static int read_render_stats(RtScene *s, RtRenderStats *out) {
 }
 // Timing of the last rt_render by kernel: {whole frame, render part (megakernel or shade+trace loop), trace kernel launches summed,
 // film gather} in ms, the number of pipeline iterations (0: megakernel) and how many of them were timed.  The events are read once per timed launch:
-// every later call returns the same bits (RtScene::stats_cache), whatever was queued on the stream in between (rt_radiance_device records no event).
+// every later call returns the same bits (LastLaunch::stats), whatever was queued on the stream in between (rt_radiance_device records no event).
 int rt_last_render_stats(RtScene *s, RtRenderStats *out) {
     if (!s || !out) return fail(RT_EINVAL, "null argument");
-    if (!s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
-    if (!s->stats_cached) {
-        if (int rc = read_render_stats(s, &s->stats_cache)) return rc;
-        s->stats_cached = true;
+    if (!s->last.timed) return fail(RT_ESTATE, "no timed launch yet");
+    if (!s->last.stats_read) {
+        if (int rc = read_render_stats(s, &s->last.stats)) return rc;
+        s->last.stats_read = true;
     }
-    *out = s->stats_cache;
+    *out = s->last.stats;
     return RT_OK;
 }
 int rt_last_render_ms(RtScene *s, float *total_ms, float *kernel_ms) {
-    if (!s || !s->have_timing) return fail(RT_ESTATE, "no timed launch yet");
+    if (!s || !s->last.timed) return fail(RT_ESTATE, "no timed launch yet");
     RtRenderStats st;
     if (int rc = rt_last_render_stats(s, &st)) return rc;
     if (total_ms) *total_ms = st.total_ms;        // render kernel(s) + film gather

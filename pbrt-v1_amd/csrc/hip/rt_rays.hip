@@ -77,17 +77,18 @@ __global__ __launch_bounds__(RT_RAYS_BLOCK) void hit_geometry_kernel(const DevSc
 
 // ------------------------------------------------------------------------------------------ host side
 #define RT_RAYS_MAX_N (1u << 30)
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline unsigned blocks_for(uint32_t n) { return (n + RT_RAYS_BLOCK - 1) / RT_RAYS_BLOCK; }
 
-// the refusals every call shares, before anything is launched
-static int check_rays(const char *fn, const RtScene *s, const void *dev_rays, uint32_t n) {
-    const std::string f(fn);
-    if (!s) return fail(RT_EINVAL, f + ": null scene");
-    if (!dev_rays) return fail(RT_EINVAL, f + ": null ray pointer");
-    if (!aligned16(dev_rays)) return fail(RT_EINVAL, f + ": dev_rays is not 16-byte aligned");
-    if (n > RT_RAYS_MAX_N) return fail(RT_EINVAL, f + ": n = " + std::to_string(n) + " is above 2^30");
-    return RT_OK;
+// the refusals every call shares, before anything is launched (rt_host.h)
+static int check_rays(const std::string &fn, const RtScene *s, const void *dev_rays, uint32_t n) {
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, dev_rays, "ray pointer")) || (rc = refuse_unaligned16(fn, dev_rays, "dev_rays"))) return rc;
+    return n > RT_RAYS_MAX_N ? fail(RT_EINVAL, fn + ": n = " + std::to_string(n) + " is above 2^30") : RT_OK;
+}
+// ... and a call's hit array
+static int check_hits(const std::string &fn, const void *dev_hits) {
+    if (int rc = refuse_null(fn, dev_hits, "hit pointer")) return rc;
+    return refuse_unaligned16(fn, dev_hits, "dev_hits");
 }
 
 // Lay the rays out, write the queue counters, run the trace kernel over them.  `hit_plane`: the caller's RtHit array or s->any_hits.
@@ -100,8 +101,7 @@ static int trace_device(RtScene *s, const RtRay *dev_rays, uint32_t n, int any, 
     job.q_o = q_o; job.q_d = q_d; job.q_slot = nullptr; job.q_count = s->trace_qc; job.hit = hit_plane;
     job.n_slots = 0; job.spill = s->spill; job.n_threads = s->n_threads; job.counters = s->counters;
     // rt_set_counting is honoured: the counting twin or the timed kernel (the hits are the same, rt_flavour.h)
-    const flavour::Request rq{0, s->facts.accel_kind == RT_ACCEL_GRID, s->volume.present != 0, s->facts.counting, s->facts.has_ext, false};
-    const int k = flavour::Trace::index(rq);
+    const int k = flavour::Trace::index(plan::request(nullptr, s->facts, nullptr));
     hipLaunchKernelGGL(g_pipe_trace[k], dim3(s->grids.trace[k]), dim3(RT_BLOCK), 0, s->stream, (const DevScene *)s->dev_scene, job);
     HIPCHK(hipGetLastError());
     return RT_OK;
@@ -110,19 +110,18 @@ static int trace_device(RtScene *s, const RtRay *dev_rays, uint32_t n, int any, 
 extern "C" {
 
 int rt_trace_closest_device(RtScene *s, const RtRay *dev_rays, uint32_t n, RtHit *dev_hits) {
-    static const char *fn = "rt_trace_closest_device";
+    static const std::string fn = "rt_trace_closest_device";
     if (int rc = check_rays(fn, s, dev_rays, n)) return rc;
-    if (!dev_hits) return fail(RT_EINVAL, std::string(fn) + ": null hit pointer");
-    if (!aligned16(dev_hits)) return fail(RT_EINVAL, std::string(fn) + ": dev_hits is not 16-byte aligned");
+    if (int rc = check_hits(fn, dev_hits)) return rc;
     if (n == 0) return RT_OK;
     HIPCHK(hipSetDevice(s->device));
     return trace_device(s, dev_rays, n, 0, reinterpret_cast<float4 *>(dev_hits));
 }
 
 int rt_trace_any_device(RtScene *s, const RtRay *dev_rays, uint32_t n, uint8_t *dev_occluded) {
-    static const char *fn = "rt_trace_any_device";
+    static const std::string fn = "rt_trace_any_device";
     if (int rc = check_rays(fn, s, dev_rays, n)) return rc;
-    if (!dev_occluded) return fail(RT_EINVAL, std::string(fn) + ": null output pointer");
+    if (int rc = refuse_null(fn, dev_occluded, "output pointer")) return rc;
     if (n == 0) return RT_OK;
     HIPCHK(hipSetDevice(s->device));
     if (int rc = ensure(s, s->any_hits, size_t(n))) return rc;
@@ -133,13 +132,12 @@ int rt_trace_any_device(RtScene *s, const RtRay *dev_rays, uint32_t n, uint8_t *
 }
 
 int rt_hit_geometry_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uint32_t n, const RtHitGeometry *out) {
-    static const char *fn = "rt_hit_geometry_device";
+    static const std::string fn = "rt_hit_geometry_device";
     if (int rc = check_rays(fn, s, dev_rays, n)) return rc;
-    if (!dev_hits) return fail(RT_EINVAL, std::string(fn) + ": null hit pointer");
-    if (!aligned16(dev_hits)) return fail(RT_EINVAL, std::string(fn) + ": dev_hits is not 16-byte aligned");
-    if (!out) return fail(RT_EINVAL, std::string(fn) + ": null RtHitGeometry");
+    if (int rc = check_hits(fn, dev_hits)) return rc;
+    if (int rc = refuse_null(fn, out, "RtHitGeometry")) return rc;
     if (!out->p && !out->ng && !out->ns && !out->uv && !out->material && !out->light)
-        return fail(RT_EINVAL, std::string(fn) + ": every field of the RtHitGeometry is null (nothing is wanted)");
+        return fail(RT_EINVAL, fn + ": every field of the RtHitGeometry is null (nothing is wanted)");
     if (n == 0) return RT_OK;
     HIPCHK(hipSetDevice(s->device));
     // dg.u / dg.v of a mesh with "uv" read the mesh's uvs: on the device from the first call that wants them (once per scene; rt_scene.hip)

@@ -544,55 +544,8 @@ static int scene_create(const RtSceneDesc *d, int device, const RtPrebuiltAccel 
         for (int a = 0; a < 3; ++a) { f.vol_p0[a] = d->volume.p0[a]; f.vol_p1[a] = d->volume.p1[a]; f.cam_pos[a] = d->camera.camera_to_world[4 * a + 3]; }   // CameraToWorld(0,0,0)
     }
 
-    // persistent launch geometry: as many resident blocks as the kernel's registers/LDS admit
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, s->device));
-    s->n_cus = prop.multiProcessorCount;
-    unsigned trace_per_cu = ~0u;
-    if (const char *e = knob("PBRT_HIP_TRACE_BLOCKS_PER_CU")) trace_per_cu = unsigned(std::max(1, std::atoi(e)));   // occupancy experiments
-    unsigned mx = 0;                                            // the largest grid of a family
-    auto resident = [&](const auto &kernels, auto &grids, unsigned at_most = ~0u) -> int {      // a family's kernels -> resident blocks x CUs
-        static_assert(sizeof kernels / sizeof kernels[0] == sizeof grids / sizeof grids[0], "a grid per table entry");
-        for (size_t k = 0; k < kernels.size(); ++k) {
-            int per_cu = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernels[k], RT_BLOCK, 0));
-            grids[k] = unsigned(prop.multiProcessorCount) * std::max(1u, std::min(unsigned(std::max(per_cu, 0)), at_most));
-            mx = std::max(mx, grids[k]);
-        }
-        return RT_OK;
-    };
-    ResidentGrids &g = s->grids;
-    for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) if ((rc = resident(*g_render_kernels[i], g.mega[i]))) return rc;
-    {   // a fixed kernel shares its generic twin's scratch (n_threads, the spill area): never a larger grid than the twin's
-        const unsigned others = mx;
-        if ((rc = resident(g_render_kernels_fixed, g.fixed))) return rc;
-        for (int k = 0; k < flavour::Fixed::N; ++k) g.fixed[k] = std::min(g.fixed[k], g.mega[flavour::Fixed::integrator(k)][flavour::Fixed::generic(k)]);
-        for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) {        // ... and a scene twin never a larger one than its fixed-frame twin's
-            if (!flavour::FixedScene::has(i)) { g.fixed_scene[i].fill(0u); continue; }
-            if ((rc = resident(*g_render_kernels_fixed_scene[i], g.fixed_scene[i]))) return rc;
-            for (int k = 0; k < flavour::FixedScene::N; ++k) g.fixed_scene[i][k] = std::min(g.fixed_scene[i][k], g.fixed[flavour::FixedScene::fixed_twin(k, i)]);
-        }
-        mx = others;
-    }
-    if ((rc = resident(g_render_kernels_weighted, g.weighted)) || (rc = resident(g_render_kernels_bidir, g.bidir))) return rc;
-    s->grid = mx;                                               // ... of the megakernels
-    {   // the debug integrator's kernels need fewer registers than any of those: their grids stop at the largest of the others, so that the scratch
-        // every frame shares (n_threads) is sized as it was
-        const unsigned others = mx;
-        if ((rc = resident(g_render_kernels_debug, g.debug))) return rc;
-        for (unsigned &n : g.debug) n = std::min(n, others);
-        mx = others;
-    }
-    {   // the radiance-query kernels carry the code of Mega's EXT entries: they share the scratch every frame shares and never take a larger grid
-        const unsigned others = mx;
-        for (int i = 0; i <= RT_INTEGRATOR_PATH; ++i) {
-            if ((rc = resident(*g_radiance_kernels[i], g.rays[i]))) return rc;
-            for (unsigned &n : g.rays[i]) n = std::min(n, others);
-        }
-        mx = others;
-    }
-    if ((rc = resident(g_pipe_trace, g.trace, trace_per_cu)) || (rc = resident(g_pipe_march, g.march))) return rc;
-    s->n_threads = mx * RT_BLOCK;                               // ... of all: the spill area is shared
+    // persistent launch geometry: as many resident blocks as the kernels' registers / LDS admit (rt_host.h)
+    if ((rc = size_resident_grids(s->device, s->grids, s->n_cus, s->n_threads))) return rc;
     s->spill_depth = s->tree.max_depth > RT_TRACE_STACK ? s->tree.max_depth - RT_TRACE_STACK + 1 : 1;     // RT_TRACE_STACK <= RT_STACK_LDS
     if ((rc = s->work_counter.grow(64))) return rc;             // 8 band counters, one 64-byte line each (the pipeline uses the first)
     if ((rc = s->counters.grow(64))) return rc;                 // 8 RtCounters, 16 RT_PROFILE, 2 x 16 RT_PROFILE_STAGES

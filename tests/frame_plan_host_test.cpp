@@ -418,11 +418,143 @@ static void test_march() {
         CHECK(refused(rd, inv, no_advance)); }
 }
 
+// ---------------------------------------------------------------------------------------------- the launch
+// What a frame launches, as a table: the first row whose condition holds names the family (a query runs the radiance kernels; the queue
+// pipeline where the schedule says so; the bidirectional integrator, DirectLighting "weighted" and the debug integrator have a family each; a qualifying
+// frame takes the scene twin where the integrator has one and the scene has one light, else the fixed-frame twin; everything else the generic megakernel)
+struct LaunchCase { RtRenderDesc rd; SceneFacts sf; Schedule sc; bool query; };
+static bool lc_weighted(const LaunchCase &c) { return c.rd.integrator == RT_INTEGRATOR_DIRECT && c.rd.strategy == RT_STRATEGY_WEIGHTED; }
+static bool lc_scene_twin(const LaunchCase &c) {
+    return c.sc.fixed_frame && (c.rd.integrator == RT_INTEGRATOR_DIRECT || c.rd.integrator == RT_INTEGRATOR_PATH) && c.sf.n_lights == 1u && c.sf.scene_twins;
+}
+struct LaunchRule { Launch::Family family; bool (*holds)(const LaunchCase &); };
+static const LaunchRule launch_rules[] = {
+    {Launch::Rays, [](const LaunchCase &c) { return c.query; }},
+    {Launch::Pipeline, [](const LaunchCase &c) { return c.sc.pipeline != 0; }},
+    {Launch::Bidir, [](const LaunchCase &c) { return c.rd.integrator == RT_INTEGRATOR_BIDIRECTIONAL; }},
+    {Launch::Weighted, lc_weighted},
+    {Launch::Debug, [](const LaunchCase &c) { return c.rd.integrator == RT_INTEGRATOR_DEBUG; }},
+    {Launch::FixedScene, lc_scene_twin},
+    {Launch::Fixed, [](const LaunchCase &c) { return c.sc.fixed_frame; }},
+    {Launch::Mega, [](const LaunchCase &) { return true; }},
+};
+// the one entry k of a family's N whose flavour (and what else the family's entries differ by) `serves` accepts; -1 when none or several do
+template <class Serves> static int only_entry(int n, Serves serves) {
+    int found = -1;
+    for (int k = 0; k < n; ++k) if (serves(k)) { if (found >= 0) return -1; found = k; }
+    return found;
+}
+// ... for the request of a case: the entry counts exactly when the scene counts, is built for its accelerator and medium, and carries the EXT code when the
+// scene needs it.  Mega has more than one such entry: of those, the one with EXT exactly when the frame counts (a counting twin always carries it) or needs
+// it, and the high-occupancy flavour exactly when a timed frame without EXT asks for it
+static bool serves(const flavour::Flavour &f, const LaunchCase &c, bool has_vol = true) {
+    return f.count == c.sf.counting && f.accel == c.sf.accel_kind && (!has_vol || f.vol == c.sf.medium) && (f.ext || !c.sf.has_ext);
+}
+static int expected_entry(Launch::Family family, const LaunchCase &c, int axes) {
+    const int integ = c.rd.integrator;
+    const bool want_high = c.sc.high_occupancy != 0 && !c.sf.counting && !c.sf.has_ext;
+    switch (family) {
+    case Launch::Mega: return only_entry(flavour::Mega::N, [&](int k) { const flavour::Flavour f = flavour::Mega::flavour(k, integ); return serves(f, c) && f.ext == (c.sf.counting || c.sf.has_ext) && f.high_occ == want_high; });
+    case Launch::Fixed: return only_entry(flavour::Fixed::N, [&](int k) { return serves(flavour::Fixed::flavour(k), c) && flavour::Fixed::integrator(k) == integ; });
+    case Launch::FixedScene: return only_entry(flavour::FixedScene::N, [&](int k) { return serves(flavour::FixedScene::flavour(k), c) && flavour::FixedScene::axes(k) == axes; });
+    case Launch::Debug: return only_entry(flavour::Debug::N, [&](int k) { return serves(flavour::Debug::flavour(k), c); });
+    case Launch::Weighted: return only_entry(flavour::Weighted::N, [&](int k) { return serves(flavour::Weighted::flavour(k), c); });
+    case Launch::Bidir: return only_entry(flavour::Bidir::N, [&](int k) { return serves(flavour::Bidir::flavour(k), c, false); });      // (a medium is refused before the launch)
+    case Launch::Rays: return only_entry(flavour::Rays::N, [&](int k) { return serves(flavour::Rays::flavour(k, integ), c); });
+    case Launch::Pipeline: return 0;
+    }
+    return -1;
+}
+static void check_launch(const LaunchCase &c) {
+    const Launch ln = plan_launch(c.rd, c.sf, c.sc, c.query);
+    Launch::Family family = Launch::Mega;
+    for (const LaunchRule &r : launch_rules) if (r.holds(c)) { family = r.family; break; }
+    const int axes = family == Launch::FixedScene ? (fixed::SCENE_ONE_LIGHT | (c.sf.specular_materials ? 0 : fixed::SCENE_NO_SPECULAR)) : 0;
+    CHECK(ln.family == family);
+    CHECK(ln.integ == c.rd.integrator);
+    CHECK(ln.scene_axes == axes);
+    const int k = expected_entry(family, c, axes);
+    CHECK(k >= 0);
+    CHECK(ln.k == k);
+    // a fixed-frame kernel is timed, without EXT, without a medium and at high occupancy: plan_schedule admits no other frame to it
+    if (family == Launch::Fixed || family == Launch::FixedScene) CHECK(!c.sf.counting && !c.sf.has_ext && !c.sf.medium && c.sc.high_occupancy != 0);
+}
+
+static void test_launch() {
+    const std::optional<int> unset, off(0), on(1);
+    for (const Combo &c : combos())
+    for (int scene = 0; scene < 3; ++scene) {
+        CASE(std::string("launch: ") + c.name + (scene == 0 ? ", large scene" : scene == 1 ? ", tiny scene" : ", large scene with a medium"));
+        const std::string what = g_what;
+        const bool weighted = c.integ == RT_INTEGRATOR_DIRECT && c.strategy == RT_STRATEGY_WEIGHTED, bidir = c.integ == RT_INTEGRATOR_BIDIRECTIONAL, debug = c.integ == RT_INTEGRATOR_DEBUG;
+        if (bidir && scene == 2) continue;                // rt_render refuses the bidirectional integrator in a medium
+        for (int bits = 0; bits < 32; ++bits)             // counting, EXT, three lights (of one sample each), a specular material, a grid
+        for (const std::optional<int> &pipeline : {unset, off, on})
+        for (const std::optional<int> &fixed_frame : {unset, off, on})
+        for (const std::optional<int> &high_occ : {unset, off, on})
+        for (int query = 0; query < 2; ++query) {
+            if (query && (weighted || bidir || debug)) continue;          // plan_query refuses them
+            LaunchCase lc{desc(c.integ, c.strategy), scene == 1 ? tiny_fat() : large_scene(), Schedule{}, query != 0};
+            lc.sf.medium = scene == 2; lc.sf.counting = (bits & 1) != 0; lc.sf.has_ext = (bits & 2) != 0;
+            if (bits & 4) { lc.sf.n_lights = 3; lc.sf.light_samples = {1, 1, 1}; }
+            lc.sf.specular_materials = (bits & 8) != 0;
+            if (bits & 16) lc.sf.accel_kind = RT_ACCEL_GRID;
+            FrameKnobs kn; kn.pipeline = pipeline; kn.fixed_frame = fixed_frame; kn.high_occ = high_occ;
+            g_what = what + " bits " + std::to_string(bits) + " pipeline " + std::to_string(pipeline.value_or(-1)) + " fixed_frame " + std::to_string(fixed_frame.value_or(-1)) +
+                     " high_occ " + std::to_string(high_occ.value_or(-1)) + (query ? " query" : "");
+            lc.sc = scheduled(lc.rd, lc.sf, kn);
+            const Schedule frame = lc.sc;
+            if (query) CHECK(!plan_query(lc.rd, QueryRange{3, 8}, lc.sc));
+            check_launch(lc);
+            const Launch ln = plan_launch(lc.rd, lc.sf, lc.sc, lc.query);
+            if (weighted || bidir || debug) CHECK(ln.family != Launch::Pipeline && ln.family != Launch::Fixed && ln.family != Launch::FixedScene);
+            if (query) {                                  // ... whatever the frame itself would have taken, and without plan_query's reset of the schedule too
+                CHECK(ln.family == Launch::Rays);
+                CHECK(plan_launch(lc.rd, lc.sf, frame, true).family == Launch::Rays);
+            }
+        }
+    }
+    // ---- what the precedence decides where plan_schedule would not lead: schedules made by hand
+    const SceneFacts large = large_scene();
+    {   CASE("launch: Whitted has no scene twin"); Schedule sc = scheduled(desc(RT_INTEGRATOR_WHITTED), large); CHECK(sc.fixed_frame && sc.fixed_scene == 0);
+        sc.fixed_scene = fixed::SCENE_ONE_LIGHT | fixed::SCENE_NO_SPECULAR;
+        const Launch ln = plan_launch(desc(RT_INTEGRATOR_WHITTED), large, sc, false);
+        CHECK(ln.family == Launch::Fixed && ln.scene_axes == 0 && ln.k == 2 * RT_INTEGRATOR_WHITTED); }
+    {   CASE("launch: axes no twin was compiled for"); const RtRenderDesc rd = desc(RT_INTEGRATOR_PATH); Schedule sc = scheduled(rd, large);
+        CHECK(plan_launch(rd, large, sc, false).family == Launch::FixedScene && plan_launch(rd, large, sc, false).scene_axes == (fixed::SCENE_ONE_LIGHT | fixed::SCENE_NO_SPECULAR));
+        sc.fixed_scene = fixed::SCENE_NO_SPECULAR;        // every scene twin is compiled for one light
+        CHECK(plan_launch(rd, large, sc, false).family == Launch::Fixed && plan_launch(rd, large, sc, false).scene_axes == 0);
+        sc.fixed_scene = fixed::SCENE_ONE_LIGHT; sc.fixed_frame = false;      // no scene twin without the fixed frame
+        CHECK(plan_launch(rd, large, sc, false).family == Launch::Mega && plan_launch(rd, large, sc, false).scene_axes == 0); }
+    {   CASE("launch: a scene that keeps its frames off the scene twins"); SceneFacts sf = large; sf.scene_twins = false; const RtRenderDesc rd = desc(RT_INTEGRATOR_DIRECT, RT_STRATEGY_ONE);
+        check_launch(LaunchCase{rd, sf, scheduled(rd, sf), false});
+        CHECK(plan_launch(rd, sf, scheduled(rd, sf), false).family == Launch::Fixed); }
+    {   CASE("launch: debug ignores the fixed-frame choice"); const RtRenderDesc rd = desc(RT_INTEGRATOR_DEBUG); Schedule sc = scheduled(rd, large);
+        sc.fixed_frame = true; sc.fixed_scene = fixed::SCENE_ONE_LIGHT;
+        const Launch ln = plan_launch(rd, large, sc, false);
+        CHECK(ln.family == Launch::Debug && ln.scene_axes == 0 && ln.k == 0); }
+    for (const Combo &c : combos()) {
+        if (c.integ != RT_INTEGRATOR_BIDIRECTIONAL && !(c.integ == RT_INTEGRATOR_DIRECT && c.strategy == RT_STRATEGY_WEIGHTED)) continue;
+        CASE(std::string("launch: PIPELINE=1, ") + c.name); FrameKnobs kn; kn.pipeline = 1; const RtRenderDesc rd = desc(c.integ, c.strategy);
+        CHECK(plan_launch(rd, large, scheduled(rd, large, kn), false).family == (c.integ == RT_INTEGRATOR_BIDIRECTIONAL ? Launch::Bidir : Launch::Weighted)); }
+    {   CASE("launch: a query takes neither the pipeline nor a fixed kernel"); const RtRenderDesc rd = desc(RT_INTEGRATOR_PATH); Schedule sc = scheduled(rd, large);
+        sc.pipeline = 1; sc.fixed_frame = true; sc.fixed_scene = fixed::SCENE_ONE_LIGHT;
+        const Launch ln = plan_launch(rd, large, sc, true);
+        CHECK(ln.family == Launch::Rays && ln.scene_axes == 0 && ln.k == 0 && ln.integ == RT_INTEGRATOR_PATH); }
+    {   CASE("request: without a frame"); SceneFacts sf = large; sf.accel_kind = RT_ACCEL_GRID; sf.medium = true; sf.has_ext = true; sf.counting = true;
+        const flavour::Request r = request(nullptr, sf, nullptr), z = request(nullptr, large, nullptr);
+        CHECK(r.integ == 0 && r.grid && r.vol && r.count && r.ext && !r.high_occ);
+        CHECK(z.integ == 0 && !z.grid && !z.vol && !z.count && !z.ext && !z.high_occ);
+        const RtRenderDesc rd = desc(RT_INTEGRATOR_PATH); Schedule sc = scheduled(rd, large);
+        CHECK(sc.high_occupancy == 1 && request(&rd, large, &sc).high_occ && request(&rd, large, &sc).integ == RT_INTEGRATOR_PATH && !request(&rd, large, nullptr).high_occ); }
+}
+
 int main() {
     test_requests();
     test_extent();
     test_schedule();
     test_march();
+    test_launch();
     if (g_failed) { std::fprintf(stderr, "frame_plan_host_test: %d checks failed\n", g_failed); return 1; }
     std::printf("frame_plan_host_test: ok (%d cases)\n", g_cases);
     return 0;

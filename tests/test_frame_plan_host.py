@@ -1,5 +1,5 @@
 """What the host plans for a frame (pbrt-v1_amd/csrc/hip/rt_frame_plan.h), on the host: tests/frame_plan_host_test.cpp checks the work extent, the
-sample-request tables, the scheduling policy with its knobs and the medium's march bounds against the reference's rules and the policy as DESIGN.md
+sample-request tables, the scheduling policy with its knobs, the medium's march bounds and the launch (plan_launch: family and table entry) against the reference's rules and the policy as DESIGN.md
 states it, as a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer.  No GPU, no HIP header: that the program compiles with
 a host compiler is the proof that the header has none."""
 import os
@@ -29,7 +29,7 @@ def test_frame_plan_under_sanitizers(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
     out = r.stdout + r.stderr
     assert r.returncode == 0, out
-    assert "frame_plan_host_test: ok (235 cases)" in r.stdout, out
+    assert "frame_plan_host_test: ok (264 cases)" in r.stdout, out
     for word in ("Sanitizer", "runtime error", "CHECK("):
         assert word not in out, out
 
