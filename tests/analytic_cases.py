@@ -6,7 +6,8 @@ Every case names the term it is there for and one wrong twin of its form that th
 
 Two families read the hit itself: "geometry" cases run SurfaceIntegrator "debug" with one channel triple (u, v, the normals, the hit mask of
 the camera ray), "textures" cases light a surface whose material parameters come from Texture graphs, so that a sample is
-f(material resolved at the hit) I / d^2 |cos|."""
+f(material resolved at the hit) I / d^2 |cos|.  The "march" family runs the volume integrators "emission" and "single" through homogeneous, exponential
+and volumegrid regions: their marches draw random offsets, so a sample is held to the exact integral within the allowance D of analytic_forms.Scene.allowance."""
 import importlib.util
 import os
 import re
@@ -30,7 +31,7 @@ SCENES = _scenes()
 RES = 64
 COLORS = {"Kd", "Ks", "Kr", "Kt", "reflect", "transmit", "opacity", "I", "L", "sigma_a", "sigma_s", "Le"}
 POINTS = {"from", "to", "p0", "p1", "p2"}
-FAMILIES = ("lights", "lobes", "quadrics", "specular", "medium", "geometry", "textures")
+FAMILIES = ("lights", "lobes", "quadrics", "specular", "medium", "geometry", "textures", "march")
 
 PLANE_CAM = dict(lookat=(0, 2, -6, 0, .6, 0, 0, 1, 0))
 QUADRIC_CAM = dict(lookat=(0, 0, -4, 0, 0, 0, 0, 1, 0))
@@ -290,6 +291,69 @@ PROBES = {
 }
 
 
+# ------------------------------------------------------------------------------------------------ march: the volume integrators and density media
+# The plane-and-box layout of medium_homogeneous with ONE delta light outside the box.  A march draws (the scatter offset, every Tau's offset),
+# so these cases are held to the exact integral within the allowance D of analytic_forms.Scene.allowance, which bounds what any draw can do;
+# the conditions that keep every other draw out are asserted there.  The "_tr" cases (Le black under "emission": transmittances alone) may be
+# thick and take a small step, so that D (first order in stepsize x sigma_t) stays a few percent; the "_thin" cases have an optical depth of the
+# order of 0.01, because a density region's marched Tr is only known to about half its optical depth (per-step Taus at .5 stepsize).
+BOX = dict(p0=(-3, 0, -2.5), p1=(3, 3.5, 4))
+SMALL_BOX = dict(p0=(-2, 0, -2), p1=(2, 2.5, 2))
+VOL_CTM = [("Translate", .3, .8, .5), ("Rotate", 25, 0, 1, 0), ("Rotate", 8, 1, 0, 0), ("Scale", 1.2, .9, 1.1)]
+SIGMA = dict(sigma_a=(.05, .08, .12), sigma_s=(.1, .06, .03))
+M_POINT = dict(kind="point", I=(75, 62, 50), **{"from": (1, 5, 1)})
+UPDIR = (.6, 2, .4)                   # off the axes and of length 2.13: Normalize(up) is part of the term
+
+
+def grid_values(nx, ny, nz, seed):
+    """seeded densities in [0, 2) with three decimals (exact in the scene text)"""
+    return np.round(np.random.default_rng(seed).random(nx * ny * nz) * 2.0, 3).astype(np.float32)
+
+
+def march_case(term, twin, medium, integrator, stepsize, light=M_POINT, material=MATTE, **kw):
+    return plane_case(term, twin, [light], material, family="march", volume_integrator=integrator, stepsize=stepsize, medium=medium, **kw)
+
+
+GRID = dict(kind="volumegrid", nx=3, ny=4, nz=5, values=grid_values(3, 4, 5, 11))
+CASES.update({
+    "march_emission": march_case("homogeneous with Le: T Lo + Lv, Lv = Le (1 - exp(-sigma_t l)) / sigma_t per channel", "emission_unattenuated",
+                                 dict(kind="homogeneous", Le=(.3, .2, .4), **BOX, **SIGMA), "emission", .03),
+    "march_single_forward": march_case("homogeneous, single scattering of a point light, g = .6: sigma_s PhaseHG L T_shadow along the ray", "phase_g_sign_flipped",
+                                       dict(kind="homogeneous", g=.6, **BOX, **SIGMA), "single", .05),
+    "march_single_back_spot": march_case("homogeneous, single scattering of a spot light whose cone edge crosses the box, g = -.4, the camera inside the box",
+                                         "shadow_transmittance_dropped", dict(kind="homogeneous", g=-.4, p0=(-3, 0, -7), p1=(3, 3.5, 4), **SIGMA), "single", .025,
+                                         light=dict(kind="spot", I=(150, 130, 110), coneangle=30, conedeltaangle=12, **{"from": (0, 5, -1), "to": (.3, 0, 0)})),
+    "dens_exp_tr": march_case("exponential density: the height from pMin along Normalize(updir); Tau at stepsize and at 4 x stepsize", "height_from_origin",
+                              dict(kind="exponential", a=1, b=.5, updir=UPDIR, **BOX, **SIGMA), "emission", .02, also=("updir_unnormalised",)),
+    "dens_exp_ctm_tr": march_case("the same region declared under Translate / Rotate / non-uniform Scale: WorldToVolume", "volume_ctm_ignored",
+                                  dict(kind="exponential", a=1, b=.5, updir=UPDIR, ctm=VOL_CTM, **SMALL_BOX, **SIGMA), "emission", .02),
+    "dens_grid_tr": march_case("volumegrid 3 x 4 x 5: the - .5 voxel offset, Floor2Int below 0, clamped corners, z-y-x order, the lerps", "voxel_centres_at_corners",
+                               dict(GRID, sigma_a=(.04, .06, .09), sigma_s=(.06, .04, .02), **BOX), "emission", .01, also=("grid_axes_transposed",)),
+    "dens_grid_ctm_tr_grid": march_case("the same grid under a CTM, through the grid accelerator", "volume_ctm_ignored",
+                                        dict(GRID, sigma_a=(.04, .06, .09), sigma_s=(.06, .04, .02), ctm=VOL_CTM, **SMALL_BOX), "emission", .01, accel="grid"),
+    "dens_exp_emission_thin": march_case("a thin exponential region with Le: Lve = Density le", "height_from_origin",
+                                         dict(kind="exponential", a=1, b=.5, updir=UPDIR, Le=(.3, .2, .4), sigma_a=(.0008, .001, .0012), sigma_s=(.0008, .0006, .0004), **BOX),
+                                         "emission", .04),
+    "dens_grid_single_thin": march_case("a thin volumegrid, single scattering, g = .5: sigma_s Density(p), PhaseHG, the shadow Tau at 4 x stepsize", "sigma_s_not_scaled_by_density",
+                                        dict(GRID, g=.5, sigma_a=(.0002, .0002, .0002), sigma_s=(.0008, .0006, .0004), **BOX), "single", .025,
+                                        light=dict(kind="point", I=(40000, 33000, 27000), **{"from": (1, 5, 1)}), material=("matte", dict(Kd=(.005, .004, .003))),
+                                        also=("phase_g_sign_flipped",)),
+})
+
+
+def _volume_text(med):
+    """the Volume statement of a march case between AttributeBegin and AttributeEnd, so that its CTM is the region's alone"""
+    out = ['"point p0" [%s] "point p1" [%s] "color sigma_a" [%s] "color sigma_s" [%s]' % tuple(_fmt(med[k]) for k in ("p0", "p1", "sigma_a", "sigma_s"))]
+    if "Le" in med:
+        out.append('"color Le" [%s]' % _fmt(med["Le"]))
+    out += ['"float %s" [%s]' % (k, _fmt(med[k])) for k in ("g", "a", "b") if k in med]
+    if "updir" in med:
+        out.append('"vector updir" [%s]' % _fmt(med["updir"]))
+    if med["kind"] == "volumegrid":
+        out.append('"integer nx" [%d] "integer ny" [%d] "integer nz" [%d] "float density" [%s]' % (med["nx"], med["ny"], med["nz"], _fmt(med["values"])))
+    return 'AttributeBegin\n%sVolume "%s" %s\nAttributeEnd\n' % (_ctm_text(med.get("ctm", [])), med["kind"], " ".join(out))
+
+
 def _fmt(v):
     return " ".join("%.9g" % float(np.float32(x)) for x in np.atleast_1d(v))
 
@@ -360,9 +424,15 @@ def scene_text(name, jitter=False, seed=7, probe_dump=None):
     if "lensradius" in cam:
         extra += ' "float lensradius" [%s] "float focaldistance" [%s]' % (_fmt(cam["lensradius"]), _fmt(cam["focaldistance"]))
     out.append('Camera "%s"%s\n' % (kind, extra))
-    out.append('Film "image" "integer xresolution" [%d] "integer yresolution" [%d] "string filename" ["out.exr"]\n' % (xres, yres))
+    march = name in CASES and c["family"] == "march"
+    # (a march case: a camera ray that hits nothing has alpha 0 and still carries Lv; the film must not multiply it away)
+    out.append('Film "image" "integer xresolution" [%d] "integer yresolution" [%d] "string filename" ["out.exr"]%s\n' % (xres, yres, ' "bool premultiplyalpha" ["false"]' if march else ""))
     if jitter:
         out.append('Sampler "stratified" "integer seed" [%d] "integer xsamples" [2] "integer ysamples" [2] "bool jitter" ["true"]\n' % seed)
+    elif march:
+        # a march draws: the reference runs with its random numbers keyed by camera sample (the oracle-side sampler wrapper, which the product's
+        # parser unwraps into its own seed parameter), so that its film can be compared with the device's pixel by pixel
+        out.append('Sampler "keyed" "string inner" ["stratified"] "integer seed" [0] "integer xsamples" [1] "integer ysamples" [1] "bool jitter" ["false"]\n')
     else:
         out.append('Sampler "stratified" "integer xsamples" [1] "integer ysamples" [1] "bool jitter" ["false"]\n')
     out.append('PixelFilter "box" "float xwidth" [.5] "float ywidth" [.5]\n')
@@ -373,7 +443,7 @@ def scene_text(name, jitter=False, seed=7, probe_dump=None):
     else:
         out.append('SurfaceIntegrator "whitted" "integer maxdepth" [%d]\n' % c.get("maxdepth", 0))
     if c.get("volume_integrator"):
-        out.append('VolumeIntegrator "%s"\n' % c["volume_integrator"])
+        out.append('VolumeIntegrator "%s"%s\n' % (c["volume_integrator"], (' "float stepsize" [%s]' % _fmt(c["stepsize"])) if "stepsize" in c else ""))
     out.append('Accelerator "%s"\nWorldBegin\n' % c.get("accel", "kdtree"))
     for l in c["lights"]:
         out.append("AttributeBegin\n%sLightSource \"%s\" %s\nAttributeEnd\n" % (_ctm_text(l.get("ctm", [])), l["kind"], _params(l)))
@@ -389,7 +459,9 @@ def scene_text(name, jitter=False, seed=7, probe_dump=None):
         else:
             out.append('Shape "%s" %s\n' % (kind, _params(sp)))
         out.append("AttributeEnd\n")
-    if c.get("medium"):
+    if c.get("medium") and "kind" in c["medium"]:
+        out.append(_volume_text(c["medium"]))
+    elif c.get("medium"):
         out.append('Volume "homogeneous" %s\n' % _params(c["medium"]))
     out.append("WorldEnd\n")
     return "".join(out)
@@ -425,6 +497,8 @@ def _textures(decls, twin):
         made[t["name"]] = F.Texture(t["cls"], mapping, twin=twin, **p)
     return made
 LIGHT_TWINS = {"spot_axis_untransformed"}
+MEDIUM_TWINS = {"height_from_origin", "updir_unnormalised", "voxel_centres_at_corners", "grid_axes_transposed", "volume_ctm_ignored", "phase_g_sign_flipped",
+                "emission_unattenuated", "shadow_transmittance_dropped", "sigma_s_not_scaled_by_density"}
 
 
 def form(name, wrong=False):
@@ -455,7 +529,11 @@ def form(name, wrong=False):
             surfaces.append((shape, F.Material(s["material"][0], twin=mtwin, **s["material"][1])))
     med = c.get("medium")
     medium = F.Medium(med["p0"], med["p1"], med["sigma_a"], med["sigma_s"]) if med else None
-    return F.Scene(camera, surfaces, lights, medium, c.get("maxdepth", 0), twin=twin if twin not in MATERIAL_TWINS | SHAPE_TWINS | LIGHT_TWINS | TEXTURE_TWINS else None,
+    if med and "kind" in med:
+        more = {k: med[k] for k in ("Le", "g", "a", "b", "updir", "nx", "ny", "nz", "values") if k in med}
+        medium = F.Medium(med["p0"], med["p1"], med["sigma_a"], med["sigma_s"], v2w=_ctm(med.get("ctm", [])), kind=med["kind"], integrator=c["volume_integrator"],
+                          stepsize=c["stepsize"], twin=twin if twin in MEDIUM_TWINS else None, **more)
+    return F.Scene(camera, surfaces, lights, medium, c.get("maxdepth", 0), twin=twin if twin not in MATERIAL_TWINS | SHAPE_TWINS | LIGHT_TWINS | TEXTURE_TWINS | MEDIUM_TWINS else None,
                    debug=c.get("debug"))
 
 
@@ -477,10 +555,10 @@ def measure(name, rgb, alpha):
     ix, iy = pixel_centres()
     ix, iy = ix[:RES, :RES], iy[:RES, :RES]
     sc = form(name)
-    L, _, _ = sc.samples(ix, iy)
+    L, D = evaluate(sc, ix, iy)
     band = F.band(sc, ix, iy)
     inc = ~band
-    e = F.sample_error(rgb, L, inc)
+    e = F.sample_error(rgb, L, inc, D)
     o, d, mint, maxt = sc.camera.rays(ix, iy)
     t, n, idx, root = sc.closest(o, d, mint, maxt)
     hit = (idx >= 0).astype(np.float64)
@@ -501,21 +579,52 @@ def measure(name, rgb, alpha):
         falloff = float((spots[0].sample(p)[3] == 1)[hit > 0].mean())
     return dict(band=band, band_share=float(band.mean()), ref_err=float(e[inc].max()), hit_share=float(hit.mean()), lcase=float(np.abs(L[inc]).max()),
                 alpha_equal=alpha_ok, far_root_share=float(((root == 1) & (hit > 0)).mean()),
-                falloff_share=falloff, L=L, e=e)
+                falloff_share=falloff, L=L, e=e, D=D, tight_share=tight_share(L, D, inc), tightness=tightness(rgb, L, D, inc))
+
+
+MAX_ALLOWANCE = 0.05        # a march case's allowance D stays under this share of the sample's scale ...
+MIN_TIGHT_SHARE = 0.90      # ... on at least this share of the included samples, so that D cannot hide a failure
+
+
+def evaluate(sc, ix, iy):
+    """-> L and the allowance D (None for a scene without a marched medium: its samples are draw-free and held to L itself)"""
+    if sc.medium is not None and sc.medium.marches:
+        L, D, _, _ = sc.allowance(ix, iy)
+        return L, D
+    return sc.samples(ix, iy)[0], None
+
+
+def tight_share(L, D, inc):
+    """the share of the included samples whose allowance (its largest channel) is at most MAX_ALLOWANCE of the sample's scale"""
+    return 1.0 if D is None else float((D.max(-1) <= MAX_ALLOWANCE * F.sample_scale(L, inc))[inc].mean())
+
+
+def tightness(got, L, D, inc):
+    """the largest |got - L| / D over the included samples and channels whose D is at least a thousandth of the sample's scale (below that
+    rounding, not a draw, is what is left): how much of its allowance a renderer uses"""
+    if D is None:
+        return 0.0
+    big = (D >= 1e-3 * F.sample_scale(L, inc)[..., None]) & inc[..., None]
+    with np.errstate(all="ignore"):
+        return float(np.where(big, np.abs(np.asarray(got, np.float64) - L) / D, 0.0).max())
 
 
 def bar(name, ref_errs):
-    """4 x max(ref_err of the case, median ref_err over the case's family): the reference's own deviation from float64 is the scale"""
+    """4 x max(ref_err of the case, median ref_err over the case's family): the reference's own deviation from float64 is the scale.  A "march"
+    case's ref_err is the reference's largest EXCESS over its allowance, which is 0 where the reference sits inside D everywhere: the
+    float-rounding scale of the same exp(-tau) arithmetic, medium_homogeneous's ref_err, is a third term, so that the bar cannot collapse."""
     fam = [v for n, v in ref_errs.items() if CASES[n]["family"] == CASES[name]["family"]]
-    return BAR_FACTOR * max(ref_errs[name], float(np.median(fam)))
+    more = [ref_errs["medium_homogeneous"]] if CASES[name]["family"] == "march" else []
+    return BAR_FACTOR * max([ref_errs[name], float(np.median(fam))] + more)
 
 
 def twin_share(name, rgb, band, bar_value, twin=True):
-    """the share of the included samples on which the reference's film lies beyond 10 x the bar from the case's wrong twin (or the named one)"""
+    """the share of the included samples on which the reference's film lies beyond 10 x the bar (a march case: beyond the twin's allowance D plus
+    10 x the bar) from the case's wrong twin (or the named one)"""
     ix, iy = pixel_centres()
-    L, _, _ = form(name, wrong=twin).samples(ix[:RES, :RES], iy[:RES, :RES])
+    L, D = evaluate(form(name, wrong=twin), ix[:RES, :RES], iy[:RES, :RES])
     inc = ~band
-    return float((F.sample_error(rgb, L, inc)[inc] > 10 * bar_value).mean())
+    return float((F.sample_error(rgb, L, inc, D)[inc] > 10 * bar_value).mean())
 
 
 def measure_probe(name, rec):

@@ -1,6 +1,7 @@
 """Float64 closed forms of what one Whitted camera sample computes in a scene of a few analytic surfaces lit by delta lights: cameras,
 ray / quad and ray / quadric intersection, point / spot / distant lights, the BSDFs of matte, plastic, uber, shinymetal and translucent
-as the reference assembles them, the mirror step and the transmittance of a homogeneous medium; and of what the hit itself carries: a
+as the reference assembles them, the mirror step, the transmittance of a homogeneous medium and what the volume integrators "emission" and "single" estimate
+by marching a homogeneous, exponential or volumegrid region (Medium: the exact integral and an allowance for the march's random offsets); and of what the hit itself carries: a
 triangle mesh's barycentrics, (u, v), geometric and shading normal (Mesh), the quadrics' (u, v), the texture classes and 2-D mappings evaluated
 at the hit (Texture, Mapping), materials resolved from them per sample (Textured) and the debug integrator's channels.  Plain numpy, vectorised over samples,
 independent of the package: tests/test_analytic_host.py proves on the reference's films that these are the reference's functions,
@@ -755,12 +756,186 @@ class Material:
 # ------------------------------------------------------------------------------------------------ medium
 class Medium:
     """Volume "homogeneous" (volumes/homogeneous.cpp:63-67): tau over the part of a ray's [mint, maxt] inside the box p0..p1 (in volume
-    space, core/volume.cpp's IntersectP through BBox::IntersectP) is its world length times sigma_a + sigma_s"""
+    space, core/volume.cpp's IntersectP through BBox::IntersectP) is its world length times sigma_a + sigma_s.
 
-    def __init__(self, p0, p1, sigma_a, sigma_s, v2w=None):
+    With Le, single scattering or a density (kinds "exponential", "volumegrid") the region is one that the volume integrator MARCHES with
+    random offsets.  The float64 side then states the exact integrals (depth(), lv()) and, beside them, an allowance that bounds what any
+    offset can do (interval(), lv()); it never replays a draw.  Lengths s along a ray are world lengths along its unit direction."""
+
+    def __init__(self, p0, p1, sigma_a, sigma_s, v2w=None, kind="homogeneous", Le=(0, 0, 0), g=0.0, a=1.0, b=1.0, updir=(0, 1, 0),
+                 nx=1, ny=1, nz=1, values=None, integrator="emission", stepsize=1.0, twin=None):
+        """kind "exponential" (volumes/exponential.cpp) and "volumegrid" (volumes/volumegrid.cpp) are DensityRegions (core/volume.h:62-90):
+        sigma_a, sigma_s and Le are scaled by Density(WorldToVolume(p)).  v2w: the CTM at the Volume statement.  integrator, stepsize: the
+        VolumeIntegrator ("emission", integrators/emission.cpp; "single", integrators/single.cpp).  twin: a deliberately wrong variant (tests only)."""
         self.p0, self.p1 = np.minimum(f32(p0), f32(p1)), np.maximum(f32(p0), f32(p1))
+        self.sigma_s = f32(sigma_s) * np.ones(3)
         self.sigma_t = f32(sigma_a) * np.ones(3) + f32(sigma_s) * np.ones(3)
-        self.w2v = np.linalg.inv(np.eye(4) if v2w is None else v2w)
+        self.w2v = np.linalg.inv(np.eye(4) if (v2w is None or twin == "volume_ctm_ignored") else v2w)
+        self.kind, self.twin, self.integrator, self.step = kind, twin, integrator, float(f32(stepsize))
+        self.le, self.g = f32(Le) * np.ones(3), float(f32(g)) * (-1.0 if twin == "phase_g_sign_flipped" else 1.0)
+        self.a, self.b = float(f32(a)), float(f32(b))
+        self.up = f32(updir) if twin == "updir_unnormalised" else _norm(f32(updir))            # exponential.cpp:33
+        self.n = np.array([int(nx), int(ny), int(nz)])
+        self.values = None if values is None else f32(values).ravel()
+        # a region that the float64 side integrates along the ray and that carries an allowance (Scene.allowance); the homogeneous box under
+        # "emission" with Le black is the closed form below and has none
+        self.marches = kind != "homogeneous" or integrator == "single" or bool(self.le.any())
+
+    # ---- the region along a ray ----------------------------------------------------------------------------------------------------
+    def clip(self, o, d, lo, hi):
+        """-> the unit direction and the part [s0, s1] of o + s dn, s a WORLD length, inside the extent (DensityRegion::Tau normalises the
+        direction and scales mint and maxt, core/volume.cpp:145-150; IntersectP takes the ray to volume space, where s is still the parameter),
+        and whether there is such a part.  Where there is none s0 = s1 = 0."""
+        length = np.linalg.norm(d, axis=-1)
+        dn = d / length[..., None]
+        oo, od = xpoint(self.w2v, o), xvec(self.w2v, dn)
+        t0, t1 = np.broadcast_to(lo, length.shape) * length, np.broadcast_to(hi, length.shape) * length
+        with np.errstate(all="ignore"):
+            for a in range(3):
+                inv = 1.0 / od[..., a]
+                tn, tf = (self.p0[a] - oo[..., a]) * inv, (self.p1[a] - oo[..., a]) * inv
+                tn, tf = np.minimum(tn, tf), np.maximum(tn, tf)
+                t0, t1 = np.maximum(t0, np.where(np.isnan(tn), -np.inf, tn)), np.minimum(t1, np.where(np.isnan(tf), np.inf, tf))
+            ok = np.isfinite(t0) & np.isfinite(t1) & (t1 > t0)
+        return dn, np.where(ok, t0, 0.0), np.where(ok, t1, 0.0), ok
+
+    def density(self, p):
+        """Density(WorldToVolume(p)) at points of a clipped segment (so the extent's Inside test, which only rounding could fail there, is left out)"""
+        q = xpoint(self.w2v, p)
+        if self.kind == "homogeneous":
+            return np.ones(q.shape[:-1])
+        if self.kind == "exponential":                                                         # exponential.cpp:40-44
+            rel = q if self.twin == "height_from_origin" else q - self.p0
+            return self.a * np.exp(-self.b * _dot(rel, self.up))
+        # volumegrid.cpp:64-84: voxel centres at (i + .5) / n, Floor2Int, indices clamped, density[z nx ny + y nx + x], lerps along x, then y, then z
+        nx, ny, nz = self.n
+        vox = (q - self.p0) / (self.p1 - self.p0) * self.n - (0.0 if self.twin == "voxel_centres_at_corners" else 0.5)
+        v = np.floor(vox)
+        dx, dy, dz = (vox - v)[..., 0], (vox - v)[..., 1], (vox - v)[..., 2]
+        v = v.astype(np.int64)
+
+        def D(ax, ay, az):
+            x, y, z = np.clip(v[..., 0] + ax, 0, nx - 1), np.clip(v[..., 1] + ay, 0, ny - 1), np.clip(v[..., 2] + az, 0, nz - 1)
+            return self.values[(x * ny * nz + y * nz + z) if self.twin == "grid_axes_transposed" else (z * nx * ny + y * nx + x)]
+        lerp = lambda t, a, b: (1 - t) * a + t * b
+        d00, d10 = lerp(dx, D(0, 0, 0), D(1, 0, 0)), lerp(dx, D(0, 1, 0), D(1, 1, 0))
+        d01, d11 = lerp(dx, D(0, 0, 1), D(1, 0, 1)), lerp(dx, D(0, 1, 1), D(1, 1, 1))
+        return lerp(dz, lerp(dy, d00, d10), lerp(dy, d01, d11))
+
+    def density_bounds(self):
+        """(max f, a bound of the total variation of f along ANY straight segment inside the extent), f = Density: crude and global, for the thin
+        regions where they enter at second order.  An exponential is monotone along a line: TV <= max - min over the box.  A line crosses at most
+        nx + ny + nz + 1 cells of the grid, and inside a cell the trilinear value stays between its corners'."""
+        if self.kind == "homogeneous":
+            return 1.0, 0.0
+        if self.kind == "exponential":
+            c = np.array([[x, y, z] for x in (self.p0[0], self.p1[0]) for y in (self.p0[1], self.p1[1]) for z in (self.p0[2], self.p1[2])])
+            f = self.a * np.exp(-self.b * _dot(c if self.twin == "height_from_origin" else c - self.p0, self.up))
+            return float(f.max()), float(f.max() - f.min())
+        return float(self.values.max()), float((self.n.sum() + 1) * (self.values.max() - self.values.min()))
+
+    PIECES = 32
+
+    def nodes(self, o, dn, s0, s1, q, pieces=True):
+        """Quadrature along the clipped segment: it is cut into pieces on which the integrand is smooth (a volumegrid: at every plane through
+        voxel centres, between which the trilinear density is a cubic of s; otherwise PIECES equal parts), and each piece gets the q Gauss-Legendre
+        nodes.  -> s [.., K] in ascending order, the piece ends included (with weight 0: they serve the total variation), and the weights."""
+        if self.kind == "volumegrid" and pieces:
+            oo, od = xpoint(self.w2v, o), xvec(self.w2v, dn)
+            cuts = [s0[..., None], s1[..., None]]
+            off = 0.0 if self.twin == "voxel_centres_at_corners" else 0.5
+            for a in range(3):
+                c = self.p0[a] + (np.arange(self.n[a]) + off) / self.n[a] * (self.p1[a] - self.p0[a])
+                with np.errstate(all="ignore"):
+                    s = (c - oo[..., a, None]) / od[..., a, None]
+                cuts.append(np.clip(np.where(np.isfinite(s), s, 0.0), s0[..., None], s1[..., None]))
+            B = np.sort(np.concatenate(cuts, -1), -1)
+        elif pieces:
+            B = s0[..., None] + (s1 - s0)[..., None] * np.linspace(0.0, 1.0, self.PIECES + 1)
+        else:
+            B = np.stack([s0, s1], -1)
+        x, w = np.polynomial.legendre.leggauss(q)
+        lo, hi = B[..., :-1], B[..., 1:]
+        mid, half = (lo + hi) / 2, (hi - lo) / 2
+        s = np.concatenate([lo[..., None], mid[..., None] + half[..., None] * x], -1).reshape(lo.shape[:-1] + (-1,))
+        ww = np.concatenate([np.zeros(lo.shape + (1,)), half[..., None] * w], -1).reshape(s.shape)
+        return np.concatenate([s, B[..., -1:]], -1), np.concatenate([ww, np.zeros(s.shape[:-1] + (1,))], -1)
+
+    def depth(self, o, d, lo, hi, q=3, pieces=True):
+        """of f = Density along the part of the ray inside the extent: the exact integral (a cubic per piece under 3 nodes; an exponential to
+        1e-12 on PIECES parts), its total variation over the nodes and piece ends, its maximum.  Times sigma_t this is tau."""
+        dn, s0, s1, ok = self.clip(o, d, lo, hi)
+        s, w = self.nodes(o, dn, s0, s1, q, pieces)
+        f = self.density(o[..., None, :] + s[..., None] * dn[..., None, :]) * ok[..., None]
+        return (w * f).sum(-1), np.abs(np.diff(f, axis=-1)).sum(-1), f.max(-1)
+
+    def interval(self, o, d, lo, hi, h):
+        """Transmittance over [lo, hi] of the ray as Tau computes it with step h and ANY offset u in [0, 1) (core/volume.cpp:139-157): samples of
+        f every h from s0 + u h while s < s1.  Cell k holds sample k and the last cell overhangs s1 by at most h, so the sum differs from the
+        integral by at most h (TV(f; [s0, s1]) + max f).  -> exp(-tau), tau, that bound of tau (per channel).  A homogeneous region's Tau is
+        its length times sigma_t whatever u (volumes/homogeneous.cpp:63-67)."""
+        tau, tv, fmax = self.depth(o, d, lo, hi)
+        dd = 0.0 * tau if self.kind == "homogeneous" else h * (tv + fmax)
+        return np.exp(-tau[..., None] * self.sigma_t), tau[..., None] * self.sigma_t, dd[..., None] * self.sigma_t
+
+    # ---- VolumeIntegrator::Li ------------------------------------------------------------------------------------------------------------
+    def phase(self, cos):
+        """PhaseHG(w, wp, g) (core/volume.cpp:44-49) at cos = Dot(w, wp).  The integrators call p(p, -ray.d, -wi) (single.cpp:107), so cos is
+        Dot(ray.d, wi): g > 0 favours light that keeps its direction on the way to the camera."""
+        g = self.g
+        return (1 - g * g) / (4 * PI * (1 + g * g - 2 * g * cos) ** 1.5)
+
+    def lv(self, o, d, lo, hi, light):
+        """The exact value of what EmissionIntegrator::Li / SingleScattering::Li estimate along the camera ray (emission.cpp:61-95, single.cpp:56-116),
+        the integral over the part [s0, s1] inside the extent of
+            g(s) = Tr(s) (Lve(s) + sigma_s(s) PhaseHG(Dot(ray.d, wi)) L_light(s) T_shadow(s)),
+        and the allowance: the march puts ONE sample into each of N = ceil((s1 - s0) / stepsize) cells that tile [s0, s1] exactly, at the same
+        offset in each, so its sum differs from the integral by at most step TV(g).  In a density region the march's Tr is a product of per-step Taus
+        at .5 stepsize and T_shadow a Tau at 4 stepsize: with every tau within dc (ds) of the integral, each term is within a factor
+        exp(+-(dc + ds)) of g.  -> Lv, D, the lower end of Tr at s1 (the roulette's quantity)."""
+        shape = o.shape[:-1]
+        o, d = o.reshape(-1, 3), d.reshape(-1, 3)
+        lo, hi = np.broadcast_to(lo, shape).reshape(-1), np.broadcast_to(hi, shape).reshape(-1)
+        Lv, Dv, trlow = np.zeros((len(o), 3)), np.zeros((len(o), 3)), np.ones((len(o), 3))
+        single = self.integrator == "single" and light is not None and bool(self.sigma_s.any())
+        fmax, tvmax = self.density_bounds()
+        for b0 in range(0, len(o), 2048):                      # a block of rays at a time (the nodes of a block: a few hundred thousand points)
+            sl = slice(b0, b0 + 2048)
+            dn, s0, s1, ok = self.clip(o[sl], d[sl], lo[sl], hi[sl])
+            s, w = self.nodes(o[sl], dn, s0, s1, 4)
+            p = o[sl, None, :] + s[..., None] * dn[:, None, :]
+            dens = self.density(p)
+            if self.kind == "homogeneous":
+                cum = s - s0[:, None]
+            else:             # the depth up to each node by the trapezoid rule over the nodes: the regions marched here are thin (tau of order .01)
+                cum = np.concatenate([np.zeros((len(s), 1)), np.cumsum((dens[:, 1:] + dens[:, :-1]) / 2 * np.diff(s, axis=-1), -1)], -1)
+            tr = np.exp(-cum[..., None] * self.sigma_t)
+            g = (1.0 if self.twin == "emission_unattenuated" else tr) * dens[..., None] * self.le
+            if single:
+                li, wi, pos, _ = light.sample(p)
+                tau_s = self.depth(p, pos - p, RAY_EPSILON, 1 - RAY_EPSILON, q=6 if self.kind == "volumegrid" else 3, pieces=self.kind == "exponential")[0]
+                tsh = 1.0 if self.twin == "shadow_transmittance_dropped" else np.exp(-tau_s[..., None] * self.sigma_t)
+                ss = self.sigma_s * (1.0 if self.twin == "sigma_s_not_scaled_by_density" else dens[..., None])
+                g = g + tr * ss * self.phase(_dot(dn[:, None, :], wi))[..., None] * li * tsh
+            g = g * ok[:, None, None]
+            n = np.maximum(np.ceil((s1 - s0) / self.step), 1.0)
+            step = ((s1 - s0) / n)[:, None]
+            integral, tv = (w[..., None] * g).sum(-2), np.abs(np.diff(g, axis=-2)).sum(-2)
+            # float32: where the segment ends ON the extent (not at the ray's own mint or at the surface hit), a first sample at u near 0 or a last
+            # one at u near 1 lies within rounding of that face, and Inside() of the rounded point may answer no: Density, sigma_s and Lve are 0 there
+            # and the cell's term is lost.  One end at most for a given u.
+            length = np.linalg.norm(d[sl], axis=-1)
+            on_face0, on_face1 = (s0 > lo[sl] * length)[:, None], (s1 < hi[sl] * length)[:, None]
+            dev = step * (tv + np.maximum(g[:, 0] * on_face0, g[:, -1] * on_face1))
+            dc = 0.0
+            if self.kind != "homogeneous":
+                # every step's Tau at .5 stepsize: (h / 2) (TV over the step + max f) each; the overhangs add up over the n steps and the start
+                dc = 0.5 * self.step * (tvmax + (n[:, None] + 1) * fmax) * self.sigma_t
+                ds = (4 * self.step * (tvmax + fmax) * self.sigma_t) if single else 0.0
+                dev = dev + np.expm1(dc + ds) * (integral + dev)
+            Lv[sl], Dv[sl] = integral, dev
+            trlow[sl] = np.exp(-(cum[:, -1, None] * self.sigma_t + dc))
+        return Lv.reshape(shape + (3,)), Dv.reshape(shape + (3,)), trlow.reshape(shape + (3,))
 
     def transmittance(self, o, d, mint, maxt):
         oo, od = xpoint(self.w2v, o), xvec(self.w2v, d)
@@ -788,6 +963,8 @@ class Scene:
         self.debug = debug
         self.trace = dict(cells=[], wraps=[])
         self.mats = {}
+        self.sig_only = False          # band(): only the signature is read, so a march's integral is left out
+        self.D = None                  # the allowance of the last li() (zero without a marched medium)
 
     def details(self, o, d, mint, maxt, idx):
         """(u, v), the shading normal and the sub-outcome (the triangle, where it decides a value) of the closest hits: a mesh's from
@@ -884,7 +1061,10 @@ class Scene:
             sig = (sig * 2 + occluded) * 4 + np.where(hit, side, 0)
             sig = sig * 2 + np.where(hit, zone == 0, 0)
             tr = 1.0
-            if self.medium is not None:
+            if self.medium is not None and self.medium.marches:
+                # VisibilityTester::Transmittance has no Sample: Tau at 4 x stepsize from a draw (emission.cpp:54-57, single.cpp:49-52)
+                tr, tau_s, dd_s = self.medium.interval(so, sd, lo, hi, 4 * self.medium.step)
+            elif self.medium is not None:
                 tr = self.medium.transmittance(so, sd, lo, hi)
             for m_no, (_, mat) in enumerate(surfaces):
                 sel = hit & (idx == m_no) & ~occluded
@@ -932,9 +1112,46 @@ class Scene:
                         L = np.where(ok[..., None], L + w * l2, L)
                         sig = np.where(ok, sig * 1000003 + s2 + 1, sig)
                     sig = sig * 2 + (sel & (sint2 >= 1))
+        self.D = np.zeros(o.shape)
+        if self.medium is not None and self.medium.marches:
+            # Scene::Li (core/scene.cpp:120-126): T Lo + Lv, alpha the surface integrator's alone: a camera ray that hits nothing carries Lv at alpha 0
+            self.march_conditions(depth)
+            end = np.where(hit, t, maxt)
+            tc, tau_c, dd_c = self.medium.interval(o, d, mint, end, self.medium.step)
+            S = np.where(hit[..., None], L * tc, 0.0)
+            # the intervals T in [exp(-(tau + d)), exp(-max(tau - d, 0))] of the camera and the shadow segment, through the product
+            up, low = np.exp(np.minimum(dd_c, tau_c) + np.minimum(dd_s, tau_s)), np.exp(-(dd_c + dd_s))
+            self.D = S * np.maximum(up - 1, 1 - low)
+            if self.sig_only:
+                return S, hit.astype(np.float64), sig
+            Lv, Dv, trlow = self.medium.lv(o, d, mint, end, self.lights[0])
+            # no roulette draw: the march's lowest possible Tr.y() stays at or above 0.01 wherever the march adds anything (emission.cpp:84-88)
+            y = trlow @ np.array([0.212671, 0.715160, 0.072169])
+            assert (y[(Lv > 0).any(-1)] >= 0.01).all(), "a march of this scene could reach the Russian roulette"
+            self.D = self.D + Dv
+            return S + Lv, hit.astype(np.float64), sig
         if self.medium is not None:
             L = L * self.medium.transmittance(o, d, mint, np.where(hit, t, maxt))
         return np.where(hit[..., None], L, 0.0), hit.astype(np.float64), sig
+
+    def march_conditions(self, depth):
+        """What keeps every draw but the offsets out of a march (conditions on the float64 scene, not measurements): Scene::Li is not entered from a
+        recursion; one delta light (lightNum is 0, pdf is 1, u1 and u2 unused) that lies outside the region (1 / d^2 stays bounded along every ray);
+        every surface in y <= 0, the region and the light in y >= 0, so that no shadow segment from a point of the region is occluded."""
+        m = self.medium
+        assert depth == 0 and self.maxdepth == 0 and len(self.lights) == 1 and self.lights[0].kind in ("point", "spot")
+        q = xpoint(m.w2v, self.lights[0].pos)
+        assert not ((q >= m.p0) & (q <= m.p1)).all(), "the light lies inside the region"
+        corners = np.array([[x, y, z] for x in (m.p0[0], m.p1[0]) for y in (m.p0[1], m.p1[1]) for z in (m.p0[2], m.p1[2])])
+        assert xpoint(np.linalg.inv(m.w2v), corners)[:, 1].min() >= 0 and self.lights[0].pos[1] > 0
+        assert all(isinstance(shp, Quad) and shp.p[:, 1].max() <= 0 for shp, _ in self.surfaces)
+
+    def allowance(self, ix, iy):
+        """-> L, D, alpha, signature: the radiance as samples() gives it and beside it the per-sample, per-channel allowance D >= 0, which
+        bounds what ANY choice of the draws that enter a march (the scatter offset, every Tau's offset) can move the renderer's value away from L;
+        derived from the float64 scene alone (Medium.interval, Medium.lv).  Zero for a scene without a marched medium."""
+        L, alpha, sig = self.samples(ix, iy)
+        return L, self.D, alpha, sig
 
     def samples(self, ix, iy):
         """radiance, alpha and signature of the camera samples at image positions (ix, iy)"""
@@ -957,6 +1174,7 @@ def band(scene, ix, iy):
     positions BAND_OFFSET pixels away.  At a 60 degree field of view over 64 pixels that is 3e-4 rad of the camera ray, a few hundred
     times the float32 rounding of a ray direction; no error of any renderer enters."""
     ix, iy = np.asarray(ix, np.float64), np.asarray(iy, np.float64)
+    scene.sig_only = True
     _, _, s0 = scene.samples(ix, iy)
     w0 = scene.trace["wraps"]
     out = np.zeros(ix.shape, bool)
@@ -967,6 +1185,7 @@ def band(scene, ix, iy):
                 out |= s != s0
                 for a, b in zip(scene.trace["wraps"], w0):       # across a mapping's seam the coordinate jumps by 1
                     out |= np.abs(a - b) > 0.5
+    scene.sig_only = False
     return out
 
 
@@ -987,9 +1206,16 @@ def ray_band(scene, o, d, mint, maxt, angle=3e-4):
     return out
 
 
-def sample_error(got, L, included):
-    """e = max_c |got - L| / (max_c |L| + 0.01 Lcase), Lcase the largest channel of L over the included samples"""
+def sample_scale(L, included):
+    """max_c |L| + 0.01 Lcase, Lcase the largest channel of L over the included samples"""
     lcase = float(np.abs(L[included]).max()) if included.any() else 0.0
-    num, den = np.abs(np.asarray(got, np.float64) - L).max(-1), np.abs(L).max(-1) + 0.01 * lcase
+    return np.abs(L).max(-1) + 0.01 * lcase
+
+
+def sample_error(got, L, included, D=None):
+    """e = max_c |got - L| / (max_c |L| + 0.01 Lcase), Lcase the largest channel of L over the included samples; with an allowance D
+    (Scene.allowance) the excess e' = max_c max(0, |got - L| - D) over the same scale"""
+    num, den = np.abs(np.asarray(got, np.float64) - L), sample_scale(L, included)
+    num = (num if D is None else np.maximum(0.0, num - D)).max(-1)
     with np.errstate(all="ignore"):
         return np.where(den > 0, num / den, np.where(num > 0, np.inf, 0.0))

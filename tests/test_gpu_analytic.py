@@ -11,7 +11,12 @@ fixture's film (tests/golden/analytic/, tests/test_analytic_host.py).  The films
 tests/test_gpu_parity.py, every pixel within 1e-5, on every case, quadrics included, outside the fixture's band.
 
 The "geometry" cases hold the debug integrator's records (u, v, |ng|, |ns|, the hit mask of each camera sample, alpha exactly 1) to the float64 meshes
-and quadrics, the "textures" cases a Whitted sample of a surface whose material is resolved from a Texture graph at the hit: same measure, band and bars."""
+and quadrics, the "textures" cases a Whitted sample of a surface whose material is resolved from a Texture graph at the hit: same measure, band and bars.
+
+The "march" cases (VolumeIntegrator "emission" / "single" through homogeneous, exponential and volumegrid regions: march_begin, march_steps, density_at,
+density_tau, the pipeline's march kernel) draw random offsets, so a record is held to the exact float64 integral within the allowance D that bounds what ANY
+offset can do: e' = max_c max(0, |got - L| - D) over the same scale, under 4 max(ref_err, the family's median, medium_homogeneous's ref_err).  Their films stay
+under the strict bar against the reference's films (rendered with the same keyed random numbers), and a camera ray that hits nothing carries Lv at alpha 0."""
 import os
 
 import numpy as np
@@ -26,7 +31,8 @@ pytestmark = pytest.mark.gpu
 
 NAMES = list(A.CASES)
 FLAVOUR_CASES = ["plastic_rough_.02", "quadric_hyperboloid", "medium_homogeneous",       # one lobe, one quadric, the medium,
-                 "geom_mesh_n_shading", "tex_mix_depth4"]                                 # one debug frame, one textured frame
+                 "geom_mesh_n_shading", "tex_mix_depth4",                                 # one debug frame, one textured frame,
+                 "march_single_forward", "dens_grid_single_thin"]                         # a march through a homogeneous and through a density region
 
 
 def load(name):
@@ -57,13 +63,22 @@ def check_samples(name, label, rec, bar):
     """the records of one render against the float64 form at each record's own image position"""
     sc = A.form(name)
     ix, iy = rec[:, 4].astype(np.float64), rec[:, 5].astype(np.float64)
-    L, hit, _ = sc.samples(ix, iy)
+    if A.CASES[name]["family"] == "march":   # D: the allowance of a "march" case (what any draw of its march can do), None elsewhere
+        L, D, hit, _ = sc.allowance(ix, iy)
+    else:
+        (L, hit, _), D = sc.samples(ix, iy), None
     band = F.band(sc, ix, iy)
     inc = ~band
-    e = F.sample_error(rec[:, 0:3], L, inc)
+    e = F.sample_error(rec[:, 0:3], L, inc, D)
     worst = int(np.argmax(np.where(inc, e, -1)))
     print("ANALYTIC-SAMPLES %s %s n %d band %.4f max_e %.3g bar %.3g at (%.2f, %.2f) got %s want %s" %
           (name, label, len(rec), band.mean(), e[inc].max(), bar, ix[worst], iy[worst], rec[worst, 0:3], L[worst]))
+    if D is not None:
+        # the allowance cannot hide a failure: it stays under 5 % of the sample's scale on 90 % of the samples at these positions too; sky samples carry Lv
+        tight, used, sky = A.tight_share(L, D, inc), A.tightness(rec[:, 0:3], L, D, inc), inc & (hit == 0)
+        print("ANALYTIC-ALLOWANCE %s %s tight share %.3f largest |got - L| / D %.3f sky samples %d with Lv %d" % (name, label, tight, used, int(sky.sum()), int((L[sky] > 0).any(-1).sum())))
+        assert tight >= A.MIN_TIGHT_SHARE, (name, label, tight)
+        assert np.array_equal((rec[sky, 0:3] > 0).any(-1), (L[sky] > 0).any(-1)), (name, label, "a camera ray that hits nothing does not carry the form's Lv")
     assert np.isfinite(rec[:, 0:4]).all(), name
     assert band.mean() <= A.BAND_CAP, (name, label, band.mean())
     assert np.array_equal(rec[inc, 3], hit[inc].astype(np.float32)), (name, label, "alpha is not exactly 1 on hits and 0 on misses")
