@@ -394,6 +394,41 @@ typedef struct RtHitGeometry {      /* device pointers, each may be NULL (field 
     int32_t *light;      /* [n] area-light index of the primitive, -1 if none or a miss   */
 } RtHitGeometry;
 int rt_hit_geometry_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uint32_t n, const RtHitGeometry *out);
+/* What an integrator asks of a hit: Intersection::GetBSDF (primitive.cpp:135-141 -> Shape::GetShadingGeometry + Material::GetBSDF), then BSDF::f,
+ * BSDF::Pdf, BSDF::Sample_f and BSDF::NumComponents (core/reflection.cpp, core/reflection.h:382-388), and Intersection::Le (primitive.cpp:142-145).
+ * One query per (ray, hit) pair; computed with the render kernels' code (rt_shade.h, rt_texture.h), so a lobe is one call.
+ *  - Outgoing direction.  wo = -d of ray i, as every integrator forms it (whitted.cpp:69, directlighting.cpp:100, path.cpp:98).  d must be of unit
+ *    length; the library does not renormalise.  dev_hits are the records rt_trace_closest_device wrote for dev_rays.
+ *  - The BSDF is the one Intersection::GetBSDF builds at that hit, unchanged: the shading frame of the render kernels (per-vertex N / S,
+ *    ReverseOrientation, handedness-swapping transforms, the quadrics' dpdu; BSDF ctor reflection.cpp:471-479), the geometric normal that decides
+ *    between BRDFs and BTDFs (:483-488), the scene's material -- resolved from its textures at the hit where it has textured parameters -- and the
+ *    lobes in the order the seven materials add them (matte.cpp, plastic.cpp, uber.cpp:62-87, shinymetal.cpp:60-61, translucent.cpp:59-78,
+ *    mirror.cpp:51-53, glass.cpp:56-61).
+ *  - A miss, or a record whose prim is no primitive of the scene, gives zeros in every float output, 0 in n_components and 0 in s_type.
+ *  - A sample with pdf == 0 gives s_wi = s_f = 0, s_pdf = 0 and s_type = 0, as the reference returns (reflection.cpp:407-411, :428-431).
+ *  - Asynchronous on the scene's stream; no copy from the device and no wait.  The only workspace is for scenes with textured materials: one resolved
+ *    record per resident thread, the pool the frames use -- its size does not depend on n, and as for rt_radiance_device it grows (waiting for the
+ *    stream once) only when no frame or query before has made it.  A kernel lane beyond the resident threads takes its next query a grid further.
+ *  - It is not a frame and it traces nothing: the film, the sample buffer, the counters and the record of the last launch are untouched, and a later
+ *    rt_render gives the film it gave before.
+ *  - Refused before any launch with RT_EINVAL (rt_last_error says which): a null scene; with n > 0 a null ray, hit or query pointer, a query with no
+ *    output, f or pdf wanted without wi, an s_* output wanted without u, ray or hit pointers that are not 16-byte aligned; n above 2^30.  n == 0 is
+ *    RT_OK and launches nothing. */
+/* BxDFType bits, core/reflection.h:52-68 */
+enum { RT_BSDF_REFLECTION = 1, RT_BSDF_TRANSMISSION = 2, RT_BSDF_DIFFUSE = 4, RT_BSDF_GLOSSY = 8, RT_BSDF_SPECULAR = 16, RT_BSDF_ALL = 31 };
+typedef struct RtBsdfQuery {   /* device pointers; any output may be NULL (not wanted) */
+    const float *wi;           /* in  [n][3] world directions, for f / pdf; may be NULL if neither is wanted   */
+    const float *u;            /* in  [n][3] u1, u2, u3 of BSDF::Sample_f; may be NULL if no s_* is wanted      */
+    const int32_t *flags;      /* in  [n] BxDFType mask per query, or NULL: RT_BSDF_ALL for all                 */
+    float   *f;                /* out [n][3] BSDF::f(wo, wi, flags)          reflection.cpp:480-494             */
+    float   *pdf;              /* out [n]    BSDF::Pdf(wo, wi, flags)        :458-470                           */
+    float   *s_wi, *s_f;       /* out [n][3] BSDF::Sample_f(wo, &wi, u1, u2, u3, &pdf, flags, &type) :402-457   */
+    float   *s_pdf;            /* out [n]                                                                       */
+    int32_t *s_type;           /* out [n]    sampledType, 0 when pdf == 0                                       */
+    int32_t *n_components;     /* out [n]    BSDF::NumComponents(flags)      reflection.h:382-388               */
+    float   *le;               /* out [n][3] Intersection::Le(wo) (primitive.cpp:142-145, area.h: Lemit if Dot(dg.nn, wo) > 0) */
+} RtBsdfQuery;
+int rt_bsdf_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uint32_t n, const RtBsdfQuery *q);
 /* Camera::GenerateRay (core/camera.h:33-34; perspective.cpp:51-82, orthographic.cpp:48-79, environment.cpp:47-61) as rt_camera_rays, into
  * dev_rays[count]: the rays of camera samples first .. first + count - 1, bit for bit those of rt_camera_rays */
 int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays);

@@ -34,7 +34,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse",
 
 
 HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_mega_fsd.hip", "rt_mega_fsp.hip", "rt_mega_rw.hip", "rt_mega_rd.hip", "rt_mega_rp.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
-             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
+             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_bsdf.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
 def _include_closure(path, seen=None):
@@ -270,6 +270,18 @@ class RtHitGeometry(C.Structure):                  # include/pbrt_hip.h: six dev
 HIT_FIELDS = ("p", "ng", "ns", "uv", "material", "light")      # DeviceScene.intersect(fields=...): name -> (columns, integer?)
 _HIT_FIELD_SHAPE = {"p": (3, False), "ng": (3, False), "ns": (3, False), "uv": (2, False), "material": (0, True), "light": (0, True)}
 
+# BxDFType bits (core/reflection.h; include/pbrt_hip.h RT_BSDF_*): the `flags` of DeviceScene.bsdf and what its `s_type` holds
+BSDF_REFLECTION, BSDF_TRANSMISSION, BSDF_DIFFUSE, BSDF_GLOSSY, BSDF_SPECULAR, BSDF_ALL = 1, 2, 4, 8, 16, 31
+
+
+class RtBsdfQuery(C.Structure):                    # include/pbrt_hip.h: device pointers, three inputs and eight outputs, NULL = not given / not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("wi", "u", "flags", "f", "pdf", "s_wi", "s_f", "s_pdf", "s_type", "n_components", "le")]
+
+
+BSDF_FIELDS = ("f", "pdf", "s_wi", "s_f", "s_pdf", "s_type", "n_components", "le")      # DeviceScene.bsdf(fields=...): name -> (columns, integer?)
+_BSDF_FIELD_SHAPE = {"f": (3, False), "pdf": (0, False), "s_wi": (3, False), "s_f": (3, False), "s_pdf": (0, False), "s_type": (0, True),
+                     "n_components": (0, True), "le": (3, False)}
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -318,7 +330,7 @@ def hip_lib():
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
                      "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
                      "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device",
-                     "rt_sample_positions_device", "rt_film_add_device"):
+                     "rt_sample_positions_device", "rt_film_add_device", "rt_bsdf_device"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -335,6 +347,7 @@ def hip_lib():
         L.rt_trace_closest_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_trace_any_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
+        L.rt_bsdf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtBsdfQuery)]
         L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_sample_positions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
@@ -1087,6 +1100,67 @@ class DeviceScene:
                 cur.wait_stream(mine)
         out = {"prim": hits.view(torch.int32)[:, 0], "t": hits[:, 1], "b1": hits[:, 2], "b2": hits[:, 3]}
         out.update(extra)
+        return out
+
+    @staticmethod
+    def _check_query_tensor(torch, t, name, n, cols, dtype, like):
+        """an input of bsdf() beside the rays: the checks of _check_ray_tensor for a [n, cols] (cols = 0: [n]) tensor of `dtype` on the rays' device"""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: a torch tensor is needed, got %s" % (name, type(t).__name__))
+        if t.dtype != dtype:
+            raise ValueError("%s: dtype %s is needed, got %s" % (name, dtype, t.dtype))
+        shape = (n, cols) if cols else (n,)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: shape %s is needed, got %s" % (name, list(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor is needed" % name)
+        if t.device != like.device:
+            raise ValueError("%s: the tensor is on %s, the rays on %s" % (name, t.device, like.device))
+
+    def bsdf(self, rays, hits, wi=None, u=None, flags=None, fields=BSDF_FIELDS) -> dict:
+        """What an integrator asks of a hit (rt_bsdf_device): Intersection::GetBSDF, then BSDF::f / Pdf / Sample_f / NumComponents, and Intersection::Le,
+        with wo = -d of each ray (directions of unit length).  rays: the [n, 8] tensor given to intersect(); hits: the dict intersect() returned for
+        it (or its [n, 4] record tensor).  wi: float32 [n, 3] world directions (needed for `f`, `pdf`); u: float32 [n, 3] = u1, u2, u3 of Sample_f
+        (needed for the `s_*` fields); flags: int32 [n] BSDF_* masks, None = BSDF_ALL for all.  Returns per requested field a torch tensor on the
+        scene's device: `f`, `s_wi`, `s_f`, `le` float32 [n, 3], `pdf`, `s_pdf` float32 [n], `s_type`, `n_components` int32 [n].  A miss gives zeros;
+        a failed sample (s_pdf == 0) gives s_wi = s_f = 0 and s_type = 0.  Nothing of a frame is touched."""
+        import torch
+        fields = tuple(fields)
+        for f in fields:
+            if f not in _BSDF_FIELD_SHAPE:
+                raise ValueError("fields: unknown field %r (known: %s)" % (f, ", ".join(BSDF_FIELDS)))
+        if not fields:
+            raise ValueError("fields: at least one of %s is needed" % ", ".join(BSDF_FIELDS))
+        self._check_ray_tensor(torch, rays, getattr(self, "_device", None))
+        n, dev = int(rays.shape[0]), rays.device
+        rec = hits
+        if isinstance(hits, dict):                     # intersect()'s prim / t / b1 / b2 are views of one [n, 4] record array: column 0 starts it
+            rec = hits["prim"]
+            if n and (rec.stride(0) != 4 or hits["t"].data_ptr() != rec.data_ptr() + 4):
+                raise ValueError("hits: the dict intersect() returned is needed (prim, t, b1, b2 as views of one [n, 4] record array)")
+            rec = torch.as_strided(rec.view(torch.float32), (n, 4), (4, 1)) if n else torch.empty((0, 4), dtype=torch.float32, device=dev)
+        self._check_query_tensor(torch, rec, "hits", n, 4, torch.float32, rays)
+        if wi is None and ("f" in fields or "pdf" in fields):
+            raise ValueError("wi: needed for the fields f and pdf")
+        if u is None and any(f.startswith("s_") for f in fields):
+            raise ValueError("u: needed for the fields s_wi, s_f, s_pdf and s_type")
+        if wi is not None:
+            self._check_query_tensor(torch, wi, "wi", n, 3, torch.float32, rays)
+        if u is not None:
+            self._check_query_tensor(torch, u, "u", n, 3, torch.float32, rays)
+        if flags is not None:
+            self._check_query_tensor(torch, flags, "flags", n, 0, torch.int32, rays)
+        out = {f: (torch.empty(n, dtype=torch.int32 if _BSDF_FIELD_SHAPE[f][1] else torch.float32, device=dev) if not _BSDF_FIELD_SHAPE[f][0]
+                   else torch.empty((n, _BSDF_FIELD_SHAPE[f][0]), dtype=torch.float32, device=dev)) for f in fields}
+        if n:
+            q = RtBsdfQuery(wi=wi.data_ptr() if wi is not None else None, u=u.data_ptr() if u is not None else None,
+                            flags=flags.data_ptr() if flags is not None else None, **{f: t.data_ptr() for f, t in out.items()})
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_bsdf_device(self._s, C.c_void_p(rays.data_ptr()), C.c_void_p(rec.data_ptr()), n, C.byref(q)))
+            if mine is not None:
+                cur.wait_stream(mine)
         return out
 
     def occluded(self, rays):

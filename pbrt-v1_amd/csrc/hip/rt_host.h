@@ -2,7 +2,7 @@
 // the owners of its device memory, events and stream, the kernel tables with their resident grids (rt_flavour.h; persistent_kernel is the one place that
 // turns a planned launch, rt_frame_plan.h plan::Launch, into a kernel and a grid), the record of the last timed launch (LastLaunch) and the refusals the device-pointer entry points share.  rt_scene.hip builds scenes (layouts, uploads, the accelerator ABI), rt_film.hip owns the film kernels and the rt_film_* ABI,
 // rt_kernels.hip renders (make_frame binds what rt_frame_plan.h plans, launch_persistent launches what plan_launch chose, the queue pipeline, rt_render, rt_trace_*), rt_rays.hip traces caller-supplied rays in device
-// memory (rt_trace_*_device, rt_hit_geometry_device), rt_film_add.hip adds caller-supplied radiances in device memory to the film (the kernels of rt_film_add_device /
+// memory (rt_trace_*_device, rt_hit_geometry_device), rt_bsdf.hip answers an integrator's questions of such hits (rt_bsdf_device), rt_film_add.hip adds caller-supplied radiances in device memory to the film (the kernels of rt_film_add_device /
 // rt_sample_positions_device).  Round 6: split out of a 2 300-line rt_kernels.hip.
 #pragma once
 #include "rt_flavour.h"
@@ -222,6 +222,9 @@ struct RtScene {
     // rt_film_add_device (rt_kernels.hip): the image positions of the call's samples, two floats each -- the call's own staging, sized by the largest
     // range added so far; the sample buffer above stays the last frame's
     DevBuf<float> add_xy;
+    // rt_bsdf_device (rt_bsdf.hip): the descriptor resolve_hit_material reads -- where the resolved-material records lie (mat_pool_base as of
+    // bsdf_pool_base) and how many lanes own one; the records themselves are level 0 of the frames' pool, one per resident thread
+    DevBuf<DevFrame> bsdf_frame; unsigned bsdf_pool_base = 0;
 };
 #define RT_PIPE_QN 4096          // ring of per-iteration queue counters
 #define RT_PIPE_TIMED 256        // iterations whose trace launch is bracketed by events

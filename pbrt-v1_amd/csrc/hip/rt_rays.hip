@@ -7,14 +7,12 @@
 //                        rt_ray_guard.h applied, and the queue counters of the launch (the host path, rt_kernels.hip trace_common, uploads both from the host).
 //   (rt_pipeline.h)      pipe_trace_kernel itself, the entry flavour::Trace names: the caller's RtHit array is its hit plane.
 //   occlusion_kernel     the hit plane of an any-hit launch -> one byte per ray.
-//   hit_geometry_kernel  one lane per ray: the traversal's hit state rebuilt from (ray, RtHit), then make_vertex<true> / hit_point_uv -- the code the render
+//   hit_geometry_kernel  one lane per ray: the traversal's hit state rebuilt from (ray, RtHit) (rt_hit_state.h), then make_vertex<true> / hit_point_uv -- the code the render
 //                        kernels and the debug integrator run (rt_shade.h, rt_texture.h) -- for the fields the caller asked for.
-#include "rt_host.h"
+#include "rt_hit_state.h"
 #include "rt_ray_guard.h"
 
 namespace rt {
-
-#define RT_RAYS_BLOCK 256
 
 __global__ __launch_bounds__(RT_RAYS_BLOCK) void rays_layout_kernel(const float4 *__restrict__ rays, unsigned n, float4 *__restrict__ q_o, float4 *__restrict__ q_d,
                                                                     unsigned *__restrict__ qc, int any) {
@@ -43,13 +41,7 @@ __global__ __launch_bounds__(RT_RAYS_BLOCK) void hit_geometry_kernel(const DevSc
     const DevScene &sc = *scp;
     const unsigned i = blockIdx.x * RT_RAYS_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float4 a = RT_GPTR(const float4, rays)[size_t(2) * i], b = RT_GPTR(const float4, rays)[size_t(2) * i + 1];
-    const float4 h = RT_GPTR(const float4, hits)[i];
-    Trav tv;
-    tv.o = mk3(a.x, a.y, a.z); tv.d = mk3(a.w, b.x, b.y); tv.mint = b.z;
-    tv.hit_prim = __float_as_int(h.x); tv.maxt = h.y; tv.b1 = h.z; tv.b2 = h.w;     // primitive.cpp:120: the accepted hit shortened the ray to t
-    tv.any = false;
-    const bool hit = unsigned(tv.hit_prim) < sc.n_tris;                 // (a record that names no primitive of this scene counts as a miss)
+    RT_HIT_STATE(tv, hit, sc, rays, hits, i);                           // (rt_hit_state.h: a record that names no primitive of this scene counts as a miss)
     V3 p = mk3(0.f), ng = mk3(0.f), ns = mk3(0.f);
     float u = 0.f, v = 0.f;
     int mat = -1, light = -1;
@@ -76,21 +68,6 @@ __global__ __launch_bounds__(RT_RAYS_BLOCK) void hit_geometry_kernel(const DevSc
 }  // namespace rt
 
 // ------------------------------------------------------------------------------------------ host side
-#define RT_RAYS_MAX_N (1u << 30)
-static inline unsigned blocks_for(uint32_t n) { return (n + RT_RAYS_BLOCK - 1) / RT_RAYS_BLOCK; }
-
-// the refusals every call shares, before anything is launched (rt_host.h)
-static int check_rays(const std::string &fn, const RtScene *s, const void *dev_rays, uint32_t n) {
-    int rc;
-    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, dev_rays, "ray pointer")) || (rc = refuse_unaligned16(fn, dev_rays, "dev_rays"))) return rc;
-    return n > RT_RAYS_MAX_N ? fail(RT_EINVAL, fn + ": n = " + std::to_string(n) + " is above 2^30") : RT_OK;
-}
-// ... and a call's hit array
-static int check_hits(const std::string &fn, const void *dev_hits) {
-    if (int rc = refuse_null(fn, dev_hits, "hit pointer")) return rc;
-    return refuse_unaligned16(fn, dev_hits, "dev_hits");
-}
-
 // Lay the rays out, write the queue counters, run the trace kernel over them.  `hit_plane`: the caller's RtHit array or s->any_hits.
 static int trace_device(RtScene *s, const RtRay *dev_rays, uint32_t n, int any, float4 *hit_plane) {
     if (int rc = ensure(s, s->ray_planes, size_t(n) * 2)) return rc;

@@ -377,6 +377,30 @@ RT_DEV float bsdf_pdf(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
     return pdf / nc;
 }
 
+// BSDF::f(wo, wi, flags) reflection.cpp:480-494 for any BxDFType mask (rt_bsdf_device): the geometric normal takes the BTDFs or the BRDFs out of
+// `flags`, then the matching lobes in lobe order.  A specular lobe's f is black (SpecularReflection::f reflection.h:208-210, SpecularTransmission likewise).  With BX_ALL it is bsdf_f.
+template <bool EXT>
+RT_DEV V3 bsdf_f_flags(MatRef m, const Vertex &v, V3 woW, V3 wiW, int flags) {
+    const V3 wi = to_local(v, wiW), wo = to_local(v, woW);
+    if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) flags &= ~BX_TRANSMISSION;
+    else flags &= ~BX_REFLECTION;
+    return bsdf_f_lobes<EXT>(m, wo, wi, flags);
+}
+// BSDF::Pdf(wo, wi, flags) reflection.cpp:458-470 for any BxDFType mask: the matching lobes' pdfs in lobe order over the number of matching lobes.  A
+// specular lobe counts in the denominator and adds 0 (SpecularReflection::Pdf reflection.h:213-215).  With BX_ALL it is bsdf_pdf.
+template <bool EXT>
+RT_DEV float bsdf_pdf_flags(MatRef m, const Vertex &v, V3 woW, V3 wiW, int flags) {
+    const int nc = bsdf_num_components<EXT>(m, flags);
+    if (nc == 0) return 0.f;
+    const V3 wo = to_local(v, woW), wi = to_local(v, wiW);
+    float pdf = 0.f;
+    if (mat_has_diffuse<EXT>(m) && flags_match(BX_REFLECTION | BX_DIFFUSE, flags)) pdf += diffuse_pdf(wo, wi);
+    if (mat_has_diffuse_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_DIFFUSE, flags)) pdf += diffuse_t_pdf(wo, wi);
+    if (mat_has_glossy<EXT>(m) && flags_match(BX_REFLECTION | BX_GLOSSY, flags)) pdf += glossy_pdf(m, wo, wi);
+    if (mat_has_glossy_t<EXT>(m) && flags_match(BX_TRANSMISSION | BX_GLOSSY, flags)) pdf += glossy_t_pdf(m, wo, wi);
+    return pdf / nc;
+}
+
 // BSDF::Sample_f reflection.cpp:402-457.  Returns f; pdf == 0 means "no sample".
 template <bool EXT>
 RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, float u2, float u3,
