@@ -526,6 +526,23 @@ RT_DEV decltype(auto) light_of(const DevScene &sc, int i) {
     if constexpr (SX::one_light) return (RT_LIGHT_K(sc));
     else return (RT_LIGHT(sc, i));
 }
+// ... the fields of that record an area-light estimate asks for (estimate_direct_begin, estimate_direct_bsdf), read as VALUES at the head of the stage.
+// Through the reference above each field is a scalar load and a wait of its own where the stage first asks for it -- n_tris, first_tri,
+// reverse_orientation, area, color: round trips in series around the emitter's triangles; read together they wait once.
+// Switched off with -DRT_EMITTER_HOIST=0 (measurements: profiles/small_emitter_kernels.txt).
+#ifndef RT_EMITTER_HOIST
+#define RT_EMITTER_HOIST 1
+#endif
+struct LightHead { int type; float color[3]; unsigned first_tri, n_tris; int reverse_orientation; float area; int quadric; };
+template <class SX, class LT>
+RT_DEV decltype(auto) light_head(const LT &L) {
+    if constexpr (SX::one_light && RT_EMITTER_HOIST != 0) {
+        LightHead h;
+        h.type = L.type; h.color[0] = L.color[0]; h.color[1] = L.color[1]; h.color[2] = L.color[2];
+        h.first_tri = L.first_tri; h.n_tris = L.n_tris; h.reverse_orientation = L.reverse_orientation; h.area = L.area; h.quadric = L.quadric;
+        return h;
+    } else return (L);
+}
 // ... and request k (light sample, BSDF sample, BSDF component) of light li in DirectLighting "all"'s table (DevFrame::light_dims; li < n_lights)
 template <class SX>
 RT_DEV DimReq light_dim(const DevFrame &fr, int li, int k) {
@@ -534,12 +551,13 @@ RT_DEV DimReq light_dim(const DevFrame &fr, int li, int k) {
 }
 template <bool EXT, bool DEFER = false, bool GEOM_N = false, class SX = fixed::AnyScene, int ACCEL = -1>
 RT_DEV void estimate_direct_bsdf(const DevScene &sc, Lane &ln) {
-    const auto &Lt = light_of<SX>(sc, ln.cur_light);
+    const auto &Ld = light_of<SX>(sc, ln.cur_light);
+    const auto &Lt = light_head<SX>(Ld);                                        // (no delta light reads past this line)
     ln.stage = ST_ED_DONE;
     if (light_is_delta<EXT>(Lt)) return;                                        // IsDeltaLight()
     MatRef m = RT_MAT(sc, ln.v.mat);
     V3 wi; float bsdfPdf; int sampled;
-    V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, ln.bs1, ln.bs2, ln.bcs, bsdfPdf, BX_ALL & ~BX_SPECULAR, sampled);
+    V3 f = bsdf_sample_f<EXT, SX::no_specular>(m, ln.v, ln.v.wo, wi, ln.bs1, ln.bs2, ln.bcs, bsdfPdf, BX_ALL & ~BX_SPECULAR, sampled);
     if (!is_black(f) && bsdfPdf > 0.f) {
         float lightPdf;
         if constexpr (EXT) lightPdf = light_is_infinite<EXT>(Lt) ? infinite_pdf_cosine(GEOM_N ? ln.v.ng : ln.v.nn, wi) : area_light_pdf<EXT, SX::one_light>(sc, Lt, ln.v.p, wi);
@@ -570,11 +588,12 @@ template <bool EXT, bool DEFER = false, bool GEOM_N = false, class SX = fixed::A
 RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float ls1, float ls2) {
     ln.cur_light = light;
     ln.Ld = mk3(0.f);
-    const auto &Lt = light_of<SX>(sc, light);
+    const auto &Ld = light_of<SX>(sc, light);
+    const auto &Lt = light_head<SX>(Ld);                                        // (Ld: the whole record, for a delta light)
     MatRef m = RT_MAT(sc, ln.v.mat);
     V3 wi, Li, sd; float lightPdf, smax;
     if (light_is_delta<EXT>(Lt)) {                                              // point.cpp:61-66, spot.cpp:80-84, distant.cpp:63-67
-        Li = delta_light_sample(Lt, ln.v.p, wi, sd, smax);
+        Li = delta_light_sample(Ld, ln.v.p, wi, sd, smax);
         lightPdf = 1.f;
     } else if constexpr (EXT) {                                                 // (discarded in the other kernels: their code is what it was)
         if (light_is_infinite<EXT>(Lt)) {                                       // infinite.cpp:96-116, n = bsdf->dgShading.nn; SetRay(p, wi)
@@ -589,6 +608,20 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
             Li = area_L(Lt, ns, -wi);
             sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
         }
+    } else if constexpr (SX::one_light && RT_SMALL_EMITTER != 0) {              // area.cpp:58-68, the one light of a scene twin
+        V3 ns, ps;
+        if (emitter_is_small(Lt)) {                                             // (wave-uniform) the sample and its pdf share one read of the emitter's records
+            const EmitterPair e = emitter_pair(sc, Lt);
+            ps = area_sample_point_small(e, Lt, ls1, ls2, ln.rng, ns);
+            wi = normalize3(ps - ln.v.p);
+            lightPdf = area_light_pdf_small(e, Lt, ln.v.p, wi);
+        } else {                                                                // (the loops alone: the question has been asked)
+            ps = area_sample_point<EXT, true, false>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
+            wi = normalize3(ps - ln.v.p);
+            lightPdf = area_light_pdf<EXT, true, false>(sc, Lt, ln.v.p, wi);
+        }
+        Li = area_L(Lt, ns, -wi);
+        sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
     } else {                                                                    // area.cpp:58-68
         V3 ns;
         V3 ps = area_sample_point<EXT, SX::one_light>(sc, Lt, ln.v.p, ls1, ls2, ln.rng, ns);
@@ -598,11 +631,11 @@ RT_DEV void estimate_direct_begin(const DevScene &sc, Lane &ln, int light, float
         sd = ps - ln.v.p; smax = 1.f - RT_RAY_EPSILON;
     }
     if (lightPdf > 0.f && !is_black(Li)) {
-        V3 f = bsdf_f<EXT>(m, ln.v, ln.v.wo, wi);
+        V3 f = bsdf_f<EXT, SX::no_specular>(m, ln.v, ln.v.wo, wi);
         if (!is_black(f)) {
             if (light_is_delta<EXT>(Lt)) ln.pend = div_s((f * Li) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn), lightPdf);
             else {
-                float bsdfPdf = bsdf_pdf<EXT>(m, ln.v, ln.v.wo, wi);
+                float bsdfPdf = bsdf_pdf<EXT, SX::no_specular>(m, ln.v, ln.v.wo, wi);
                 float fw = 1 * lightPdf, gw = 1 * bsdfPdf;
                 float weight = (fw * fw) / (fw * fw + gw * gw);
                 ln.pend = div_s(((f * Li) * absdot3(wi, GEOM_N ? ln.v.ng : ln.v.nn)) * weight, lightPdf);
@@ -1029,7 +1062,7 @@ RT_DEV void stage_body(const DevScene &sc, const DevFrame &fr, Lane &ln, unsigne
             bcs = dim_value<FX>(fr, ln, fr.one_d[3 * k + 2], 0, 0);
         } else { bs1 = ln.rng.next_float(); bs2 = ln.rng.next_float(); bcs = ln.rng.next_float(); }
         V3 wi; float pdf; int flags;
-        V3 f = bsdf_sample_f<EXT>(m, ln.v, ln.v.wo, wi, bs1, bs2, bcs, pdf, BX_ALL, flags);
+        V3 f = bsdf_sample_f<EXT, SX::no_specular>(m, ln.v, ln.v.wo, wi, bs1, bs2, bcs, pdf, BX_ALL, flags);
         if (is_black(f) || pdf == 0.f) { ln.stage = ST_RETURN; return; }
         ln.specular = !SX::no_specular && (flags & BX_SPECULAR) != 0;
         ln.thr = ln.thr * div_s(f * absdot3(wi, ln.v.nn), pdf);

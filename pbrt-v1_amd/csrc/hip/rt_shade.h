@@ -352,9 +352,21 @@ RT_DEV V3 bsdf_f_lobes(MatRef m, V3 wo, V3 wi, int flags) {
 }
 template <bool EXT> RT_DEV bool mat_has_btdf(MatRef m) { return mat_has_diffuse_t<EXT>(m) || mat_has_glossy_t<EXT>(m); }
 
+// MATTE (here, in bsdf_pdf and in bsdf_sample_f): every material of the scene is matte (fixed::Scene::no_specular, rt_fixed_frame.h), so the BSDF at
+// hand has exactly the diffuse lobe -- Lambertian or Oren-Nayar by m.on_b -- and nothing asks m.type or walks the lobe list; the expressions that reach
+// a result are the ones the general form runs for a matte material, in its order.  Switched off with -DRT_MATTE_LOBES=0
+// (measurements: profiles/small_emitter_kernels.txt).
+#ifndef RT_MATTE_LOBES
+#define RT_MATTE_LOBES 1
+#endif
 // BSDF::f reflection.cpp:480-494 (flags = BSDF_ALL): only the non-specular lobes have a non-zero f
-template <bool EXT>
+template <bool EXT, bool MATTE = false>
 RT_DEV V3 bsdf_f(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
+    if constexpr (MATTE && !EXT && RT_MATTE_LOBES != 0) {
+        V3 wi = to_local(v, wiW), wo = to_local(v, woW);
+        if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) return mk3(0.f) + diffuse_f(m, wo, wi);
+        return mk3(0.f);
+    }
     if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m) && !mat_has_btdf<EXT>(m)) return mk3(0.f);
     V3 wi = to_local(v, wiW), wo = to_local(v, woW);
     if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) return bsdf_f_lobes<EXT>(m, wo, wi, BX_ALL & ~BX_TRANSMISSION);   // BRDFs only
@@ -363,8 +375,14 @@ RT_DEV V3 bsdf_f(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
 }
 
 // BSDF::Pdf reflection.cpp:458-470 (flags = BSDF_ALL)
-template <bool EXT>
+template <bool EXT, bool MATTE = false>
 RT_DEV float bsdf_pdf(MatRef m, const Vertex &v, V3 woW, V3 wiW) {
+    if constexpr (MATTE && !EXT && RT_MATTE_LOBES != 0) {                        // one component
+        V3 wo = to_local(v, woW), wi = to_local(v, wiW);
+        float pdf = 0.f;
+        pdf += diffuse_pdf(wo, wi);
+        return pdf / 1;
+    }
     int nc = bsdf_total_components<EXT>(m);
     if (nc == 0) return 0.f;
     if (!mat_has_diffuse<EXT>(m) && !mat_has_glossy<EXT>(m) && !mat_has_btdf<EXT>(m)) return 0.f / float(nc);
@@ -402,10 +420,25 @@ RT_DEV float bsdf_pdf_flags(MatRef m, const Vertex &v, V3 woW, V3 wiW, int flags
 }
 
 // BSDF::Sample_f reflection.cpp:402-457.  Returns f; pdf == 0 means "no sample".
-template <bool EXT>
+template <bool EXT, bool MATTE = false>
 RT_DEV V3 bsdf_sample_f(MatRef m, const Vertex &v, V3 woW, V3 &wiW, float u1, float u2, float u3,
                         float &pdf, int flags, int &sampled) {
     sampled = 0; pdf = 0.f;
+    if constexpr (MATTE && !EXT && RT_MATTE_LOBES != 0) {
+        // one lobe matches or none does: `which` is 0 whatever u3 is, and nothing else reads u3
+        if (!flags_match(BX_REFLECTION | BX_DIFFUSE, flags)) return mk3(0.f);
+        V3 wo = to_local(v, woW);
+        float dx, dy; concentric_disk(u1, u2, dx, dy);                  // BxDF::Sample_f reflection.cpp:219-226 with CosineSampleHemisphere mc.h:38-44
+        V3 wi = mk3(dx, dy, sqrtf(fmaxf(0.f, 1.f - dx * dx - dy * dy)));
+        if (wo.z < 0.f) wi.z *= -1.f;
+        pdf = diffuse_pdf(wo, wi);
+        if (pdf == 0.f) return mk3(0.f);
+        sampled = BX_REFLECTION | BX_DIFFUSE;
+        wiW = to_world(v, wi);
+        V3 f = mk3(0.f);
+        if (dot3(wiW, vertex_ng<EXT>(v)) * dot3(woW, vertex_ng<EXT>(v)) > 0) f = mk3(0.f) + diffuse_f(m, wo, wi);
+        return f;
+    }
     int matching = bsdf_num_components<EXT>(m, flags);
     if (matching == 0) return mk3(0.f);
     int which = min(int(floorf(u3 * matching)), matching - 1);     // Floor2Int(double(u3*matching))
@@ -523,6 +556,32 @@ RT_DEV void light_tri(const DevScene &sc, unsigned k, V3 &p1, V3 &p2, V3 &p3) {
     const float RT_G *t = RT_GPTR(const float, sc.light_tris) + size_t(k) * 16;
     p1 = mk3(t[0], t[1], t[2]); p2 = mk3(t[3], t[4], t[5]); p3 = mk3(t[6], t[7], t[8]);
     }
+}
+
+// The emitter of one or two triangles (the ceiling quad of the large frames), in the K forms below: both records of DevScene::light_tris -- 16 floats
+// each: p1, p2, p3 in words 0..8, the cdf of ShapeSet::Sample in word 10, the normal in 12..14 -- are read as VALUES into scalar registers, together
+// and with one wait, before anything chooses between them; with one triangle the second record is the first again.  A choice between two loaded
+// values is a per-lane select; a choice between the two records' words would be a vector load from a selected address again.
+// Switched off with -DRT_SMALL_EMITTER=0 (measurements: profiles/small_emitter_kernels.txt).
+#ifndef RT_SMALL_EMITTER
+#define RT_SMALL_EMITTER 1
+#endif
+struct EmitterTri { V3 p1, p2, p3, n; float cdf; };
+struct EmitterPair { EmitterTri t0, t1; };
+RT_DEV EmitterTri emitter_tri(const DevScene &sc, unsigned k) {
+    const float RT_K *t = RT_KPTR(const float, sc.light_tris) + size_t(k) * 16;
+    EmitterTri e;
+    e.p1 = mk3(t[0], t[1], t[2]); e.p2 = mk3(t[3], t[4], t[5]); e.p3 = mk3(t[6], t[7], t[8]);
+    e.cdf = t[10];
+    e.n = mk3(t[12], t[13], t[14]);
+    return e;
+}
+template <class LT> RT_DEV bool emitter_is_small(const LT &L) { return L.n_tris - 1u <= 1u; }     // one or two triangles: a scalar compare, the record is in scalar registers
+template <class LT> RT_DEV EmitterPair emitter_pair(const DevScene &sc, const LT &L) {
+    EmitterPair e;
+    e.t0 = emitter_tri(sc, L.first_tri);
+    e.t1 = emitter_tri(sc, L.first_tri + (L.n_tris - 1u));
+    return e;
 }
 
 // ---- delta lights: {Point,Spot,Distant}Light::Sample_L(p, &wi, &visibility) (point.cpp:55-60, spot.cpp:61-79,
@@ -672,11 +731,33 @@ RT_DEV float quadric_light_pdf(const DevScene &sc, unsigned qi, V3 p, V3 wi) {  
     return pdf;
 }
 
+// Shape::Pdf of an emitter of one or two triangles whose records are at hand (emitter_pair): the loop of area_light_pdf unrolled, k = 0 then k = 1, the last hit wins
+template <class LT>
+RT_DEV float area_light_pdf_small(const EmitterPair &e, const LT &L, V3 p, V3 wi) {
+    bool any = false; float thit = 0.f; V3 nl = mk3(0.f);
+    float t, b1, b2;
+    if (tri_test(e.t0.p1, e.t0.p2 - e.t0.p1, e.t0.p3 - e.t0.p1, p, wi, RT_RAY_EPSILON, RT_INF, t, b1, b2)) { any = true; thit = t; nl = e.t0.n; }
+    if (L.n_tris > 1u) {
+        if (tri_test(e.t1.p1, e.t1.p2 - e.t1.p1, e.t1.p3 - e.t1.p1, p, wi, RT_RAY_EPSILON, RT_INF, t, b1, b2)) { any = true; thit = t; nl = e.t1.n; }
+    }
+    // the tail of area_light_pdf below
+    if (!any) return 0.f;
+    V3 ph = p + wi * thit;
+    V3 dd = p - ph;
+    float ad = absdot3(nl, -wi);
+    float pdf = (dd.x * dd.x + dd.y * dd.y + dd.z * dd.z) / (ad * L.area);
+    if (ad == 0.f) pdf = 0.f;
+    return pdf;
+}
 // Shape::Pdf(p, wi) shape.h:96-107 evaluated on the emitter's own triangles:
 // ShapeSet::Intersect (shape.h:150-156) keeps the LAST triangle hit, the ray's maxt is never shortened.
-template <bool EXT, bool K = false, class LT>
+// SMALL = false: the caller has asked emitter_is_small itself and this is its other branch
+template <bool EXT, bool K = false, bool SMALL = true, class LT>
 RT_DEV float area_light_pdf(const DevScene &sc, const LT &L, V3 p, V3 wi) {
     if (EXT && L.quadric >= 0) return quadric_light_pdf(sc, unsigned(L.quadric), p, wi);
+    if constexpr (K && SMALL && RT_SMALL_EMITTER != 0) {
+        if (emitter_is_small(L)) return area_light_pdf_small(emitter_pair(sc, L), L, p, wi);
+    }
     bool any = false; float thit = 0.f; V3 nl = mk3(0.f);
     for (unsigned k = 0; k < L.n_tris; ++k) {
         V3 p1, p2, p3; light_tri<K>(sc, L.first_tri + k, p1, p2, p3);
@@ -704,11 +785,31 @@ RT_DEV float area_light_pdf(const DevScene &sc, const LT &L, V3 p, V3 wi) {
 // AreaLight::L light.h:93-96
 template <class LT> RT_DEV V3 area_L(const LT &L, V3 n, V3 w) { return dot3(n, w) > 0 ? mat_color(L.color) : mk3(0.f); }
 
+// ShapeSet::Sample of an emitter of one or two triangles whose records are at hand: the draw iff there are two, the pick by `ls < cdf0` a per-lane select of values
+template <class LT, class RNG>
+RT_DEV V3 area_sample_point_small(const EmitterPair &e, const LT &L, float u1, float u2, RNG &rng, V3 &ns) {
+    float ls = 0.f;
+    if (L.n_tris > 1u) ls = rng.next_float();
+    const bool first = !(L.n_tris > 1u) || ls < e.t0.cdf;                        // (the cdf is compared after the draw's branch, so its load waits with the records')
+    const V3 p1 = mk3(first ? e.t0.p1.x : e.t1.p1.x, first ? e.t0.p1.y : e.t1.p1.y, first ? e.t0.p1.z : e.t1.p1.z);
+    const V3 p2 = mk3(first ? e.t0.p2.x : e.t1.p2.x, first ? e.t0.p2.y : e.t1.p2.y, first ? e.t0.p2.z : e.t1.p2.z);
+    const V3 p3 = mk3(first ? e.t0.p3.x : e.t1.p3.x, first ? e.t0.p3.y : e.t1.p3.y, first ? e.t0.p3.z : e.t1.p3.z);
+    // Triangle::Sample + UniformSampleTriangle on the triangle picked, as area_sample_point below
+    float su1 = sqrtf(u1);
+    float b1 = 1.f - su1, b2 = u2 * su1;
+    V3 ps = b1 * p1 + b2 * p2 + (1.f - b1 - b2) * p3;
+    ns = normalize3(cross3(p2 - p1, p3 - p1));
+    if (L.reverse_orientation) ns = ns * -1.f;
+    return ps;
+}
 // shape->Sample(p,u1,u2,&ns): ShapeSet::Sample shape.h:115-121 (one extra RandomFloat when the emitter has
 // more than one triangle) + Triangle::Sample trianglemesh.cpp:336-349 + UniformSampleTriangle mc.cpp:136-141
-template <bool EXT, bool K = false, class LT, class RNG>
+template <bool EXT, bool K = false, bool SMALL = true, class LT, class RNG>
 RT_DEV V3 area_sample_point(const DevScene &sc, const LT &L, V3 pref, float u1, float u2, RNG &rng, V3 &ns) {
     if (EXT && L.quadric >= 0) return quadric_sample(sc, unsigned(L.quadric), L.reverse_orientation != 0, pref, u1, u2, ns);
+    if constexpr (K && SMALL && RT_SMALL_EMITTER != 0) {
+        if (emitter_is_small(L)) return area_sample_point_small(emitter_pair(sc, L), L, u1, u2, rng, ns);
+    }
     unsigned k = 0;
     if (L.n_tris > 1) {
         float ls = rng.next_float();
