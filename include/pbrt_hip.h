@@ -429,6 +429,49 @@ typedef struct RtBsdfQuery {   /* device pointers; any output may be NULL (not w
     float   *le;               /* out [n][3] Intersection::Le(wo) (primitive.cpp:142-145, area.h: Lemit if Dot(dg.nn, wo) > 0) */
 } RtBsdfQuery;
 int rt_bsdf_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uint32_t n, const RtBsdfQuery *q);
+/* What EstimateDirect asks of a light (core/transport.cpp:123-193): Light::Sample_L, Light::Pdf, Light::Le and Light::IsDeltaLight, one query per
+ * (point, light) pair, computed with the render kernels' code (rt_shade.h).  With it a caller can write next-event estimation:
+ * light -> rt_trace_any_device(s_ray) -> rt_bsdf_device(f at wi = s_wi) -> f * s_L * |s_wi . ns| / s_pdf.
+ *  - Sampling forms.  With `nrm` the call is Sample_L(p, n, u1, u2, &wi, &pdf, &vis) and Pdf(p, n, wi), the forms EstimateDirect uses: area.cpp:58-72,
+ *    infinite.cpp:96-120 (a cosine-weighted direction about +-n), and for point, spot and distant lights the light.h:58-66 defaults, which drop n.
+ *    With nrm == NULL it is Sample_L(p, u1, u2, &wi, &pdf, &vis) and Pdf(p, wi): area.cpp:73-82, :93-95; infinite.cpp:121-131 (the uniform sphere,
+ *    no draw).  Whitted's Sample_L(p, &wi, &vis) and the emission form Sample_L(scene, u1..u4, &ray, &pdf) are not offered.
+ *  - The outputs are the reference's, unchanged: a sample with pdf == 0 or black L still returns its wi and ray, as Sample_L does; the caller applies
+ *    EstimateDirect's own test (transport.cpp:153).
+ *  - Delta lights (point.cpp:61-69, spot.cpp:79-86, distant.cpp:66-73) return s_pdf = 1 and pdf = 0 and ignore u.
+ *  - Shadow ray.  s_ray is VisibilityTester::r (light.h:78-83): SetSegment, {p, ps - p, RAY_EPSILON, 1 - RAY_EPSILON}, for point, spot and area
+ *    lights; SetRay, {p, wi, RAY_EPSILON, inf}, for distant and infinite lights.  It can be handed to rt_trace_any_device as it is.  The caller gets
+ *    visibility only: the transmittance of a medium along s_ray (VisibilityTester::Transmittance, light.cpp) is not computed.
+ *  - Random draws.  Two places draw one RandomFloat() each: ShapeSet::Sample (shape.h:115-121; emitters of more than one triangle) and the infinite
+ *    light's z flip (infinite.cpp:104).  They come from the keyed stream of camera sample `key` under `seed` (draw c of sample k is
+ *    pcg(c + pcg(k + seed * 0x9E3779B9)), as a frame derives it), starting at the supplied counter; s_draws says how far the stream moved.  A caller who
+ *    passes a camera sample's index and the counter the frame's integrator would be at reproduces the frame's draw.
+ *  - Le is Light::Le(ray(p, wi)) of that light alone: the infinite light's L (infinite.cpp:83-95), black for every other (light.cpp).
+ *  - A `light` outside [0, n_lights) gives zeros in every output.
+ *  - The light's type is read per query: a wavefront whose queries name lights of several types runs each type's code in turn, so callers do best to
+ *    group queries by light.
+ *  - Asynchronous on the scene's stream; no host copy, no wait, no workspace.  It is not a frame and it traces nothing: the film, the sample buffer,
+ *    the counters, rt_last_render_stats and rt_last_render_ms are untouched.
+ *  - Refused before any launch with RT_EINVAL (rt_last_error names the function and the field): a null scene; with n > 0 a null query, null p or null
+ *    light, a query with no output wanted, an s_* output wanted without u, pdf or le wanted without wi, an s_ray that is not 16-byte aligned; n above
+ *    2^30.  n == 0 is RT_OK and launches nothing. */
+typedef struct RtLightQuery {      /* device pointers unless said otherwise */
+    const float    *p;        /* in  [n][3] reference points                                              */
+    const float    *nrm;      /* in  [n][3] normal at p, or NULL: the forms without a normal              */
+    const int32_t  *light;    /* in  [n]    index into RtSceneDesc.lights (scene order)                   */
+    const float    *u;        /* in  [n][2] u1, u2; may be NULL if no s_* output is wanted                */
+    const uint32_t *rng;      /* in  [n][2] key, first counter of the keyed stream; NULL: key = i, 0      */
+    const float    *wi;       /* in  [n][3] unit directions for pdf / le; may be NULL if neither wanted   */
+    uint32_t        seed;     /* host value, the meaning of RtRenderDesc.seed                             */
+    float   *s_wi, *s_L;      /* out [n][3] Light::Sample_L(p, n, u1, u2, &wi, &pdf, &vis) / (p, u1, u2, ...) */
+    float   *s_pdf;           /* out [n]                                                                  */
+    RtRay   *s_ray;           /* out [n]    VisibilityTester::r (light.h:78-83): SetSegment or SetRay; 16-byte aligned */
+    int32_t *s_draws;         /* out [n]    RandomFloat() calls the sample made (0 or 1)                  */
+    float   *pdf;             /* out [n]    Light::Pdf(p, n, wi) / Pdf(p, wi)                             */
+    float   *le;              /* out [n][3] Light::Le(ray(p, wi)) of that light                           */
+    int32_t *is_delta;        /* out [n]    Light::IsDeltaLight()                                         */
+} RtLightQuery;
+int rt_light_device(RtScene *s, uint32_t n, const RtLightQuery *q);
 /* Camera::GenerateRay (core/camera.h:33-34; perspective.cpp:51-82, orthographic.cpp:48-79, environment.cpp:47-61) as rt_camera_rays, into
  * dev_rays[count]: the rays of camera samples first .. first + count - 1, bit for bit those of rt_camera_rays */
 int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays);

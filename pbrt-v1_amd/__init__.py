@@ -34,7 +34,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse",
 
 
 HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_mega_fsd.hip", "rt_mega_fsp.hip", "rt_mega_rw.hip", "rt_mega_rd.hip", "rt_mega_rp.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
-             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_bsdf.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
+             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_bsdf.hip", "rt_light.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
 def _include_closure(path, seen=None):
@@ -282,6 +282,16 @@ BSDF_FIELDS = ("f", "pdf", "s_wi", "s_f", "s_pdf", "s_type", "n_components", "le
 _BSDF_FIELD_SHAPE = {"f": (3, False), "pdf": (0, False), "s_wi": (3, False), "s_f": (3, False), "s_pdf": (0, False), "s_type": (0, True),
                      "n_components": (0, True), "le": (3, False)}
 
+
+class RtLightQuery(C.Structure):                   # include/pbrt_hip.h: device pointers (six inputs, eight outputs; NULL = not given / not wanted) and the host value seed
+    _fields_ = ([(n, C.c_void_p) for n in ("p", "nrm", "light", "u", "rng", "wi")] + [("seed", C.c_uint32)] +
+                [(n, C.c_void_p) for n in ("s_wi", "s_L", "s_pdf", "s_ray", "s_draws", "pdf", "le", "is_delta")])
+
+
+LIGHT_FIELDS = ("s_wi", "s_L", "s_pdf", "s_ray", "s_draws", "pdf", "le", "is_delta")      # DeviceScene.light(fields=...): name -> (columns, integer?)
+_LIGHT_FIELD_SHAPE = {"s_wi": (3, False), "s_L": (3, False), "s_pdf": (0, False), "s_ray": (8, False), "s_draws": (0, True), "pdf": (0, False),
+                      "le": (3, False), "is_delta": (0, True)}
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -330,7 +340,7 @@ def hip_lib():
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
                      "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
                      "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device",
-                     "rt_sample_positions_device", "rt_film_add_device", "rt_bsdf_device"):
+                     "rt_sample_positions_device", "rt_film_add_device", "rt_bsdf_device", "rt_light_device"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -348,6 +358,7 @@ def hip_lib():
         L.rt_trace_any_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
         L.rt_bsdf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtBsdfQuery)]
+        L.rt_light_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLightQuery)]
         L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_sample_positions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
@@ -1177,6 +1188,65 @@ class DeviceScene:
             if mine is not None:
                 cur.wait_stream(mine)
         return occ
+
+    def light(self, p, light, n=None, u=None, rng=None, wi=None, seed=None, fields=LIGHT_FIELDS) -> dict:
+        """What EstimateDirect asks of a light (rt_light_device): Light::Sample_L, Pdf, Le and IsDeltaLight at points in device memory.
+        p: float32 [m, 3] reference points; light: int32 [m] indices into the scene's lights (scene order; group queries by light for speed);
+        n: float32 [m, 3] normals at p -- given, the forms EstimateDirect uses (the infinite light samples a cosine about +-n), None: the forms
+        without a normal; u: float32 [m, 2] = u1, u2 (needed for the `s_*` fields); rng: uint32 (or int32 bit patterns) [m, 2] = key and first
+        counter of the keyed stream the sample's RandomFloat() comes from, None = (i, 0); wi: float32 [m, 3] unit directions (needed for `pdf`, `le`);
+        seed: None = the parsed frame's.  Returns per requested field a torch tensor on the device: `s_wi`, `s_L`, `le` float32 [m, 3], `s_pdf`, `pdf`
+        float32 [m], `s_ray` float32 [m, 8] (the shadow ray, ready for occluded()), `s_draws`, `is_delta` int32 [m].  Nothing of a frame is touched."""
+        import torch
+        fields = tuple(fields)
+        for f in fields:
+            if f not in _LIGHT_FIELD_SHAPE:
+                raise ValueError("fields: unknown field %r (known: %s)" % (f, ", ".join(LIGHT_FIELDS)))
+        if not fields:
+            raise ValueError("fields: at least one of %s is needed" % ", ".join(LIGHT_FIELDS))
+        if not isinstance(p, torch.Tensor):
+            raise ValueError("p: a torch tensor is needed, got %s" % type(p).__name__)
+        if p.dim() != 2:
+            raise ValueError("p: shape [m, 3] is needed, got %s" % (tuple(p.shape),))
+        m = int(p.shape[0])
+        self._check_query_tensor(torch, p, "p", m, 3, torch.float32, p)
+        self._check_query_tensor(torch, light, "light", m, 0, torch.int32, p)
+        if u is None and any(f.startswith("s_") for f in fields):
+            raise ValueError("u: needed for the fields s_wi, s_L, s_pdf, s_ray and s_draws")
+        if wi is None and ("pdf" in fields or "le" in fields):
+            raise ValueError("wi: needed for the fields pdf and le")
+        if n is not None:
+            self._check_query_tensor(torch, n, "n", m, 3, torch.float32, p)
+        if u is not None:
+            self._check_query_tensor(torch, u, "u", m, 2, torch.float32, p)
+        if wi is not None:
+            self._check_query_tensor(torch, wi, "wi", m, 3, torch.float32, p)
+        if rng is not None:
+            if isinstance(rng, torch.Tensor) and rng.dtype == torch.int32:
+                self._check_query_tensor(torch, rng, "rng", m, 2, torch.int32, p)
+            else:
+                self._check_query_tensor(torch, rng, "rng", m, 2, getattr(torch, "uint32", torch.int32), p)
+        if not p.is_cuda:
+            raise ValueError("p: a tensor in device memory is needed, got one on %s" % p.device)
+        d = getattr(self, "_device", None)
+        if d is not None and d >= 0 and p.device.index != d:
+            raise ValueError("p: the tensor is on %s, the scene on device %d" % (p.device, d))
+        if seed is None:
+            seed = self.parsed.render_view()["seed"]
+        dev = p.device
+        out = {f: (torch.empty(m, dtype=torch.int32 if _LIGHT_FIELD_SHAPE[f][1] else torch.float32, device=dev) if not _LIGHT_FIELD_SHAPE[f][0]
+                   else torch.empty((m, _LIGHT_FIELD_SHAPE[f][0]), dtype=torch.float32, device=dev)) for f in fields}
+        if m:
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            q = RtLightQuery(p=ptr(p), nrm=ptr(n), light=ptr(light), u=ptr(u), rng=ptr(rng), wi=ptr(wi), seed=int(seed) & 0xFFFFFFFF,
+                             **{f: t.data_ptr() for f, t in out.items()})
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_light_device(self._s, m, C.byref(q)))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return out
 
     def radiance(self, rays, first: int = 0):
         """Scene::Li for rays in device memory (rt_radiance_device): a float32 [n, 4] torch tensor (L.r, L.g, L.b, alpha) on the scene's device.

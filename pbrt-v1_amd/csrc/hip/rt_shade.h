@@ -639,6 +639,8 @@ RT_DEV V3 infinite_sample_cosine(V3 n, float u1, float u2, RNG &rng, float &pdf)
 }
 // Pdf(p, n, wi) :117-120
 RT_DEV float infinite_pdf_cosine(V3 n, V3 wi) { return absdot3(n, wi) * RT_INV_TWOPI; }
+// Pdf(p, wi) :129-131 (rt_light.hip: no frame asks the form without a normal)
+RT_DEV float infinite_pdf_sphere() { return 1.f / (4.f * RT_PI); }
 // Sample_L(p, u1, u2, wi, pdf, vis) :121-128: UniformSampleSphere (mc.cpp:74-81), pdf = UniformSpherePdf() = 1 / (4 pi) (mc.cpp:82-84; Pdf(p, wi) :129-131)
 RT_DEV V3 infinite_sample_sphere(float u1, float u2, float &pdf) {
     const float z = 1.f - 2.f * u1;
