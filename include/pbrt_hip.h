@@ -440,8 +440,8 @@ int rt_bsdf_device(RtScene *s, const RtRay *dev_rays, const RtHit *dev_hits, uin
  *    EstimateDirect's own test (transport.cpp:153).
  *  - Delta lights (point.cpp:61-69, spot.cpp:79-86, distant.cpp:66-73) return s_pdf = 1 and pdf = 0 and ignore u.
  *  - Shadow ray.  s_ray is VisibilityTester::r (light.h:78-83): SetSegment, {p, ps - p, RAY_EPSILON, 1 - RAY_EPSILON}, for point, spot and area
- *    lights; SetRay, {p, wi, RAY_EPSILON, inf}, for distant and infinite lights.  It can be handed to rt_trace_any_device as it is.  The caller gets
- *    visibility only: the transmittance of a medium along s_ray (VisibilityTester::Transmittance, light.cpp) is not computed.
+ *    lights; SetRay, {p, wi, RAY_EPSILON, inf}, for distant and infinite lights.  It can be handed to rt_trace_any_device as it is.  The transmittance
+ *    of a medium along s_ray (VisibilityTester::Transmittance, light.cpp) is rt_medium_device's `tr` of that ray, below.
  *  - Random draws.  Two places draw one RandomFloat() each: ShapeSet::Sample (shape.h:115-121; emitters of more than one triangle) and the infinite
  *    light's z flip (infinite.cpp:104).  They come from the keyed stream of camera sample `key` under `seed` (draw c of sample k is
  *    pcg(c + pcg(k + seed * 0x9E3779B9)), as a frame derives it), starting at the supplied counter; s_draws says how far the stream moved.  A caller who
@@ -472,6 +472,58 @@ typedef struct RtLightQuery {      /* device pointers unless said otherwise */
     int32_t *is_delta;        /* out [n]    Light::IsDeltaLight()                                         */
 } RtLightQuery;
 int rt_light_device(RtScene *s, uint32_t n, const RtLightQuery *q);
+/* What an integrator asks of the participating medium (scene->volumeRegion) and of the volume integrator, one query per row, computed with the
+ * render kernels' code (rt_integrate.h).  With it a caller's next-event estimation holds in a scene with a Volume:
+ * ... * s_L * tr(s_ray) ..., and Scene::Li's T * Lo + Lv (core/scene.cpp:120-126) can be had factor by factor.
+ *  - Point outputs.  VolumeRegion::sigma_a / sigma_s / sigma_t / Lve / p at p (with w, wp for the phase function).  A homogeneous region
+ *    (homogeneous.cpp:47-62) tests extent.Inside(WorldToVolume(p)) for all five; a density region (core/volume.h:62-90 with exponential.cpp /
+ *    volumegrid.cpp Density) scales the constants by Density(WorldToVolume(p)), and its p() is PhaseHG without an inside test.
+ *  - hit, t01.  VolumeRegion::IntersectP(ray, &t0, &t1); t01 is 0, 0 where hit is 0.
+ *  - tau.  VolumeRegion::Tau(ray, step_size, u[i]): homogeneous.cpp:63-67 (step and offset ignored), core/volume.cpp:137-153.
+ *  - tr.  With `u` it is VolumeIntegrator::Transmittance(scene, ray, sample, alpha) with a sample: Exp(-Tau(ray, step_size, u[i])), no draw.  With
+ *    u == NULL it is Scene::Transmittance(ray) (scene.cpp:127-129; emission.cpp:47-59, single.cpp:48-56): step 4.f * step_size and, as offset, one
+ *    RandomFloat() of the keyed stream at the caller's counter -- drawn for a homogeneous region too, which ignores it.
+ *  - lv.  EmissionIntegrator::Li(scene, ray, sample, alpha) (emission.cpp:60-95) with a sample whose scatter value is u_scatter[i]: one RandomFloat()
+ *    per step for the step's Tau (at .5f * step_size), the Russian-roulette draw when Tr.y() < 1e-3, all from the keyed stream at the caller's
+ *    counter.  The ray is taken as given (a frame hands over camera rays cut at their hits).  SingleScattering::Li is not offered: its shadow rays
+ *    make it a frame's job (rt_radiance_device).
+ *  - Random draws.  As for rt_light_device: draw c of key k under `seed`; rng == NULL means key = i, counter 0.  tr (without u) and lv each start at
+ *    the caller's counter; draws is the larger of the two advances.
+ *  - A scene without a medium gives tr = 1, 0 in every other float output, hit = 0, and draws = 1 where tr without u was asked, else 0: what
+ *    Transmittance returns for a null volumeRegion -- nothing else is ever asked of one.
+ *  - Every march ends.  Before any launch the call refuses (RT_EINVAL) a step_size that is not positive and finite, and one for which the volume's
+ *    diagonal takes more than 2^20 Tau samples or more than 65536 march steps: rt_render's limits, and the kernel's loop caps.  Per query, after
+ *    clipping, a march cannot advance when t + step == t at the larger in magnitude of t0, t1 for the smallest step the query uses (.5f * step_size
+ *    with lv, step_size with tau or u, else 4.f * step_size); an unusable ray (a non-finite o or d, d == 0, a NaN mint or maxt) and a clipped interval
+ *    that is not finite count the same.  Such a query gets 0 in tau, tr and lv and bit 0 (RT_MEDIUM_NO_ADVANCE) in status.  Bit 1
+ *    (RT_MEDIUM_TOO_LONG): lv along a ray whose direction is so short that the march would take more than 65536 steps; lv is 0.  Other queries are
+ *    unaffected.  maxt = +inf and mint > maxt are ordinary rays.
+ *  - Asynchronous on the scene's stream; no host copy, no wait, no workspace.  It is not a frame: the film, the sample buffer, the counters,
+ *    rt_last_render_stats and rt_last_render_ms are untouched, and a later rt_render gives the film it gave before.
+ *  - Refused before any launch with RT_EINVAL (rt_last_error names the function and the field): a null scene; with n > 0 a null query, a query with
+ *    no output wanted, a point output without p, phase without w or wp, a ray output without rays, rays that are not 16-byte aligned, tau without
+ *    u, lv without u_scatter, lv with volume_integrator == RT_VOLUME_SINGLE, the step limits above; n above 2^30.  n == 0 is RT_OK and
+ *    launches nothing. */
+enum { RT_MEDIUM_NO_ADVANCE = 1, RT_MEDIUM_TOO_LONG = 2 };
+typedef struct RtMediumQuery {     /* device pointers unless said otherwise; any output may be NULL (not wanted) */
+    const float    *p;         /* in  [n][3] points; may be NULL if no point output is wanted                  */
+    const float    *w, *wp;    /* in  [n][3] directions of the phase function; may be NULL if phase is not wanted */
+    const RtRay    *rays;      /* in  [n]    16-byte aligned; may be NULL if no ray output is wanted           */
+    const float    *u;         /* in  [n]    Tau's offset, or NULL: tr is Scene::Transmittance(ray)            */
+    const float    *u_scatter; /* in  [n]    the emission march's start offset; may be NULL if lv is not wanted */
+    const uint32_t *rng;       /* in  [n][2] key, first counter of the keyed stream; NULL: key = i, 0          */
+    uint32_t        seed;      /* host value, the meaning of RtRenderDesc.seed                                 */
+    float           step_size; /* host value, the volume integrator's stepsize                                 */
+    int32_t         volume_integrator; /* host value, RT_VOLUME_*: read for lv only                            */
+    float   *sigma_a, *sigma_s, *sigma_t, *lve;   /* out [n][3]                                                */
+    float   *phase;            /* out [n]    VolumeRegion::p(p, w, wp)                                         */
+    int32_t *hit;              /* out [n]    IntersectP                                                        */
+    float   *t01;              /* out [n][2] t0, t1                                                            */
+    float   *tau, *tr, *lv;    /* out [n][3]                                                                   */
+    int32_t *draws;            /* out [n]    how far the keyed stream moved                                    */
+    int32_t *status;           /* out [n]    RT_MEDIUM_* bits                                                  */
+} RtMediumQuery;
+int rt_medium_device(RtScene *s, uint32_t n, const RtMediumQuery *q);
 /* Camera::GenerateRay (core/camera.h:33-34; perspective.cpp:51-82, orthographic.cpp:48-79, environment.cpp:47-61) as rt_camera_rays, into
  * dev_rays[count]: the rays of camera samples first .. first + count - 1, bit for bit those of rt_camera_rays */
 int rt_camera_rays_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, RtRay *dev_rays);
@@ -509,6 +561,12 @@ int rt_radiance_device(RtScene *s, const RtRenderDesc *rd, const RtRay *dev_rays
  * the scene's stream, no allocation, no copy, no wait.  Refused with RT_EINVAL before any launch: a null scene or description, a null or misaligned
  * pointer with count > 0, shard_count != 1, first + count beyond the frame's camera samples.  count == 0 is RT_OK and launches nothing. */
 int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, float *dev_xy);
+/* What the volume integrator of camera samples first .. first + count - 1 of the frame `rd` describes starts from, into dev_out[count][4] 32-bit
+ * words (16-byte aligned): the float value of its tau request (Sample::oneD[tauSampleOffset][0]), the float value of its scatter request
+ * (oneD[scatterSampleOffset][0]), the key of the sample's keyed stream, and the counter at which the integrators' RandomFloat() draws start.  With
+ * them rt_medium_device reproduces a frame's medium terms: u, u_scatter and rng.  Numbering, stream behaviour and refusals as for
+ * rt_sample_positions_device; also refused: a description rt_render refuses for its sample requests, and a frame that plans no volume requests. */
+int rt_volume_samples_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, uint32_t *dev_out);
 /* Film::AddSample (scene.cpp:76 -> film/image.cpp:103-142) for n radiances in device memory: the third stage of Scene::Render's loop, behind
  * rt_camera_rays_device and rt_radiance_device.  dev_L[n][4] = L.r, L.g, L.b, alpha (16-byte aligned; the layout rt_radiance_device writes).
  *  - For i = 0 .. n-1 the bound film receives what Scene::Render would hand it for camera sample first + i of the frame `rd` describes if its

@@ -34,7 +34,7 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-msse2", "-mfpmath=sse",
 
 
 HIP_UNITS = ("rt_kernels.hip", "rt_scene.hip", "rt_film.hip", "rt_trace.hip", "rt_mega_w.hip", "rt_mega_d.hip", "rt_mega_dw.hip", "rt_mega_p.hip", "rt_mega_b.hip", "rt_mega_g.hip", "rt_mega_f.hip", "rt_mega_fsd.hip", "rt_mega_fsp.hip", "rt_mega_rw.hip", "rt_mega_rd.hip", "rt_mega_rp.hip", "rt_pipe_w.hip", "rt_pipe_d.hip",
-             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_bsdf.hip", "rt_light.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
+             "rt_pipe_p.hip", "rt_pipe_v.hip", "rt_march.hip", "rt_rays.hip", "rt_bsdf.hip", "rt_light.hip", "rt_medium.hip", "rt_film_add.hip", "kd_build.cpp", "grid_build.cpp", "leaf_layout.cpp")
 
 
 def _include_closure(path, seen=None):
@@ -292,6 +292,19 @@ LIGHT_FIELDS = ("s_wi", "s_L", "s_pdf", "s_ray", "s_draws", "pdf", "le", "is_del
 _LIGHT_FIELD_SHAPE = {"s_wi": (3, False), "s_L": (3, False), "s_pdf": (0, False), "s_ray": (8, False), "s_draws": (0, True), "pdf": (0, False),
                       "le": (3, False), "is_delta": (0, True)}
 
+class RtMediumQuery(C.Structure):                  # include/pbrt_hip.h: seven input pointers, the host values seed, step_size and volume_integrator, twelve output pointers
+    _fields_ = ([(n, C.c_void_p) for n in ("p", "w", "wp", "rays", "u", "u_scatter", "rng")] +
+                [("seed", C.c_uint32), ("step_size", C.c_float), ("volume_integrator", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("sigma_a", "sigma_s", "sigma_t", "lve", "phase", "hit", "t01", "tau", "tr", "lv", "draws", "status")])
+
+
+MEDIUM_POINT_FIELDS = ("sigma_a", "sigma_s", "sigma_t", "lve", "phase")
+MEDIUM_RAY_FIELDS = ("hit", "t01", "tau", "tr", "lv", "draws", "status")
+MEDIUM_FIELDS = MEDIUM_POINT_FIELDS + MEDIUM_RAY_FIELDS      # DeviceScene.medium(fields=...): name -> (columns, integer?)
+_MEDIUM_FIELD_SHAPE = {"sigma_a": (3, False), "sigma_s": (3, False), "sigma_t": (3, False), "lve": (3, False), "phase": (0, False), "hit": (0, True),
+                       "t01": (2, False), "tau": (3, False), "tr": (3, False), "lv": (3, False), "draws": (0, True), "status": (0, True)}
+VOLUME_EMISSION, VOLUME_SINGLE = 1, 2            # RT_VOLUME_*
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("mint", np.float32), ("maxt", np.float32)])
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 
@@ -340,7 +353,7 @@ def hip_lib():
                      "rt_accel_build", "rt_accel_info", "rt_accel_copy", "rt_accel_destroy", "rt_scene_create_prebuilt", "rt_film_resolve_device",
                      "rt_film_resolve_device_rgba", "rt_film_pack_parts", "rt_accel_leaf_layout", "rt_scene_set_density", "rt_scene_set_textures", "rt_scene_set_light_transforms",
                      "rt_trace_closest_device", "rt_trace_any_device", "rt_hit_geometry_device", "rt_camera_rays_device", "rt_scene_get_stream", "rt_radiance_device",
-                     "rt_sample_positions_device", "rt_film_add_device", "rt_bsdf_device", "rt_light_device"):
+                     "rt_sample_positions_device", "rt_film_add_device", "rt_bsdf_device", "rt_light_device", "rt_medium_device", "rt_volume_samples_device"):
             getattr(L, name).restype = C.c_int
         L.rt_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.rt_scene_set_density.argtypes = [C.c_void_p, C.c_void_p]
@@ -359,6 +372,8 @@ def hip_lib():
         L.rt_hit_geometry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtHitGeometry)]
         L.rt_bsdf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtBsdfQuery)]
         L.rt_light_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtLightQuery)]
+        L.rt_medium_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RtMediumQuery)]
+        L.rt_volume_samples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_camera_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_radiance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
         L.rt_sample_positions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
@@ -1247,6 +1262,97 @@ class DeviceScene:
             if mine is not None:
                 cur.wait_stream(mine)
         return out
+
+    def medium(self, p=None, w=None, wp=None, rays=None, u=None, u_scatter=None, rng=None, seed=None, step_size=None, fields=MEDIUM_FIELDS) -> dict:
+        """What an integrator asks of the participating medium (rt_medium_device), one query per row.  p: float32 [n, 3] points (needed for
+        `sigma_a`, `sigma_s`, `sigma_t`, `lve`, `phase`); w, wp: float32 [n, 3] directions (needed for `phase`); rays: float32 [n, 8] (needed for
+        `hit`, `t01`, `tau`, `tr`, `lv`, `draws`, `status`); u: float32 [n] Tau's offset (needed for `tau`; given, `tr` is the volume integrator's
+        Transmittance with a sample, None: Scene::Transmittance(ray), which draws its offset); u_scatter: float32 [n] (needed for `lv`); rng: uint32
+        (or int32 bit patterns) [n, 2] = key and first counter of the keyed stream, None = (i, 0); seed, step_size: None = the parsed frame's.
+        Returns per requested field a torch tensor on the device: float32 [n, 3] (`t01` [n, 2], `phase` [n]), `hit`, `draws`, `status` int32 [n].
+        `lv` is EmissionIntegrator::Li; a frame under VolumeIntegrator "single" is refused for it.  Nothing of a frame is touched."""
+        import torch
+        fields = tuple(fields)
+        for f in fields:
+            if f not in _MEDIUM_FIELD_SHAPE:
+                raise ValueError("fields: unknown field %r (known: %s)" % (f, ", ".join(MEDIUM_FIELDS)))
+        if not fields:
+            raise ValueError("fields: at least one of %s is needed" % ", ".join(MEDIUM_FIELDS))
+        want_point = any(f in MEDIUM_POINT_FIELDS for f in fields)
+        want_ray = any(f in MEDIUM_RAY_FIELDS for f in fields)
+        if want_point and p is None:
+            raise ValueError("p: needed for the fields %s" % ", ".join(MEDIUM_POINT_FIELDS))
+        if "phase" in fields and (w is None or wp is None):
+            raise ValueError("w, wp: needed for the field phase")
+        if want_ray and rays is None:
+            raise ValueError("rays: needed for the fields %s" % ", ".join(MEDIUM_RAY_FIELDS))
+        if "tau" in fields and u is None:
+            raise ValueError("u: needed for the field tau")
+        if "lv" in fields and u_scatter is None:
+            raise ValueError("u_scatter: needed for the field lv")
+        like = rays if rays is not None else p
+        if not isinstance(like, torch.Tensor):
+            raise ValueError("%s: a torch tensor is needed, got %s" % ("rays" if rays is not None else "p", type(like).__name__))
+        first = "rays" if rays is not None else "p"
+        if like.dim() != 2:
+            raise ValueError("%s: shape [n, %d] is needed, got %s" % (first, 8 if rays is not None else 3, tuple(like.shape)))
+        m = int(like.shape[0])
+        for t, name, cols in ((rays, "rays", 8), (p, "p", 3), (w, "w", 3), (wp, "wp", 3), (u, "u", 0), (u_scatter, "u_scatter", 0)):
+            if t is not None:
+                self._check_query_tensor(torch, t, name, m, cols, torch.float32, like)
+        if rng is not None:
+            if isinstance(rng, torch.Tensor) and rng.dtype == torch.int32:
+                self._check_query_tensor(torch, rng, "rng", m, 2, torch.int32, like)
+            else:
+                self._check_query_tensor(torch, rng, "rng", m, 2, getattr(torch, "uint32", torch.int32), like)
+        if not like.is_cuda:
+            raise ValueError("%s: a tensor in device memory is needed, got one on %s" % (first, like.device))
+        d = getattr(self, "_device", None)
+        if d is not None and d >= 0 and like.device.index != d:
+            raise ValueError("%s: the tensor is on %s, the scene on device %d" % (first, like.device, d))
+        view = self.parsed.render_view()
+        if seed is None:
+            seed = view["seed"]
+        if step_size is None:
+            step_size = view["step_size"]
+        dev = like.device
+        out = {f: (torch.empty(m, dtype=torch.int32 if _MEDIUM_FIELD_SHAPE[f][1] else torch.float32, device=dev) if not _MEDIUM_FIELD_SHAPE[f][0]
+                   else torch.empty((m, _MEDIUM_FIELD_SHAPE[f][0]), dtype=torch.float32, device=dev)) for f in fields}
+        if m:
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            q = RtMediumQuery(p=ptr(p), w=ptr(w), wp=ptr(wp), rays=ptr(rays), u=ptr(u), u_scatter=ptr(u_scatter), rng=ptr(rng),
+                              seed=int(seed) & 0xFFFFFFFF, step_size=float(step_size), volume_integrator=int(view["volume_integrator"]),
+                              **{f: t.data_ptr() for f, t in out.items()})
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_medium_device(self._s, m, C.byref(q)))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return out
+
+    def volume_samples(self, first: int, count: int) -> dict:
+        """rt_volume_samples_device: what the volume integrator of camera samples first .. first + count - 1 of the parsed frame starts from, as torch
+        tensors on the scene's device: `u` float32 [count] (the tau request's value), `u_scatter` float32 [count] (the scatter request's) and `rng`
+        int32 [count, 2] (the bit patterns of the stream's key and of the counter at which the integrators' draws start) -- medium()'s arguments
+        of those names."""
+        import torch
+        if first < 0 or count < 0:
+            raise ValueError("volume_samples: first and count must not be negative")
+        if not torch.cuda.is_available():
+            raise RtError("torch sees no HIP device.  torch carries a HIP runtime of its own and the first one a process loads serves both: "
+                          "import torch before this package loads libpbrt_hip.so (before the first DeviceScene), as bench.py does")
+        d = getattr(self, "_device", -1)
+        dev = torch.device("cuda", d if d is not None and d >= 0 else torch.cuda.current_device())
+        words = torch.empty((int(count), 4), dtype=torch.int32, device=dev)
+        if count:
+            cur, mine = self._scene_stream(torch, dev)
+            if mine is not None:
+                mine.wait_stream(cur)
+            _chk(hip_lib().rt_volume_samples_device(self._s, self.parsed.render_desc, int(first), int(count), C.c_void_p(words.data_ptr())))
+            if mine is not None:
+                cur.wait_stream(mine)
+        return {"u": words[:, 0].view(torch.float32).contiguous(), "u_scatter": words[:, 1].view(torch.float32).contiguous(), "rng": words[:, 2:4].contiguous()}
 
     def radiance(self, rays, first: int = 0):
         """Scene::Li for rays in device memory (rt_radiance_device): a float32 [n, 4] torch tensor (L.r, L.g, L.b, alpha) on the scene's device.

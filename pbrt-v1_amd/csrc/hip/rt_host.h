@@ -288,5 +288,7 @@ int film_gather_launch(RtScene *s, const rt::DevFrame &fr, const FilmGather &g, 
 // ---- a film add (rt_film_add.hip): the image positions of camera samples [first, first + count) of the frame bound to `fr` (with dev_L: its bad
 // radiances counted), and ImageFilm::AddSample for such a range over the film rows plan::plan_film_add found, both on the scene's stream
 int sample_positions_launch(RtScene *s, const rt::DevFrame &fr, unsigned long long first, unsigned count, float *dev_xy, const float *dev_L);
+// ---- rt_volume_samples_device (rt_medium.hip): per camera sample of [first, first + count) the frame's tau and scatter values, the stream's key and its counter
+int volume_samples_launch(RtScene *s, const rt::DevFrame &fr, unsigned long long first, unsigned count, uint32_t *dev_out);
 int film_add_form(const rt::plan::FilmAdd &p, bool &packed);       // which of the gather's two forms (PBRT_HIP_FILM_ADD forces one), before any launch
 int film_add_launch(RtScene *s, const RtRenderDesc &rd, const rt::plan::FilmAdd &p, bool packed, unsigned long long first, unsigned n, const float *dev_L, const float *dev_xy);

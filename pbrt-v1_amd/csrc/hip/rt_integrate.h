@@ -484,7 +484,9 @@ RT_DEV float density_at(const DevScene &sc, V3 q) {
 // clipped against the extent in volume space, then tau += sigma_t(rn(t0)) every `step` from t0 + u * step while t0 < t1; returns tau * step.
 // sigma_t(p) = Density(WorldToVolume(p)) * (sig_a + sig_s).  The loop is also capped at DevFrame::dens_cap samples (rt_render bounds the march by
 // the volume's world diagonal and refuses frames where t + step would not advance): a value that slips through ends the loop instead of spinning.
-RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float mint, float maxt, float step, float u) {
+// `cap_of`: where the cap comes from, asked where the loop starts -- a frame's descriptor below, a kernel argument in rt_medium.hip.
+template <class CAP>
+RT_DEV V3 density_tau_capped(const DevScene &sc, CAP cap_of, V3 o, V3 d, float mint, float maxt, float step, float u) {
     const float length = len3(d);
     if (length == 0.f) return mk3(0.f);
     const float inv = 1.f / length;
@@ -494,7 +496,7 @@ RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float 
     const V3 sig_t = mat_color(sc.vol.sigma_a) + mat_color(sc.vol.sigma_s);
     V3 tau = mk3(0.f);
     t0 += u * step;
-    const int cap = fr.dens_cap;
+    const int cap = cap_of();
 #pragma unroll 1
     for (int k = 0; t0 < t1 && k < cap; ++k) {
         const float D = density_at(sc, xform_point(sc.vol.world_to_volume, o + dn * t0));
@@ -502,6 +504,9 @@ RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float 
         t0 += step;
     }
     return tau * step;
+}
+RT_DEV V3 density_tau(const DevScene &sc, const DevFrame &fr, V3 o, V3 d, float mint, float maxt, float step, float u) {
+    return density_tau_capped(sc, [&fr] { return fr.dens_cap; }, o, d, mint, maxt, step, u);
 }
 RT_DEV V3 exp_neg(V3 tau) { return mk3(rt_expf(-tau.x), rt_expf(-tau.y), rt_expf(-tau.z)); }       // Exp(-tau)
 

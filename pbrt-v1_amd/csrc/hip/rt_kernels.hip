@@ -633,6 +633,26 @@ int rt_sample_positions_device(RtScene *s, const RtRenderDesc *rd, uint64_t firs
     if (first > samples || count > samples - first) return fail(RT_EINVAL, fn + ": first + count is beyond the frame's camera samples");
     return sample_positions_launch(s, fr, first, count, dev_xy, nullptr);
 }
+// The volume integrator's two sampler values, the stream key and the counter of camera samples first .. first + count - 1 into the caller's DEVICE
+// buffer (include/pbrt_hip.h): the frame of rt_sample_positions_device with the frame's sample requests bound (plan_requests; nothing is uploaded).
+int rt_volume_samples_device(RtScene *s, const RtRenderDesc *rd, uint64_t first, uint32_t count, uint32_t *dev_out) {
+    static const std::string fn = "rt_volume_samples_device";
+    int rc;
+    if ((rc = refuse_null(fn, s, "scene")) || (rc = refuse_null(fn, rd, "render description")) || (count > 0 && (rc = refuse_null(fn, dev_out, "output pointer")))) return rc;
+    if (count > 0 && (rc = refuse_unaligned16(fn, dev_out, "dev_out"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    DevFrame fr; if ((rc = camera_frame(rd, fr))) return rc;
+    if (fr.shard_count != 1) return fail(RT_EINVAL, fn + ": shard_count != 1 (the samples are addressed as the camera samples of the whole frame: one shard only)");
+    const unsigned long long samples = fr.total_pixels * (unsigned long long)fr.spp;
+    if (first > samples || count > samples - first) return fail(RT_EINVAL, fn + ": first + count is beyond the frame's camera samples");
+    plan::Requests rq;
+    if (plan::Refusal r = plan::plan_requests(*rd, s->facts, fr.spp, rq)) return fail(r.code, r.msg);
+    if (rq.n1d < 2) return fail(RT_EINVAL, fn + ": the frame plans no volume requests");
+    fr.n1d = rq.n1d; fr.n2d = rq.n2d; fr.lhs_total = rq.lhs_total; fr.pixgen_draws = rq.pixgen_draws;
+    std::memcpy(fr.one_d, rq.one_d, sizeof fr.one_d); std::memcpy(fr.two_d, rq.two_d, sizeof fr.two_d);
+    if (count == 0) return RT_OK;
+    return volume_samples_launch(s, fr, first, count, dev_out);
+}
 // Film::AddSample for radiances in device memory (include/pbrt_hip.h): binds what plan::plan_film_add plans -- the range's image positions into the
 // call's own staging buffer (with the scene counting: the bad radiances counted on the way), then the gather over the film rows the range reaches.
 // Nothing of the last rt_render but the film is touched: no sample buffer, no events, no LastLaunch.
